@@ -25,7 +25,11 @@ in HBM.  Timed with a barrier + torch.cuda.synchronize() on both sides, max
 over ranks.  The per-kernel figures of the `roofline` object come from HIP
 events recorded by the engine on the launch stream inside the same timed steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.
+--full adds everything else this file measures or checks (the parity gate against the oracle, the CPU baseline, the
+other configurations, the Node-hosted runs, the audio stage, the counter passes, ...).
 """
 import argparse
 import ctypes
@@ -124,6 +128,30 @@ def host_cores():
     except (OSError, ValueError):
         pass
     return n, info
+
+
+def dump_outputs(b, out_dir, samples=4, seed=0):
+    """What the last decode left for a caller of the batch, as .npy files of float64 / float32 (< 64 MB in all): every
+    picture's (stream, es_offset, type, decoded) and its 64-bit plane hash in two exact 32-bit halves, and the Y / Cr / Cb
+    planes of `samples` pictures drawn with a fixed seed (flat rows of luma_bytes / chroma_bytes, coded size)."""
+    os.makedirs(out_dir, exist_ok=True)
+    pics = b.pictures()
+    n = len(pics)
+    info = np.array([[p.stream, p.es_offset, p.type, p.decoded] for p in pics], dtype=np.float64).reshape(n, 4)
+    h = b.frame_hashes().astype(np.uint64)
+    per_picture = (b.luma_bytes + 2 * b.chroma_bytes) * 4
+    k = max(1, min(samples, n, (48 << 20) // per_picture))
+    pick = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+    ys = np.empty((k, b.luma_bytes), np.float32)
+    crs, cbs = np.empty((k, b.chroma_bytes), np.float32), np.empty((k, b.chroma_bytes), np.float32)
+    for i, p in enumerate(pick):
+        ys[i], crs[i], cbs[i] = b.read_frame(int(p))
+    out = {"picture_info": info, "frame_hash_hi": (h >> np.uint64(32)).astype(np.float64),
+           "frame_hash_lo": (h & np.uint64(0xFFFFFFFF)).astype(np.float64), "sample_pictures": pick.astype(np.float64),
+           "sample_y": ys, "sample_cr": crs, "sample_cb": cbs}
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    log("outputs of the last step: %d pictures' info and hashes, the planes of pictures %s -> %s" % (n, pick.tolist(), out_dir))
 
 
 def cpu_baseline(sample_streams, width, height):
@@ -532,7 +560,7 @@ def counters_in_this_run(args, n_streams, frames):
     out = {"fetch_bytes": {}, "write_bytes": {}, "valu": {}, "dispatches": {}}
     child = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--streams", str(n_streams), "--frames", str(frames),
              "--no-cpu-baseline", "--no-other-configs", "--no-h2d", "--no-audio", "--no-napi", "--no-counters"]
-    env = dict(os.environ, TMPDIR="/tmp", JSMPEG_BENCH_PARITY_STREAMS="0")     # the child's gate: one stream (the parent gated them all)
+    env = dict(os.environ, TMPDIR="/tmp")     # the child is a plain run, without the gate (the parent gated every stream)
     with tempfile.TemporaryDirectory(dir="/tmp") as td:
         for counters, key in ((("FETCH_SIZE",), "fetch_bytes"), (("WRITE_SIZE",), "write_bytes"), (("SQ_INSTS_VALU",), "valu")):
             d = os.path.join(td, key)
@@ -571,14 +599,25 @@ def main():
                     help="testing: run the multi-rank code path (GOP units, RCCL scatter / all-gather) with the ranks present, even one")
     ap.add_argument("--no-h2d", action="store_true", help="skip the extra run that starts every step from host memory (value_incl_h2d)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the witnessed timings of the other BASELINE.json configurations (other_configs)")
-    ap.add_argument("--two-batches", action="store_true", help="report two_batches_in_flight even with --no-other-configs (it is part of the default line)")
+    ap.add_argument("--two-batches", action="store_true", help="with --full: report two_batches_in_flight even with --no-other-configs (it is part of the --full line)")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="TEST MODE, never a measurement: the N ranks of --gpus N share the visible device(s) and the compressed units travel "
                          "over the control plane (gloo) instead of RCCL -- every line of the N > 1 program runs, on a box with one GPU")
     ap.add_argument("--no-napi", action="store_true", help="skip the Node-hosted run of the same batch (value_via_napi)")
     ap.add_argument("--no-counters", action="store_true", help="skip the rocprofv3 --pmc passes over two steps of this same program (roofline.traffic measured in this run)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the parity gate against the oracle, the CPU baseline, the host-memory variant, two batches "
+                         "in flight, the Node-hosted run, the other configurations, coded video, live ticks, the audio stage, the device copy probe "
+                         "and the counter passes (each --no-* flag still leaves its part out).  Without it a run sets up, warms up, times the "
+                         "steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, < 64 MB): every "
+                         "picture's info and plane hash, and the planes of a few pictures chosen by a fixed seed (rank 0's batch at N > 1)")
     args = ap.parse_args()
     args.h2d = False
+    if not args.full:
+        args.no_cpu_baseline = args.no_audio = args.no_h2d = args.no_other_configs = args.no_napi = args.no_counters = True
+        args.two_batches = False
     # rehearsals and --force-dist tests only: another BASELINE configuration's content as the workload (configs[4]'s 3840x2160
     # at its stated 128 streams over 8 ranks) -- the headline's workload is not selectable
     global CONFIG
@@ -929,9 +968,13 @@ def main():
     gate_scrub = dict(scrub)
     gate_scrub.pop("events", None)
     uncovered = b.counters()["uncovered_pictures"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(b, args.dump_outputs)
 
-    # ---- parity gate against the oracle (checker only) ----
-    lib_oracle = build.LIB_ORACLE if os.path.exists(build.LIB_ORACLE) else build.build_oracle()
+    # ---- parity gate against the oracle (checker only): --full, and at N > 1 always (it resolves the cross-rank history
+    # of the units that need it, which the N > 1 headline reports) ----
+    gated = args.full or multi
+    lib_oracle = build.LIB_ORACLE if not gated or os.path.exists(build.LIB_ORACLE) else build.build_oracle()
     check = list(range(n_streams)) if not os.environ.get("JSMPEG_BENCH_PARITY_STREAMS") else \
         [int(x) for x in os.environ["JSMPEG_BENCH_PARITY_STREAMS"].split(",")]
     oracle_cache = {}            # what the oracle says is decoded once per stream / unit, whatever the mode that is checked
@@ -1075,7 +1118,7 @@ def main():
             raise SystemExit("rank %d: PARITY FAILURE (%s) against the oracle on streams %r -- no number reported" % (rank, what, sorted(failed, key=repr)))
         return deviating[0]
 
-    deviating = parity_gate(X["units_of_rank"] if multi else None, "single source" if multi else "whole streams")
+    deviating = parity_gate(X["units_of_rank"] if multi else None, "single source" if multi else "whole streams") if gated else 0
 
     # ---- N > 1: the same job with every rank ingesting its own streams (only the imbalance travels), its own timed run
     # and its own parity gate; reported beside the headline, never as `value` ----
@@ -1199,24 +1242,25 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- what this GPU's HBM gives a plain kernel with k_recon's traffic mix (half reads, half writes): a device copy ----
+    # ---- what this GPU's HBM gives a plain kernel with k_recon's traffic mix (half reads, half writes): a device copy (--full) ----
     copy_gbs = None
-    try:
-        src = torch.empty(1 << 31, dtype=torch.uint8, device=dev)     # far beyond the 256 MB memory-side cache
-        dst = torch.empty_like(src)
-        src.fill_(1)
-        dst.copy_(src)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(4):
+    if args.full:
+        try:
+            src = torch.empty(1 << 31, dtype=torch.uint8, device=dev)     # far beyond the 256 MB memory-side cache
+            dst = torch.empty_like(src)
+            src.fill_(1)
             dst.copy_(src)
-        e1.record()
-        torch.cuda.synchronize()
-        copy_gbs = round(4 * 2 * (1 << 31) / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
-        del src, dst
-    except Exception as e:  # a reported reference point, never fatal
-        log("copy probe failed: %r" % (e,))
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(4):
+                dst.copy_(src)
+            e1.record()
+            torch.cuda.synchronize()
+            copy_gbs = round(4 * 2 * (1 << 31) / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
+            del src, dst
+        except Exception as e:  # a reported reference point, never fatal
+            log("copy probe failed: %r" % (e,))
 
     # ---- accounting: ES read once + planes written once + predicted MBs read once ----
     g_streams = n_streams * world
@@ -1326,7 +1370,7 @@ def main():
     # workload: profiles/r03_recon_notes.md) priced in the same bytes -- VALU issue bounds the kernel below its memory side
     skeleton_ms_per_level = 0.686
     ceilings = {"device_copy": round(copy_gbs / HBM_PEAK_GBS, 4) if copy_gbs else None,
-                "device_copy_source": "measured in this run (device_copy_measured)",
+                "device_copy_source": "measured in this run (device_copy_measured)" if copy_gbs else "not measured: bench.py --full runs the probe",
                 "valu_skeleton": round(alg_bytes_rank / max(1, levels) / (skeleton_ms_per_level * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
                 if dom["kernel"] == "k_recon" and n_streams == STREAMS_PER_GPU and frames == FRAMES_PER_STREAM else None,
                 "valu_skeleton_source": "static: %.3f ms per level for the kernel without its prediction loads and plane stores "
@@ -1373,8 +1417,9 @@ def main():
                                    ("(stream, GOP) units sharded over %d rank(s): every rank ingests its own streams, the rebalancing plan's units "
                                     "travel rank to rank (one RCCL group per step) beside the previous step's kernels" % world)) if multi else "one rank, whole streams"},
         "mpixel_per_s": round(fps * width * height / 1e6, 1),
-        "parity_checked": ("every unit of every stream of every rank against the oracle fed the same unit (%d streams x %d pictures per rank)"
-                           if multi else "every stream of every rank (%d x %d pictures per rank), device hash == oracle") % (len(check), frames),
+        "parity_checked": (("every unit of every stream of every rank against the oracle fed the same unit (%d streams x %d pictures per rank)"
+                            if multi else "every stream of every rank (%d x %d pictures per rank), device hash == oracle") % (len(check), frames))
+                          if gated else "not checked in this run: bench.py --full gates every stream against the oracle",
         "parity_gate": {"pool_overwritten_before_timed_region": True, "frames_overwritten_before_last_timed_step": gate_scrub["frames"],
                         "of_frames": n_pictures, "fill_ms_inside_timed_region": round(gate_scrub["ms"], 3),
                         "note": "the gate hashes the pool once, after the last timed step: every plane it sees was written inside the "

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -13,9 +14,9 @@ from conftest import ROOT
 pytestmark = pytest.mark.gpu
 
 
-def run_bench(*args):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--streams", "8", "--frames", "24", "--steps", "2", "--warmup", "1",
-                        "--no-audio", "--no-other-configs", "--no-h2d"] + list(args), capture_output=True, text=True, timeout=900)
+def run_bench(*args, full=True):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--streams", "8", "--frames", "24", "--steps", "2", "--warmup", "1"]
+                       + (["--full", "--no-audio", "--no-other-configs", "--no-h2d"] if full else []) + list(args), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, "stdout must carry exactly one JSON line: %r" % lines[:3]
@@ -36,6 +37,26 @@ def test_one_rank_line():
     assert abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3 and rf["avg_launch_ms"] > 0
     assert rf["reconstruct"]["status"] == 0 and set(rf["ceiling_frac"]) >= {"device_copy", "valu_skeleton"}
     assert d["parity_gate"]["pool_overwritten_before_timed_region"] is True
+
+
+def test_plain_line_and_its_outputs(tmp_path):
+    """without --full: the headline alone (no gate, no extras), the steps it was asked for, and --dump-outputs writes the
+    last step's outputs -- the same from run to run"""
+    runs = []
+    for k in range(2):
+        d = run_bench("--steps", "3", "--dump-outputs", str(tmp_path / str(k)), full=False)
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+        assert abs(d["value"] - d["config"]["pictures_per_step"] * 1e3 / d["ms_per_step"]) < 1e-3 * d["value"] + 1
+        assert d["cpu_baseline"] is None and "two_batches_in_flight" not in d and "value_via_napi" not in d and "audio_stage" not in d
+        files = sorted(os.listdir(tmp_path / str(k)))
+        assert "frame_hash_hi.npy" in files and "sample_y.npy" in files
+        arrs = {f: np.load(tmp_path / str(k) / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) < 64 << 20
+        assert len(arrs["frame_hash_lo.npy"]) == d["config"]["pictures_per_step"]
+        runs.append(arrs)
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
 
 
 def test_multi_rank_path_with_the_ranks_present():
