@@ -310,7 +310,8 @@ class Batch:
         return [int(out[i]) for i in range(k)]
 
     def set_reconstruct(self, plan):
-        """0 / "levels": always one launch per dependency level; 1 / "auto": the engine's choice (include/jsmpeg_hip.h)"""
+        """0 / "levels": always one launch per dependency level; 1 / "auto": as the batch was created -- the engine's choice, or
+        JSMPEG_HIP_RECON_ORDER then; a batch whose ordered launch flagged itself stays level by level (include/jsmpeg_hip.h)"""
         fn = self.L.jsmpeg_hip_batch_set_reconstruct
         fn.restype = ctypes.c_int
         fn.argtypes = [ctypes.c_void_p, ctypes.c_int]

@@ -135,24 +135,17 @@ jsmpeg_hip_batch_t *batch_create(const jsmpeg_hip_batch_config_t *config, uint32
 		fail("no HIP device available: the MPEG-1 decode path has no CPU fallback");
 		return nullptr;
 	}
-	jsmpeg_hip_batch_t *b = new jsmpeg_hip_batch_t();
+	jsmpeg_hip_batch_t *b = new jsmpeg_hip_batch_t();   /* (value-initialised: every pointer, handle, count and flag starts at zero) */
 	b->cfg = *config;
-	b->d_es = nullptr; b->d_streams = nullptr; b->d_scan_state = nullptr; b->d_sc_pos = nullptr;
-	b->d_sc_code = nullptr; b->d_sc_owner = nullptr; b->d_pic_sc = nullptr; b->d_slice_sc = nullptr; b->d_slice_order = nullptr; b->d_order_hist = nullptr; b->d_counters = nullptr;
-	b->d_pics = nullptr; b->d_desc = nullptr; b->d_covered = nullptr; b->h_covered = nullptr; b->h_pics = nullptr; b->h_desc = nullptr; b->ev_cov = nullptr; b->ev_idx = nullptr; b->n_uncovered = 0;
-	b->d_done = nullptr; b->d_rstatus = nullptr; b->h_rstatus = nullptr; b->ordered = false; b->stats_pending = false; b->ordered_waits = 0; b->ordered_status = 0; b->last_group = 0;
-	{ const char *e = getenv("JSMPEG_HIP_RECON_ORDER"); b->order_group = e ? (uint32_t)atoi(e) : JM_ORDER_AUTO; }
-	{ const char *e = getenv("JSMPEG_HIP_RECON_DENSE"); b->dense_mode = e ? (atoi(e) ? 1 : 0) : -1; }   /* measurements / tests: 0 never, 1 always the dense intra form; read when a batch is created */
- b->desc_cap = 0; b->d_mb = nullptr; b->d_tokens = nullptr;
-	b->d_pool_alloc = nullptr; b->d_pool = nullptr; b->d_hashes = nullptr; b->h_counters = nullptr; b->d_dbg = nullptr; b->d_rgba = nullptr;
-	b->d_ts = nullptr; b->ts_cap = 0; b->d_ts_rec = nullptr; b->d_ts_es_off = nullptr; b->d_ts_cand = nullptr; b->d_ts_writes = nullptr; b->ts_pkt_cap = 0;
-	b->d_ts_begin = nullptr; b->d_ts_len = nullptr; b->d_ts_small = nullptr;
-	for (auto &e : b->ev) e = nullptr;
-	for (auto &e : b->ev_level) e = nullptr;
-	b->n_level_ev = 0;
-	b->epoch = 0; b->n_streams = 0; b->es_bytes = 0; b->n_sc = b->n_pics = b->n_levels = b->n_decoded = b->n_slices = b->n_slice_codes = 0;
-	b->timed = false; b->stream = nullptr; b->own_stream = nullptr;
-	b->pool_frames = pool_frames; b->mb_pictures = mb_pictures; b->live = nullptr;
+	{   /* everything the decode reads from the environment (engine_internal.h) */
+		const auto env = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
+		b->recon = JmReconPolicy{ false, env("JSMPEG_HIP_RECON_ORDER", -1), getenv("JSMPEG_HIP_RECON_DENSE") ? env("JSMPEG_HIP_RECON_DENSE", 0) != 0 : -1,
+		                          getenv("JSMPEG_HIP_RECON_CHAINS") != nullptr,
+		                          env("JSMPEG_HIP_RECON_BREAK", -1), (uint32_t)env("JSMPEG_HIP_RECON_PATIENCE", 0), false };
+		b->debug_flags = env("JSMPEG_HIP_DEBUG", 0);
+		b->trace = getenv("JSMPEG_HIP_TRACE") != nullptr;
+	}
+	b->pool_frames = pool_frames; b->mb_pictures = mb_pictures;
 	b->pics_first_copy = mb_pictures ? std::min(std::max(1u, config->max_pictures), 4 * mb_pictures + 64) : std::max(1u, config->max_pictures);
 	if (config->device >= 0) {
 		if (hipSetDevice(config->device) != hipSuccess) { fail("hipSetDevice(%d) failed", config->device); delete b; return nullptr; }
@@ -208,17 +201,17 @@ extern "C" void *jsmpeg_hip_batch_own_stream(jsmpeg_hip_batch_t *b) {
 	return (void *)b->own_stream;
 }
 
-/* How the batch's passes reconstruct: 0 = always level by level, 1 = the engine's choice (one dependency-ordered launch where
- * the batch's shape suits it; what a batch is created with, unless JSMPEG_HIP_RECON_ORDER says otherwise).  For a host that
- * keeps TWO batches in flight: on wide batches the two plans take the same time one batch at a time (profiles/
- * r06n_levels_vs_ordered.txt: 64 / 32 streams x 120 pictures of 1080p, 64 x 48: within 0.1 %), and twelve short launches share
- * the GPU better with the other batch's parse than one launch whose classes wait on each other (cfg2 two in flight: 582.6 k
- * frames/s against 554.1 k; coded video 667 k against 536 k). */
+/* How the batch's passes reconstruct: 0 = always level by level, 1 = as the batch was created (the engine's choice, or what
+ * JSMPEG_HIP_RECON_ORDER said then); a batch whose ordered launch flagged itself stays level by level.  For a host that keeps
+ * TWO batches in flight: on wide batches the two plans take the same time one batch at a time (profiles/r06n_levels_vs_ordered.txt:
+ * 64 / 32 streams x 120 pictures of 1080p, 64 x 48: within 0.1 %), and twelve short launches share the GPU better with the other
+ * batch's parse than one launch whose classes wait on each other (cfg2 two in flight: 582.6 k frames/s against 554.1 k; coded
+ * video 667 k against 536 k). */
 extern "C" int jsmpeg_hip_batch_set_reconstruct(jsmpeg_hip_batch_t *b, int plan) {
 	g_err[0] = 0;
 	if (!b) return fail("null batch");
 	if (plan != 0 && plan != 1) return fail("set_reconstruct: 0 = level by level, 1 = the engine's choice");
-	b->order_group = plan == 0 ? 0u : JM_ORDER_AUTO;
+	b->recon.levels = plan == 0;
 	return 0;
 }
 
@@ -506,7 +499,7 @@ static void fill_desc(const jsmpeg_hip_batch_t *b, JmReconDesc &D, uint32_t p, i
 #include <chrono>
 struct HostTrace {
 	bool on; std::chrono::steady_clock::time_point t0; char line[1024]; size_t n;
-	HostTrace() : on(getenv("JSMPEG_HIP_TRACE") != nullptr), t0(std::chrono::steady_clock::now()), n(0) { line[0] = 0; }
+	explicit HostTrace(bool on_) : on(on_), t0(std::chrono::steady_clock::now()), n(0) { line[0] = 0; }
 	void mark(const char *what) {
 		if (!on) return;
 		const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -516,35 +509,30 @@ struct HostTrace {
 	~HostTrace() { if (on) fprintf(stderr, "decode host trace (ms):%s\n", line); }
 };
 
+/* no picture of the launch has a forward frame: the tile's form without prediction (1: k_recon_intra) -- or, for DENSE
+ * pictures, the one with a transform slot per lane (2: recon_plan.h JM_DENSE_INTRA_X16).  `bytes_per_mb_x16`: of the launch's
+ * pictures, in sixteenths. */
+static uint32_t none_predicts(const JmReconDesc *d, size_t n, uint32_t bytes_per_mb_x16, int dense) {
+	for (size_t i = 0; i < n; i++) if (d[i].fwd != nullptr) return 0;
+	if (dense >= 0) return dense ? 2u : 1u;
+	return bytes_per_mb_x16 >= JM_DENSE_INTRA_X16 ? 2u : 1u;
+}
+
+/* the arguments every reconstruct launch of the batch's current pass shares (an ordered launch adds its own) */
+static JmReconBufs recon_bufs(const jsmpeg_hip_batch_t *b) {
+	JmReconBufs rb;
+	rb.g = b->g; rb.luts = b->d_luts;
+	rb.epoch = b->epoch; rb.zero_uncovered = 1;
+	rb.need = 0; rb.patience = 0; rb.status = nullptr; rb.done = nullptr; rb.no_forward = 0;
+	return rb;
+}
+
 /* Reconstruct level by level: the pictures that wait for nothing right behind the parse (step 4a), then -- once the
  * parse has reported which pictures wrote every macroblock -- one launch per dependency level (step 4b).  The form
  * for batches that do not fill eight classes (recon_plan.h), the one-off fallback of an ordered launch that flagged
  * itself, and JSMPEG_HIP_RECON_ORDER=0. */
-/* no picture of the launch has a forward frame: the tile's form without prediction (k_recon_intra) -- and, when those pictures are
- * DENSE (bytes of compressed data per macroblock: practically every block then has AC coefficients and a tile needs a transform
- * slot per lane), the variant with 256 slots (2; measured: cfg0, 21 bytes per macroblock, -6 %; cfg2's intra pictures, 12.7, +11 %:
- * profiles/r04_recon_notes.md 8).  `bytes_per_mb_x16`: of the launch's pictures, in sixteenths. */
-#define JM_DENSE_INTRA_X16 310      /* 19.4 bytes per macroblock: all-intra 1080p at 18.0 is 5 % faster with 220 slots, at 20.7 5 % faster with 256 */
-static uint32_t none_predicts(const JmReconDesc *d, size_t n, uint32_t bytes_per_mb_x16, int dense_mode) {
-	for (size_t i = 0; i < n; i++) if (d[i].fwd != nullptr) return 0;
-	if (dense_mode >= 0) return dense_mode ? 2u : 1u;
-	return bytes_per_mb_x16 >= JM_DENSE_INTRA_X16 ? 2u : 1u;
-}
-
-/* compressed bytes per macroblock (x 16) of the batch's decoded pictures without a forward reference */
-static uint32_t batch_root_density(const jsmpeg_hip_batch_t *b) {
-	uint64_t bytes = 0, n = 0;
-	for (uint32_t p = 0; p < b->n_pics; p++) {
-		const JmPic &pic = b->h_pics[p];
-		if (!pic.decoded || pic.fwd >= 0 || pic.stream >= b->n_streams) continue;
-		const uint32_t end = p + 1 < b->n_pics && b->h_pics[p + 1].stream == pic.stream ? b->h_pics[p + 1].pos : b->h_streams[pic.stream].es_end;
-		bytes += end > pic.pos ? end - pic.pos : 0;
-		n++;
-	}
-	return n ? (uint32_t)std::min<uint64_t>(bytes * 16 / (n * (uint64_t)std::max(1, b->g.mb_size)), 0xffffffffu) : 0u;
-}
-
-static int recon_by_levels(jsmpeg_hip_batch_t *b, JmReconBufs &rb, const std::vector<int32_t> &stale, uint32_t n_roots, hipStream_t st, HostTrace &tr) {
+static int recon_by_levels(jsmpeg_hip_batch_t *b, const std::vector<int32_t> &stale, uint32_t n_roots, hipStream_t st, HostTrace &tr) {
+	JmReconBufs rb = recon_bufs(b);
 	{
 		if ((size_t)b->n_decoded + n_roots > b->desc_cap) return fail("internal: descriptor table too small");
 		uint32_t k = 0;
@@ -553,7 +541,7 @@ static int recon_by_levels(jsmpeg_hip_batch_t *b, JmReconBufs &rb, const std::ve
 	}
 	/* ---- 4a. reconstruct the pictures that wait for nothing ---- */
 	rb.desc = b->d_desc; rb.n_level_pics = n_roots;
-	rb.no_forward = none_predicts(b->h_desc, n_roots, batch_root_density(b), b->dense_mode);      /* (a seeded stream's first P picture is a root WITH a forward frame) */
+	rb.no_forward = none_predicts(b->h_desc, n_roots, b->roots_x16, b->recon.dense);      /* (a seeded stream's first P picture is a root WITH a forward frame) */
 	HIP_TRY(hipEventRecord(b->ev_level[b->n_level_ev++], st));
 	HIP_TRY(jm_launch_recon(rb, st));
 	rb.no_forward = 0;
@@ -573,45 +561,31 @@ static int recon_by_levels(jsmpeg_hip_batch_t *b, JmReconBufs &rb, const std::ve
 	}
 	HIP_TRY(hipEventSynchronize(b->ev_cov));
 	tr.mark("parse-done");
-	{
-		std::vector<int32_t> level;
-		const uint32_t n_levels = jm_plan_levels(b->h_pics, b->n_pics, stale, b->h_covered, (uint32_t)b->g.mb_size, level, &b->n_uncovered);
-		b->n_levels = n_levels; b->stats_pending = false;
-		std::vector<uint32_t> off(n_levels + 1, 0);
-		for (uint32_t p = 0; p < b->n_pics; p++) if (b->h_pics[p].decoded && level[p] > 0) off[level[p] + 1]++;
-		for (uint32_t l = 0; l < n_levels; l++) off[l + 1] += off[l];
-		const uint32_t n_later = off[n_levels];
-		if ((size_t)n_roots + n_later > b->desc_cap) return fail("internal: descriptor table too small");
-		if (getenv("JSMPEG_HIP_DEBUG_COVER"))
-			fprintf(stderr, "cover: %u of %u pictures with unwritten macroblocks, %u levels, %u pictures behind the first\n", b->n_uncovered, b->n_pics, n_levels, n_later);
-		if (n_later) {
-			std::vector<uint32_t> cur(off.begin(), off.end());
-			for (uint32_t p = 0; p < b->n_pics; p++) if (b->h_pics[p].decoded && level[p] > 0) fill_desc(b, b->h_desc[n_roots + cur[level[p]]++], p, stale[p]);
-			HIP_TRY(hipMemcpyAsync(b->d_desc + n_roots, b->h_desc + n_roots, sizeof(JmReconDesc) * n_later, hipMemcpyHostToDevice, st));
-			for (uint32_t l = 1; l < n_levels; l++) {
-				rb.desc = b->d_desc + n_roots + off[l];
-				rb.n_level_pics = off[l + 1] - off[l];
-				rb.no_forward = none_predicts(b->h_desc + n_roots + off[l], rb.n_level_pics, 0, b->dense_mode);
-				if (b->n_level_ev < 64) HIP_TRY(hipEventRecord(b->ev_level[b->n_level_ev++], st));
-				HIP_TRY(jm_launch_recon(rb, st));
-			}
+	std::vector<int32_t> level;
+	const uint32_t n_levels = jm_plan_levels(b->h_pics, b->n_pics, stale, b->h_covered, (uint32_t)b->g.mb_size, level, &b->n_uncovered);
+	b->n_levels = n_levels; b->stats_pending = false;
+	std::vector<uint32_t> off(n_levels + 1, 0);
+	for (uint32_t p = 0; p < b->n_pics; p++) if (b->h_pics[p].decoded && level[p] > 0) off[level[p] + 1]++;
+	for (uint32_t l = 0; l < n_levels; l++) off[l + 1] += off[l];
+	const uint32_t n_later = off[n_levels];
+	if ((size_t)n_roots + n_later > b->desc_cap) return fail("internal: descriptor table too small");
+	if (n_later) {
+		std::vector<uint32_t> cur(off.begin(), off.end());
+		for (uint32_t p = 0; p < b->n_pics; p++) if (b->h_pics[p].decoded && level[p] > 0) fill_desc(b, b->h_desc[n_roots + cur[level[p]]++], p, stale[p]);
+		HIP_TRY(hipMemcpyAsync(b->d_desc + n_roots, b->h_desc + n_roots, sizeof(JmReconDesc) * n_later, hipMemcpyHostToDevice, st));
+		for (uint32_t l = 1; l < n_levels; l++) {
+			rb.desc = b->d_desc + n_roots + off[l];
+			rb.n_level_pics = off[l + 1] - off[l];
+			rb.no_forward = none_predicts(b->h_desc + n_roots + off[l], rb.n_level_pics, 0, b->recon.dense);
+			if (b->n_level_ev < 64) HIP_TRY(hipEventRecord(b->ev_level[b->n_level_ev++], st));
+			HIP_TRY(jm_launch_recon(rb, st));
 		}
 	}
 	return 0;
 }
 
-extern "C" int jsmpeg_hip_batch_decode(jsmpeg_hip_batch_t *b, void *hip_stream) {
-	g_err[0] = 0;
-	if (!b) return fail("null batch");
-	HostTrace tr;
-	HIP_TRY(hipSetDevice(b->device));
-	hipStream_t st = (hipStream_t)hip_stream;
-	b->stream = st;
-	b->timed = false;
-	b->n_sc = b->n_pics = b->n_levels = b->n_decoded = b->n_slices = b->n_slice_codes = 0;
-	if (b->n_streams == 0) return 0;
-
-	/* ---- 1. start-code index + tables (device) ---- */
+/* ---- 1. start-code index + tables (device); 2. the one host turn-around: sizes + level order ---- */
+static int enqueue_index(jsmpeg_hip_batch_t *b, hipStream_t st) {
 	HIP_TRY(hipEventRecord(b->ev[0], st));
 	HIP_TRY(hipMemsetAsync(b->d_counters, 0, JM_N_COUNTERS * sizeof(uint32_t), st));
 	JmScanBufs sb;
@@ -626,31 +600,27 @@ extern "C" int jsmpeg_hip_batch_decode(jsmpeg_hip_batch_t *b, void *hip_stream) 
 	ib.width = b->cfg.width; ib.height = b->cfg.height;
 	HIP_TRY(jm_launch_index(ib, st));
 	HIP_TRY(hipEventRecord(b->ev[1], st));
-
-	/* ---- 2. the one host turn-around: sizes + level order ---- */
 	/* written by a kernel into the pinned tables, not copied by a DMA engine: a DMA job waits for the engines' other jobs -- a
 	 * host that uploads the NEXT pass's streams meanwhile (0.5 GB over PCIe on its own stream) held this turn-around for
-	 * 0.76 ms of every step (bench.py's value_incl_h2d).  JSMPEG_HIP_TURNAROUND_MEMCPY=1: the copies, for measurements */
-	static const bool turnaround_memcpy = getenv("JSMPEG_HIP_TURNAROUND_MEMCPY") != nullptr;
-	if (turnaround_memcpy) {
-		HIP_TRY(hipMemcpyAsync(b->h_counters, b->d_counters, JM_N_COUNTERS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(b->h_pics, b->d_pics, sizeof(JmPic) * b->pics_first_copy, hipMemcpyDeviceToHost, st));
-	} else {
-		HIP_TRY(jm_launch_to_host(b->h_counters_dev, b->d_counters, JM_N_COUNTERS * sizeof(uint32_t), b->h_pics_dev, b->d_pics, sizeof(JmPic) * b->pics_first_copy, st));
-	}
+	 * 0.76 ms of every step (bench.py's value_incl_h2d) */
+	HIP_TRY(jm_launch_to_host(b->h_counters_dev, b->d_counters, JM_N_COUNTERS * sizeof(uint32_t), b->h_pics_dev, b->d_pics, sizeof(JmPic) * b->pics_first_copy, st));
 	HIP_TRY(hipEventRecord(b->ev_idx, st));
 	/* the slice order (longest first: kernels.hip) goes in behind the copies and runs WHILE the host reads them and lays out
 	 * the parse: its kernels take their sizes from the device's counters, so nothing of it waits for the host -- 0.08 ms of
 	 * cfg2's step that used to stand between the host's turn-around and the parse */
-	const bool stream_order = getenv("JSMPEG_HIP_STREAM_ORDER") != nullptr;   /* (the variable: slices in stream order, for measurements) */
-	if (!stream_order) {
-		JmOrderBufs ob;
-		ob.slice_sc = b->d_slice_sc; ob.sc_pos = b->d_sc_pos; ob.sc_owner = b->d_sc_owner;
-		ob.counters = b->d_counters; ob.sc_cap = b->sc_cap; ob.es_bytes = b->es_bytes;
-		ob.hist = b->d_order_hist; ob.order = b->d_slice_order;
-		HIP_TRY(jm_launch_order(ob, st));
-	}
-	tr.mark("index-enqueued");
+	JmOrderBufs ob;
+	ob.slice_sc = b->d_slice_sc; ob.sc_pos = b->d_sc_pos; ob.sc_owner = b->d_sc_owner;
+	ob.counters = b->d_counters; ob.sc_cap = b->sc_cap; ob.es_bytes = b->es_bytes;
+	ob.hist = b->d_order_hist; ob.order = b->d_slice_order;
+	HIP_TRY(jm_launch_order(ob, st));
+	return 0;
+}
+
+struct ParseSizing { uint64_t long_slices, crit_bytes, crit_pics; };    /* what the parse's launch wants to know of the pictures */
+
+/* The decode's one host wait: the index's counters and picture table, and ONE walk over the table for everything the parse's
+ * launch and the reconstruct's plan want to know (it was three; the passes did not notice). */
+static int collect_index(jsmpeg_hip_batch_t *b, hipStream_t st, ParseSizing &ps, HostTrace &tr) {
 	HIP_TRY(hipEventSynchronize(b->ev_idx));
 	tr.mark("index-done");
 	if (b->h_counters[2]) return fail("start-code / picture table overflow: %u start codes, %u pictures (max_pictures %u)",
@@ -664,41 +634,47 @@ extern "C" int jsmpeg_hip_batch_decode(jsmpeg_hip_batch_t *b, void *hip_stream) 
 		HIP_TRY(hipStreamSynchronize(st));
 	}
 	tr.mark("pics-copied");
-	/* ONE walk over the picture table for everything the parse's launch wants to know (it was three; the passes did not notice):
-	 * decoded pictures, their slices, and how many slices are much longer than the mean (the
-	 * intra pictures' in an I + P batch: a picture's bytes / its slices against the batch's -- the slices come longest first,
-	 * jm_launch_parse gives that many fewer lanes per wavefront when the pass is of a size where it pays) */
-	uint64_t long_slices = 0, crit_bytes = 0, crit_pics = 0;
-	{
-		const uint64_t lanes = std::min(b->h_counters[4], b->sc_cap);
-		for (uint32_t p = 0; p < b->n_pics; p++) {
-			const JmPic &pic = b->h_pics[p];
-			if (!pic.decoded) continue;
-			b->n_decoded++; b->n_slices += pic.n_slices;
-			if (!pic.n_slices || pic.stream >= b->n_streams) continue;
-			const uint32_t end = p + 1 < b->n_pics && b->h_pics[p + 1].stream == pic.stream ? b->h_pics[p + 1].pos : b->h_streams[pic.stream].es_end;
-			const uint64_t bytes = end > pic.pos ? end - pic.pos : 0;
-			if (bytes * 2 * lanes >= (uint64_t)3 * b->es_bytes * pic.n_slices) long_slices += pic.n_slices;   /* >= 1.5 x the mean slice */
-			if (bytes * lanes >= (uint64_t)4 * b->es_bytes * pic.n_slices) { crit_bytes += bytes; crit_pics++; }   /* >= 4 x: coded video's intra pictures */
-		}
+	/* decoded pictures, their slices, how many slices are much longer than the mean (the intra pictures' in an I + P batch: a
+	 * picture's bytes / its slices against the batch's -- the slices come longest first, jm_launch_parse gives that many fewer
+	 * lanes per wavefront when the pass is of a size where it pays), and the compressed bytes per macroblock of the pictures
+	 * without a forward reference (the reconstruct's dense intra rule) */
+	ps = ParseSizing{ 0, 0, 0 };
+	uint64_t root_bytes = 0, roots = 0;
+	const uint64_t lanes = std::min(b->h_counters[4], b->sc_cap);
+	for (uint32_t p = 0; p < b->n_pics; p++) {
+		const JmPic &pic = b->h_pics[p];
+		if (!pic.decoded) continue;
+		b->n_decoded++; b->n_slices += pic.n_slices;
+		if (pic.stream >= b->n_streams) continue;
+		const uint32_t end = p + 1 < b->n_pics && b->h_pics[p + 1].stream == pic.stream ? b->h_pics[p + 1].pos : b->h_streams[pic.stream].es_end;
+		const uint64_t bytes = end > pic.pos ? end - pic.pos : 0;
+		if (pic.fwd < 0) { root_bytes += bytes; roots++; }
+		if (!pic.n_slices) continue;
+		if (bytes * 2 * lanes >= (uint64_t)3 * b->es_bytes * pic.n_slices) ps.long_slices += pic.n_slices;   /* >= 1.5 x the mean slice */
+		if (bytes * lanes >= (uint64_t)4 * b->es_bytes * pic.n_slices) { ps.crit_bytes += bytes; ps.crit_pics++; }   /* >= 4 x: coded video's intra pictures */
 	}
+	b->roots_x16 = roots ? (uint32_t)std::min<uint64_t>(root_bytes * 16 / (roots * (uint64_t)std::max(1, b->g.mb_size)), 0xffffffffu) : 0u;
 	if (b->live && live_assign_slots(b->live) < 0) return -1;      /* live streams: which pool slot each picture of this pass is written to */
+	return 0;
+}
+
+/* ---- 3. slice parse: every slice of the batch at once ---- */
+static int enqueue_parse(jsmpeg_hip_batch_t *b, hipStream_t st, const ParseSizing &ps, HostTrace &tr) {
 	if (b->n_pics) HIP_TRY(hipMemsetAsync(b->d_covered, 0, sizeof(uint32_t) * b->n_pics, st));
 	if (++b->epoch == 0) {
 		HIP_TRY(hipMemsetAsync(b->d_mb, 0, sizeof(JmMbRec) * (size_t)b->mb_pictures * b->g.mb_size, st));
 		b->epoch = 1;
 	}
 	HIP_TRY(hipEventRecord(b->ev[2], st));
-
-	/* ---- 3. slice parse: every slice of the batch at once ---- */
 	JmParseBufs pb;
 	pb.es = b->es_view; pb.sc_pos = b->d_sc_pos; pb.sc_code = b->d_sc_code; pb.sc_owner = b->d_sc_owner;
 	pb.pics = b->d_pics; pb.streams = b->d_streams; pb.luts = b->d_luts; pb.mb = b->d_mb; pb.tokens = b->d_tokens;
 	pb.n_sc = b->n_sc; pb.mb_size = b->g.mb_size; pb.epoch = b->epoch; pb.covered = b->d_covered;
 	pb.ticket = b->d_order_hist + 2 * JM_ORDER_BINS;
 	pb.cu_order = b->d_order_hist + 2 * JM_ORDER_BINS + 16;
-	pb.slice_sc = b->d_slice_sc; pb.n_lanes = std::min(b->h_counters[4], b->sc_cap);   /* a lane per slice code (not per start code) */
-	pb.long_slices = 0;
+	pb.slice_sc = b->d_slice_order;             /* (ordered by step 2, beside the host's turn-around) */
+	pb.n_lanes = std::min(b->h_counters[4], b->sc_cap);   /* a lane per slice code (not per start code) */
+	pb.long_slices = pb.n_lanes ? (uint32_t)std::min<uint64_t>(ps.long_slices + ps.long_slices / 8, pb.n_lanes) : 0;   /* + 1/8: the estimate is by picture, the order by slice */
 	pb.bytes_per_mb_x16 = 0; pb.t_cold = 0;
 	{   /* compressed bytes per macroblock of the decoded pictures: what the parse's header-step threshold follows */
 		const uint64_t n_dec = b->n_decoded;
@@ -708,13 +684,9 @@ extern "C" int jsmpeg_hip_batch_decode(jsmpeg_hip_batch_t *b, void *hip_stream) 
 		 * service form is theirs -- encoder-made 1080p at 16 Mbit/s (8 bytes per macroblock over all, 57 in the intra pictures):
 		 * parse 7.04 -> 6.60 ms with the dense settings (profiles/r06l_tcold_enc.txt); the generator's configurations have no such
 		 * pictures (intra ~2 x predicted) and keep theirs */
-		if (crit_pics) pb.bytes_per_mb_x16 = std::max(pb.bytes_per_mb_x16, (uint32_t)std::min<uint64_t>(1u << 20, crit_bytes * 16 / (crit_pics * (uint64_t)std::max(1, b->g.mb_size))));
+		if (ps.crit_pics) pb.bytes_per_mb_x16 = std::max(pb.bytes_per_mb_x16, (uint32_t)std::min<uint64_t>(1u << 20, ps.crit_bytes * 16 / (ps.crit_pics * (uint64_t)std::max(1, b->g.mb_size))));
 	}
-	if (!stream_order) {
-		pb.slice_sc = b->d_slice_order;             /* (ordered above, beside the host's turn-around) */
-		if (pb.n_lanes) pb.long_slices = (uint32_t)std::min<uint64_t>(long_slices + long_slices / 8, pb.n_lanes);   /* + 1/8: the estimate is by picture, the order by slice */
-	}
-	{ const char *dbg = getenv("JSMPEG_HIP_DEBUG"); pb.debug_flags = dbg ? atoi(dbg) : 0; }
+	pb.debug_flags = b->debug_flags;
 	pb.dbg = nullptr;
 	if (pb.debug_flags & 4) {   /* diagnostics: per-slice abort record, parked in the (unused) hash buffer's neighbour */
 		/* 4 words per start code (abort records) -- or, in a -DJM_PARSE_STATS build, 16 words per BATCH of slices: a head
@@ -730,120 +702,76 @@ extern "C" int jsmpeg_hip_batch_decode(jsmpeg_hip_batch_t *b, void *hip_stream) 
 	HIP_TRY(hipEventRecord(b->ev[3], st));
 	if (b->n_pics) HIP_TRY(hipMemcpyAsync(b->h_covered, b->d_covered, sizeof(uint32_t) * b->n_pics, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipEventRecord(b->ev_cov, st));
+	return 0;
+}
 
-	/* The reconstruct plan.  A picture comes after its forward reference -- and, if it leaves macroblocks UNWRITTEN,
-	 * after the frame those keep showing: the reference keeps two plane sets and rotates them after every picture
-	 * (mpeg1.c:986-994), so a macroblock a picture never writes -- e.g. a last macroblock of 6 bits (forward vector
-	 * repeated, nothing coded: common in a pan) that hides in the slack of the slice's last byte, so that
-	 * next_bytes_are_start_code ends the slice before it (mpeg1.c:1018-1020) -- keeps the decoded picture before
-	 * last.  Here every picture has its own frame, so such a block is copied from that picture's frame (`stale`).
-	 * Whether a picture has unwritten macroblocks is only known after the parse: the pictures without a forward
-	 * reference are reconstructed right behind it (step 4a: intra pictures hardly ever have such macroblocks), the
-	 * levels of all the others are laid out once the parse has reported (step 4b), while 4a runs.
-	 * (Laid out here, while the GPU is busy with the parse: the descriptors are only read by the reconstruct.) */
+/* ---- 4. ONE launch: every class walks its streams (or GOP chains) in lockstep; a picture's tiles wait for its forward
+ * reference, and a tile with a macroblock the picture never wrote for the frame that keeps showing there -- decided by the
+ * tile itself, so nothing here needs the parse's counts: no host turn-around between parse and reconstruct ---- */
+static int enqueue_ordered(jsmpeg_hip_batch_t *b, const JmOrderedPlan &plan, const std::vector<uint32_t> &chain_of,
+                           const std::vector<int32_t> &stale, hipStream_t st) {
+	for (size_t i = 0; i < plan.seq.size(); i++) {
+		JmReconDesc &D = b->h_desc[i];
+		const int32_t p = plan.seq[i];
+		if (p < 0) { memset(&D, 0, sizeof(D)); continue; }
+		fill_desc(b, D, (uint32_t)p, stale[p]);
+		D.done_pic = (uint32_t)p;
+		D.wait_fwd = b->h_pics[p].fwd >= 0 ? (uint32_t)b->h_pics[p].fwd : JM_NONE;
+		D.wait_stale = stale[p] >= 0 ? (uint32_t)stale[p] : JM_NONE;
+		if (!chain_of.empty() && stale[p] >= 0 && chain_of[stale[p]] != chain_of[p]) { D.wait_stale = JM_NONE; b->chain_heads.push_back((uint32_t)p); }
+	}
+	if (b->recon.brk >= 0 && (size_t)b->recon.brk < plan.seq.size() && plan.seq[b->recon.brk] >= 0) b->h_desc[b->recon.brk].done_pic = JM_NONE;
+	HIP_TRY(hipMemcpyAsync(b->d_desc, b->h_desc, sizeof(JmReconDesc) * plan.seq.size(), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemsetAsync(b->d_done, 0, (size_t)JM_DONE_STRIDE * sizeof(uint32_t) * b->n_pics, st));
+	HIP_TRY(hipMemsetAsync(b->d_rstatus, 0, sizeof(uint32_t) * 8, st));
+	HIP_TRY(hipMemsetAsync(b->d_rstatus + 8, 0xff, sizeof(uint32_t) * 8, st));
+	JmReconBufs rb = recon_bufs(b);
+	rb.desc = b->d_desc; rb.n_level_pics = (uint32_t)plan.seq.size();
+	rb.need = 1; rb.status = b->d_rstatus; rb.done = b->d_done; rb.patience = b->recon.patience;     /* (jm_launch_recon puts the workgroups per picture into `need`) */
+	HIP_TRY(hipEventRecord(b->ev_level[b->n_level_ev++], st));
+	HIP_TRY(jm_launch_recon(rb, st));
+	HIP_TRY(hipMemcpyAsync(b->h_rstatus, b->d_rstatus, sizeof(uint32_t) * JM_RECON_STATUS_WORDS, hipMemcpyDeviceToHost, st));
+	b->ordered = true; b->stats_pending = true; b->last_group = plan.lockstep;
+	return 0;
+}
+
+extern "C" int jsmpeg_hip_batch_decode(jsmpeg_hip_batch_t *b, void *hip_stream) {
+	g_err[0] = 0;
+	if (!b) return fail("null batch");
+	HostTrace tr(b->trace);
+	HIP_TRY(hipSetDevice(b->device));
+	hipStream_t st = (hipStream_t)hip_stream;
+	b->stream = st;
+	b->timed = false;
+	b->n_sc = b->n_pics = b->n_levels = b->n_decoded = b->n_slices = b->n_slice_codes = 0;
+	if (b->n_streams == 0) return 0;
+	if (enqueue_index(b, st) < 0) return -1;
+	tr.mark("index-enqueued");
+	ParseSizing ps;
+	if (collect_index(b, st, ps, tr) < 0 || enqueue_parse(b, st, ps, tr) < 0) return -1;
+
+	/* The reconstruct plan.  A picture comes after its forward reference -- and, if it leaves macroblocks UNWRITTEN, after
+	 * the frame those keep showing (`stale`, recon_plan.h).  Whether a picture has unwritten macroblocks is only known after
+	 * the parse: level by level, the pictures without a forward reference are reconstructed right behind it (step 4a: intra
+	 * pictures hardly ever have such macroblocks), the levels of all the others are laid out once the parse has reported
+	 * (step 4b), while 4a runs.  (Chosen and laid out here, while the GPU is busy with the parse: the descriptors are only
+	 * read by the reconstruct.) */
 	std::vector<int32_t> stale;
 	const uint32_t n_roots = batch_plan_stale(b, stale);
-	JmReconBufs rb;
-	rb.g = b->g; rb.luts = b->d_luts;
-	rb.epoch = b->epoch; rb.zero_uncovered = 1;
-	rb.need = 0; rb.patience = 0; rb.status = nullptr; rb.done = nullptr; rb.no_forward = 0;
 	b->n_level_ev = 0;
 	b->ordered = false; b->stats_pending = false; b->last_group = 0; b->ordered_status = 0; b->ordered_waits = 0;
-	JmOrderedPlan plan;
-	const uint32_t per_picture = jm_recon_tiles_per_picture(b->g);
-	const uint32_t group = b->order_group == JM_ORDER_AUTO ? 1 + (JM_ORDER_DISTANCE + per_picture - 1) / per_picture : b->order_group;
 	b->chain_heads.clear();
-	static const bool force_chains = getenv("JSMPEG_HIP_RECON_CHAINS") != nullptr;     /* tests: GOP chains whatever the batch's shape */
-	/* (a batch without a single predicted picture has nothing to order: one plain launch) */
-	const bool any_dependency = n_roots < b->n_decoded;
-	/* DENSE intra pictures (cfg4's: 27 bytes per macroblock) are worth a launch of their own -- k_recon_intra_dense, which only a
-	 * launch without predicted pictures can take: 2160p 64 x 24: reconstruct 10.73-10.81 ms level by level against 11.05-11.18 in
-	 * one ordered launch.  So, left to itself, a batch with such pictures and a shallow dependency structure goes level by level. */
-	bool dense_roots = false;
-	if (b->order_group == JM_ORDER_AUTO && b->dense_mode != 0 && any_dependency && !force_chains && batch_root_density(b) >= JM_DENSE_INTRA_X16) {
-		int32_t deepest = 0;
-		for (uint32_t p = 0; p < b->n_pics; p++) if (b->h_pics[p].decoded) deepest = std::max(deepest, b->h_pics[p].level);
-		dense_roots = deepest < 16;
-	}
-	/* WIDE batches go level by level too (late round 6, profiles/r06n_levels_vs_ordered.txt): from ~2.5 M macroblocks per level up
-	 * -- 32 streams x 120 pictures of 1080p, the headline's 64 x 120 -- a level's launch is long against the gap behind it and the
-	 * two plans take the same time (11.151 against 11.152 ms, 5.745 / 5.734); below that the one launch is 1-12 % faster and stays.
-	 * What the levels have for them where they cost nothing: they share the GPU better with another batch in flight (582.6 k
-	 * against 554.1 k frames/s), and they stand on kernel boundaries, not on the ordered launch's argument about one XCD's L2
-	 * (kernels.hip jm_recon_wait).  JSMPEG_HIP_RECON_WIDE_LEVELS=0: the ordered launch for these too (measurements). */
-	if (!dense_roots && b->order_group == JM_ORDER_AUTO && any_dependency && !force_chains) {
-		static const bool wide_rule = !(getenv("JSMPEG_HIP_RECON_WIDE_LEVELS") && atoi(getenv("JSMPEG_HIP_RECON_WIDE_LEVELS")) == 0);
-		int32_t deepest = 0;
-		for (uint32_t p = 0; p < b->n_pics; p++) if (b->h_pics[p].decoded) deepest = std::max(deepest, b->h_pics[p].level);
-		if (wide_rule && deepest < 16 && (uint64_t)b->n_decoded * (uint64_t)std::max(1, b->g.mb_size) >= (uint64_t)JM_WIDE_LEVEL_MBS * (uint64_t)(deepest + 1))
-			dense_roots = true;     /* (the same consequence: no ordered plan, no chains; recon_by_levels picks each level's kernel form by itself) */
-	}
-	bool planned = any_dependency && !dense_roots && !force_chains && group && jm_plan_ordered(b->h_pics, b->n_pics, b->n_streams, group, 8, plan, b->link_prev.size() == b->n_streams ? b->link_prev.data() : nullptr) &&
-	               (size_t)8 * plan.rows <= b->desc_cap && (b->order_group != JM_ORDER_AUTO || (plan.lockstep - 1) * per_picture >= JM_ORDER_MIN_DISTANCE);
-	std::vector<uint32_t> chain_of;
-	if (!planned && !dense_roots && any_dependency && group && (b->order_group == JM_ORDER_AUTO || force_chains) && b->link_prev.empty() && b->seeded.empty()) {
-		/* NARROW batches (fewer than eight streams, or streams of very different lengths: one file of many GOPs): the
-		 * classes walk GOP CHAINS instead of streams -- a chain = an intra picture and the P pictures behind it.  The one
-		 * thing that crosses chains is the `stale` frame of a chain's first two pictures (it belongs to the GOP before,
-		 * maybe another class's): the plan assumes those pictures write every macroblock -- intra pictures and a GOP's first
-		 * P picture practically always do -- and the assumption is CHECKED once the parse's counts are in
-		 * (batch_settle): a picture that did not is done over, with everything else, level by level. */
-		std::vector<JmPic> by_chain;
-		const uint32_t n_chains = jm_plan_chains(b->h_pics, b->n_pics, b->n_streams, chain_of, &by_chain);
-		planned = n_chains >= 8 && jm_plan_ordered(by_chain.data(), b->n_pics, n_chains, group, 8, plan) && (size_t)8 * plan.rows <= b->desc_cap &&
-		          (force_chains || (plan.lockstep - 1) * per_picture >= JM_ORDER_MIN_DISTANCE);
-		if (!planned) chain_of.clear();
-	}
-#ifdef JSMPEG_HIP_MEASUREMENT_HOOKS
-	/* measurement builds only: JSMPEG_HIP_T_SHADOW_PARSE=n -- the slice parse a SECOND time (same input, same output: the
-	 * reconstruct reads what it rewrites with the same values), with n resident workgroups on a side stream, enqueued right
-	 * before the reconstruct: what a step would cost whose parse runs beside the reconstruct of the step before
-	 * (step - parse_ms = the pipelined step; profiles/r04_recon_notes.md) */
-	static const int shadow = getenv("JSMPEG_HIP_T_SHADOW_PARSE") ? atoi(getenv("JSMPEG_HIP_T_SHADOW_PARSE")) : 0;
-	static hipStream_t side = nullptr; static hipEvent_t side_ev[2];
-	if (shadow > 0) {
-		if (!side) { HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking)); HIP_TRY(hipEventCreate(&side_ev[0])); HIP_TRY(hipEventCreate(&side_ev[1])); }
-		HIP_TRY(hipEventRecord(side_ev[0], st));
-		HIP_TRY(hipStreamWaitEvent(side, side_ev[0], 0));
-		jm_parse_resident_once = (uint32_t)shadow;
-		HIP_TRY(jm_launch_parse(pb, side));
-		HIP_TRY(hipEventRecord(side_ev[1], side));
-	}
-#endif
-	if (planned) {
-		/* ---- 4. ONE launch: every class walks its streams in lockstep; a picture's tiles wait for its forward reference,
-		 * and a tile with a macroblock the picture never wrote for the frame that keeps showing there -- decided by the
-		 * tile itself, so nothing here needs the parse's counts: no host turn-around between parse and reconstruct ---- */
-		for (size_t i = 0; i < plan.seq.size(); i++) {
-			JmReconDesc &D = b->h_desc[i];
-			const int32_t p = plan.seq[i];
-			if (p < 0) { memset(&D, 0, sizeof(D)); continue; }
-			fill_desc(b, D, (uint32_t)p, stale[p]);
-			D.done_pic = (uint32_t)p;
-			D.wait_fwd = b->h_pics[p].fwd >= 0 ? (uint32_t)b->h_pics[p].fwd : JM_NONE;
-			D.wait_stale = stale[p] >= 0 ? (uint32_t)stale[p] : JM_NONE;
-			if (!chain_of.empty() && stale[p] >= 0 && chain_of[stale[p]] != chain_of[p]) { D.wait_stale = JM_NONE; b->chain_heads.push_back((uint32_t)p); }
-		}
-		if (const char *e = getenv("JSMPEG_HIP_RECON_BREAK")) {   /* tests: picture n of the plan never reports, its successor's wait runs out */
-			const size_t i = (size_t)atoi(e);
-			if (i < plan.seq.size() && plan.seq[i] >= 0) b->h_desc[i].done_pic = JM_NONE;
-		}
-		if (const char *e = getenv("JSMPEG_HIP_RECON_PATIENCE")) rb.patience = (uint32_t)atoi(e);
-		HIP_TRY(hipMemcpyAsync(b->d_desc, b->h_desc, sizeof(JmReconDesc) * plan.seq.size(), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemsetAsync(b->d_done, 0, (size_t)JM_DONE_STRIDE * sizeof(uint32_t) * b->n_pics, st));
-		HIP_TRY(hipMemsetAsync(b->d_rstatus, 0, sizeof(uint32_t) * 8, st));
-		HIP_TRY(hipMemsetAsync(b->d_rstatus + 8, 0xff, sizeof(uint32_t) * 8, st));
-		rb.desc = b->d_desc; rb.n_level_pics = (uint32_t)plan.seq.size();
-		rb.need = 1; rb.status = b->d_rstatus; rb.done = b->d_done;     /* (jm_launch_recon puts the workgroups per picture into `need`) */
-		HIP_TRY(hipEventRecord(b->ev_level[b->n_level_ev++], st));
-		HIP_TRY(jm_launch_recon(rb, st));
-		HIP_TRY(hipMemcpyAsync(b->h_rstatus, b->d_rstatus, sizeof(uint32_t) * JM_RECON_STATUS_WORDS, hipMemcpyDeviceToHost, st));
-		b->ordered = true; b->stats_pending = true; b->last_group = plan.lockstep;
+	JmOrderedPlan plan; std::vector<uint32_t> chain_of;
+	const JmReconKind kind = jm_choose_recon(b->h_pics, b->n_pics, b->n_streams, b->n_decoded, n_roots, (uint32_t)b->g.mb_size,
+	                                         jm_recon_tiles_per_picture(b->g), b->desc_cap, b->roots_x16,
+	                                         b->link_prev.size() == b->n_streams ? b->link_prev.data() : nullptr,
+	                                         !b->link_prev.empty() || !b->seeded.empty(), b->recon, plan, chain_of);
+	if (kind == JM_RECON_LEVELS) {
+		if (recon_by_levels(b, stale, n_roots, st, tr) < 0) return -1;
+	} else {
+		if (enqueue_ordered(b, plan, chain_of, stale, st) < 0) return -1;
 		tr.mark("ordered-enqueued");
-	} else if (recon_by_levels(b, rb, stale, n_roots, st, tr) < 0) return -1;
-#ifdef JSMPEG_HIP_MEASUREMENT_HOOKS
-	if (shadow > 0) HIP_TRY(hipStreamWaitEvent(st, side_ev[1], 0));
-#endif
+	}
 	HIP_TRY(hipEventRecord(b->ev_level[b->n_level_ev], st));
 	HIP_TRY(hipEventRecord(b->ev[4], st));
 	tr.mark("levels-enqueued");
@@ -857,11 +785,9 @@ extern "C" int jsmpeg_hip_batch_decode(jsmpeg_hip_batch_t *b, void *hip_stream) 
 static int batch_redo_by_levels(jsmpeg_hip_batch_t *b) {
 	std::vector<int32_t> stale;
 	const uint32_t n_roots = batch_plan_stale(b, stale);
-	JmReconBufs rb;
-	rb.g = b->g; rb.luts = b->d_luts; rb.epoch = b->epoch; rb.zero_uncovered = 1; rb.need = 0; rb.patience = 0; rb.status = nullptr; rb.done = nullptr; rb.no_forward = 0;
-	HostTrace tr;
+	HostTrace tr(b->trace);
 	b->n_level_ev = 0; b->last_group = 0;
-	if (recon_by_levels(b, rb, stale, n_roots, b->stream, tr) < 0) return -1;
+	if (recon_by_levels(b, stale, n_roots, b->stream, tr) < 0) return -1;
 	HIP_TRY(hipEventRecord(b->ev_level[b->n_level_ev], b->stream));
 	HIP_TRY(hipStreamSynchronize(b->stream));
 	return 0;                     /* (recon_by_levels has said whether the statistics still wait for the parse's counts) */
@@ -875,7 +801,7 @@ static int batch_settle(jsmpeg_hip_batch_t *b) {
 		if (b->h_rstatus[0]) {
 			fprintf(stderr, "jsmpeg_hip: the ordered reconstruct flagged itself (status %u: %s); reconstructing level by level, and from now on\n",
 			        b->h_rstatus[0], (b->h_rstatus[0] & 2) ? "a class of workgroups ran on two XCDs" : "a picture's wait ran out of patience");
-			b->order_group = 0;
+			b->recon.demoted = true;
 			if (batch_redo_by_levels(b) < 0) return -1;
 		} else if (!b->chain_heads.empty()) {
 			/* ordered by GOP chains: did the pictures whose `stale` frame lies in another chain write every macroblock? */

@@ -49,23 +49,19 @@ static hipError_t jm_malloc(T **p, size_t bytes) {
 int luts_for_device(int dev, JmVlcLuts **out);      /* the VLC tables on a device, built and uploaded once (engine.hip) */
 static inline void geom_init(JmGeom &g, int width, int height) { jm_geom_init(g, width, height); }
 
-/* The ordered reconstruct (recon_plan.h): how far back, in workgroups of its class's dispatch order, the LAST tile of a
- * picture's forward reference should lie behind the picture's FIRST tile: (streams in lockstep - 1) x tiles per picture.
- * A class (32 CUs) holds 160 workgroups at a time; 200 back is finished but for stragglers (cfg2, 200 tiles per picture,
- * two streams in lockstep: 0-1000 unfinished first looks in 1.5 M; one stream in lockstep, distance 1: 1.16 M, three times
- * the time; 4K, 816 tiles, one stream: 0.87 M).  Below the residency the per-level launches are the better form (small
- * pictures with few streams per class).
- * Late in round 6 the distance aimed at went from 200 to 400: on CODED video (encoder-made 1080p, profiles/r06k_enc_content.md)
- * a predicted picture's tiles are mostly copies and run up against a forward reference only 204 tiles ahead -- two 1080p streams
- * in lockstep: 339 k waits, the launch 18.9 ms against 10.2 with three (0 waits; four, six, eight the same) -- and the generator's
- * cfg2 is the same with three within a box's noise (alternating on two boxes, three rounds each: 11.03-11.05 against 11.11-11.16 ms
- * on one, 11.17-11.22 against 11.14-11.15 on the other: profiles/r06n_order_ab.txt, r06o_order_ab.txt; 720p goes from four streams
- * in lockstep to six: 5.01 against 5.06).
- * JSMPEG_HIP_RECON_ORDER: 0 = always level by level, n = n streams in lockstep whatever the picture size (tests). */
-#define JM_ORDER_DISTANCE 400u
-#define JM_ORDER_MIN_DISTANCE 160u
-#define JM_ORDER_AUTO 0xffffffffu
-#define JM_WIDE_LEVEL_MBS 2500000u       /* macroblocks per dependency level from which a batch left to itself goes level by level (engine.hip) */
+/* What a batch's decode reads from the environment -- once, when the batch is created (batch_create); tests and tools set
+ * these before they create one:
+ *   JSMPEG_HIP_RECON_ORDER=0 / n     the reconstruct level by level / n streams in lockstep per class of the ordered launch
+ *                                    whatever the picture size (default: the engine's choice, recon_plan.h jm_choose_recon)
+ *   JSMPEG_HIP_RECON_DENSE=0 / 1     never / always the intra form with a transform slot per lane (default: by the intra
+ *                                    pictures' bytes per macroblock, JM_DENSE_INTRA_X16)
+ *   JSMPEG_HIP_RECON_CHAINS=1        tests: the ordered launch over GOP chains whatever the batch's shape
+ *   JSMPEG_HIP_RECON_BREAK=n         tests: picture n of the ordered plan never reports (its successor's wait runs out)
+ *   JSMPEG_HIP_RECON_PATIENCE=n      tests: polls before an ordered launch's wait gives up (0: the kernel's)
+ *   JSMPEG_HIP_DEBUG=flags           diagnostics of the slice parse (kernels.h JmParseBufs::debug_flags)
+ *   JSMPEG_HIP_TRACE=1               where the host's time goes in each decode call (stderr)
+ * Read elsewhere: JSMPEG_HIP_POISON (jm_malloc), the tuning knobs JSMPEG_HIP_PARSE_*, _T_COLD, _RECON_LDSPAD (kernels.hip),
+ * and in a -DJSMPEG_HIP_MEASUREMENT_HOOKS build JSMPEG_HIP_T_FIXEDFWD / _T_FIXEDDST (engine.hip fill_desc). */
 /* pictures the one-picture interface decodes per pass of the batch engine when that many are buffered (mpeg1_decoder_t::ahead) */
 #ifndef JM_DECODE_AHEAD
 #define JM_DECODE_AHEAD 48u        /* ... at most, and no more than fit 160 MB of frames (1080p: 48, 2160p: 12): dec_sequence_header */
@@ -113,8 +109,10 @@ struct jsmpeg_hip_batch_t {
 	std::vector<uint8_t> seeded;
 	std::vector<const uint8_t *> seed_frames;   /* [2 * stream + which] */
 	uint32_t last_group;         /* lockstep width of the last decode's launch, 0: it went level by level */
-	int dense_mode;              /* -1: dense intra pictures by their bytes per macroblock (JM_DENSE_INTRA_X16); 0 / 1: never / always (JSMPEG_HIP_RECON_DENSE) */
-	uint32_t order_group;        /* streams a class walks in lockstep; 0: always level by level; JM_ORDER_AUTO: by the picture size */
+	JmReconPolicy recon;         /* what decides the reconstruct's plan besides the pictures (recon_plan.h) */
+	int debug_flags;             /* JSMPEG_HIP_DEBUG */
+	bool trace;                  /* JSMPEG_HIP_TRACE */
+	uint32_t roots_x16;          /* compressed bytes per macroblock (x 16) of the last decode's pictures without a forward reference */
 	bool ordered;                /* the last decode used the ordered launch (its status is checked at the next sync) */
 	std::vector<uint32_t> chain_heads;   /* ordered by GOP chains (narrow batches): the pictures whose `stale` frame lies in ANOTHER chain -- they must
 	                                        turn out to have written every macroblock (checked at the next sync, else the frames are done over) */

@@ -713,9 +713,6 @@ __global__ __launch_bounds__(JM_PARSE_WG) void k_parse(JmParseBufs b) { jm_parse
 __global__ __launch_bounds__(JM_PARSE_WG) void k_parse_split(JmParseBufs b) { jm_parse_body<true>(b); }
 
 extern "C" int jsmpeg_hip_debug_parse_plan(uint32_t n_slices, uint32_t long_slices, uint32_t bytes_per_mb_x16, int with_tickets, uint32_t out[12]);
-#ifdef JSMPEG_HIP_MEASUREMENT_HOOKS
-uint32_t jm_parse_resident_once = 0;   /* measurement builds (engine.hip, JSMPEG_HIP_T_SHADOW_PARSE): the next launch's resident workgroups; not thread-safe, not in the product */
-#endif
 /* What a pass's launch is: everything jm_launch_parse decides, as host arithmetic without a HIP call (jm_launch_parse is this
  * + the fills + the launch; tests/test_parse_plan.py reads the rules through jsmpeg_hip_debug_parse_plan on a machine without
  * a GPU).  b.n_lanes != 0; `have_ticket`: the caller gave a ticket counter.  Returns the workgroups; *use_ticket: the
@@ -814,14 +811,8 @@ uint32_t jm_plan_parse(JmParseBufs &b, bool have_ticket, bool *use_ticket) {
 	uint32_t groups = (b.n_batches + JM_PARSE_WAVES - 1) / JM_PARSE_WAVES;
 	static const uint32_t resident = getenv("JSMPEG_HIP_PARSE_RESIDENT") ? (uint32_t)atoi(getenv("JSMPEG_HIP_PARSE_RESIDENT"))
 	                                                                      : JM_PARSE_RESIDENT_WGS;   /* tests: the ticket path on small inputs */
-#ifdef JSMPEG_HIP_MEASUREMENT_HOOKS
-	const uint32_t resident_now = jm_parse_resident_once ? jm_parse_resident_once : resident;
-	jm_parse_resident_once = 0;
-#else
-	const uint32_t resident_now = resident;
-#endif
-	*use_ticket = groups > resident_now && resident_now >= 1 && have_ticket;
-	if (*use_ticket) groups = resident_now;
+	*use_ticket = groups > resident && resident >= 1 && have_ticket;
+	if (*use_ticket) groups = resident;
 	else {
 		/* A pass without tickets of MORE than one workgroup per CU but fewer than two: the dispatcher gives every CU one
 		 * workgroup and some a second -- sixteen wavefronts there, eight elsewhere, and the pass lasts as long as the CUs with
@@ -834,9 +825,9 @@ uint32_t jm_plan_parse(JmParseBufs &b, bool have_ticket, bool *use_ticket) {
 		 * changes nothing (2160p 8 / 16 / 32 x 24, one 720p stream: +-0.5 %).  JSMPEG_HIP_PARSE_EVEN=0: the packed grid, =2:
 		 * everything spread (measurements, profiles/r05ae_parse_grids.txt) */
 		static const int even = getenv("JSMPEG_HIP_PARSE_EVEN") ? atoi(getenv("JSMPEG_HIP_PARSE_EVEN")) : 1;
-		if (even && groups > resident_now / 2 && groups < resident_now) groups = resident_now;
-		else if (even && b.n_batches <= resident_now / 2) groups = b.n_batches;
-		else if (even >= 2 && groups < resident_now / 2) groups = resident_now / 2;
+		if (even && groups > resident / 2 && groups < resident) groups = resident;
+		else if (even && b.n_batches <= resident / 2) groups = b.n_batches;
+		else if (even >= 2 && groups < resident / 2) groups = resident / 2;
 	}
 	return groups;
 }

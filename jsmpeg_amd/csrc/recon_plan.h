@@ -172,4 +172,87 @@ static inline uint32_t jm_plan_chains(const JmPic *pics, uint32_t n_pics, uint32
 	return n_chains;
 }
 
+/* WHICH PLAN a pass takes (jm_choose_recon below).  The ordered launch: how far back, in workgroups of its class's dispatch order, the LAST tile of a picture's forward
+ * reference should lie behind the picture's FIRST tile: (streams in lockstep - 1) x tiles per picture.
+ * A class (32 CUs) holds 160 workgroups at a time; 200 back is finished but for stragglers (cfg2, 200 tiles per picture,
+ * two streams in lockstep: 0-1000 unfinished first looks in 1.5 M; one stream in lockstep, distance 1: 1.16 M, three times
+ * the time; 4K, 816 tiles, one stream: 0.87 M).  Below the residency the per-level launches are the better form (small
+ * pictures with few streams per class).
+ * Late in round 6 the distance aimed at went from 200 to 400: on CODED video (encoder-made 1080p, profiles/r06k_enc_content.md)
+ * a predicted picture's tiles are mostly copies and run up against a forward reference only 204 tiles ahead -- two 1080p streams
+ * in lockstep: 339 k waits, the launch 18.9 ms against 10.2 with three (0 waits; four, six, eight the same) -- and the generator's
+ * cfg2 is the same with three within a box's noise (alternating on two boxes, three rounds each: 11.03-11.05 against 11.11-11.16 ms
+ * on one, 11.17-11.22 against 11.14-11.15 on the other: profiles/r06n_order_ab.txt, r06o_order_ab.txt; 720p goes from four streams
+ * in lockstep to six: 5.01 against 5.06). */
+#define JM_ORDER_DISTANCE 400u
+#define JM_ORDER_MIN_DISTANCE 160u
+/* WIDE batches go level by level (late round 6, profiles/r06n_levels_vs_ordered.txt): from ~2.5 M macroblocks per level up
+ * -- 32 streams x 120 pictures of 1080p, the headline's 64 x 120 -- a level's launch is long against the gap behind it and the
+ * two plans take the same time (11.151 against 11.152 ms, 5.745 / 5.734); below that the one launch is 1-12 % faster and stays.
+ * What the levels have for them where they cost nothing: they share the GPU better with another batch in flight (582.6 k
+ * against 554.1 k frames/s), and they stand on kernel boundaries, not on the ordered launch's argument about one XCD's L2
+ * (kernels.hip jm_recon_wait). */
+#define JM_WIDE_LEVEL_MBS 2500000u
+/* A launch without a forward frame in any picture takes the tile's form without prediction (k_recon_intra) -- and, when those
+ * pictures are DENSE (bytes of compressed data per macroblock: practically every block has AC coefficients, a tile needs a
+ * transform slot per lane), the variant with 256 slots (cfg0, 21 bytes per macroblock, -6 %; cfg2's intra pictures, 12.7, +11 %:
+ * profiles/r04_recon_notes.md 8).  Only a launch without predicted pictures can take it, so a batch left to itself with dense
+ * intra pictures (cfg4's: 27) and a shallow dependency structure goes level by level: 2160p 64 x 24: reconstruct 10.73-10.81 ms
+ * against 11.05-11.18 in one ordered launch.  In sixteenths: 19.4 bytes per macroblock (all-intra 1080p at 18.0 is 5 % faster
+ * with 220 slots, at 20.7 5 % faster with 256). */
+#define JM_DENSE_INTRA_X16 310
+
+/* What decides a batch's plan besides its pictures (engine_internal.h: set when the batch is created, the environment
+ * variables read then). */
+struct JmReconPolicy {
+	bool levels;        /* the host's setting (jsmpeg_hip_batch_set_reconstruct 0): always level by level */
+	int32_t order;      /* JSMPEG_HIP_RECON_ORDER: < 0 not set (the engine's choice), 0 level by level, n streams in lockstep */
+	int dense;          /* JSMPEG_HIP_RECON_DENSE: -1 by the intra pictures' bytes per macroblock, 0 / 1 never / always the dense form */
+	bool chains;        /* JSMPEG_HIP_RECON_CHAINS: GOP chains whatever the batch's shape */
+	int32_t brk;        /* JSMPEG_HIP_RECON_BREAK: picture n of the ordered plan never reports (< 0: none) */
+	uint32_t patience;  /* JSMPEG_HIP_RECON_PATIENCE: polls before an ordered wait gives up (0: the kernel's) */
+	bool demoted;       /* an ordered launch flagged itself: level by level from then on, whatever is set */
+};
+
+enum JmReconKind { JM_RECON_LEVELS, JM_RECON_BY_STREAMS, JM_RECON_BY_CHAINS };
+
+/* The plan of a pass whose picture table has arrived (before the parse has reported anything).  n_roots: decoded pictures
+ * without a forward reference (jm_plan_stale), roots_x16 their compressed bytes per macroblock in sixteenths; link_prev: as
+ * for jm_plan_stale; linked_or_seeded: a stream continues another or was seeded (the GOP chains' assumption fails then).
+ * Fills `plan` for the ordered kinds, `chain_of` (jm_plan_chains) for JM_RECON_BY_CHAINS. */
+static inline JmReconKind jm_choose_recon(const JmPic *pics, uint32_t n_pics, uint32_t n_streams, uint32_t n_decoded, uint32_t n_roots,
+                                          uint32_t mb_size, uint32_t tiles_per_picture, uint32_t desc_cap, uint32_t roots_x16,
+                                          const int32_t *link_prev, bool linked_or_seeded, const JmReconPolicy &pol,
+                                          JmOrderedPlan &plan, std::vector<uint32_t> &chain_of) {
+	chain_of.clear();
+	const bool own = !pol.levels && !pol.demoted && pol.order < 0;          /* the engine's own choice */
+	const uint32_t group = pol.levels || pol.demoted ? 0u
+	                     : own ? 1 + (JM_ORDER_DISTANCE + tiles_per_picture - 1) / tiles_per_picture : (uint32_t)pol.order;
+	/* (a batch without a single predicted picture has nothing to order: one plain launch) */
+	if (n_roots >= n_decoded || group == 0) return JM_RECON_LEVELS;
+	if (own && !pol.chains) {
+		int32_t deepest = 0;
+		for (uint32_t p = 0; p < n_pics; p++) if (pics[p].decoded) deepest = std::max(deepest, pics[p].level);
+		if (deepest < 16 && pol.dense != 0 && roots_x16 >= JM_DENSE_INTRA_X16) return JM_RECON_LEVELS;
+		if (deepest < 16 && (uint64_t)n_decoded * std::max(1u, mb_size) >= (uint64_t)JM_WIDE_LEVEL_MBS * (uint64_t)(deepest + 1)) return JM_RECON_LEVELS;
+	}
+	const auto fits = [&](bool far_enough_or_forced) {
+		return (size_t)8 * plan.rows <= desc_cap && (far_enough_or_forced || (plan.lockstep - 1) * tiles_per_picture >= JM_ORDER_MIN_DISTANCE);
+	};
+	if (!pol.chains && jm_plan_ordered(pics, n_pics, n_streams, group, 8, plan, link_prev) && fits(!own)) return JM_RECON_BY_STREAMS;
+	/* NARROW batches (fewer than eight streams, or streams of very different lengths: one file of many GOPs): the classes walk
+	 * GOP CHAINS instead of streams -- a chain = an intra picture and the P pictures behind it.  The one thing that crosses
+	 * chains is the `stale` frame of a chain's first two pictures (it belongs to the GOP before, maybe another class's): the
+	 * plan assumes those pictures write every macroblock -- intra pictures and a GOP's first P picture practically always
+	 * do -- and the engine CHECKS the assumption once the parse's counts are in: a picture that did not is done over, with
+	 * everything else, level by level. */
+	if ((own || pol.chains) && !linked_or_seeded) {
+		std::vector<JmPic> by_chain;
+		const uint32_t n_chains = jm_plan_chains(pics, n_pics, n_streams, chain_of, &by_chain);
+		if (n_chains >= 8 && jm_plan_ordered(by_chain.data(), n_pics, n_chains, group, 8, plan) && fits(pol.chains)) return JM_RECON_BY_CHAINS;
+		chain_of.clear();
+	}
+	return JM_RECON_LEVELS;
+}
+
 #endif

@@ -338,6 +338,35 @@ int sim_plan_chains(uint32_t n_pics, uint32_t n_streams, const uint8_t *decoded,
 	return (int)n;
 }
 
+// The plan choice (recon_plan.h, jm_choose_recon) on plain arrays, for pictures of width x height: n_roots, n_decoded,
+// macroblocks and tiles per picture worked out as the engine does.  link_prev: null or one entry per stream.  Returns the
+// kind (0 level by level, 1 ordered over streams, 2 ordered over GOP chains); *out_lockstep, *out_rows: the ordered plan's.
+int sim_choose_recon(uint32_t n_pics, uint32_t n_streams, const uint8_t *decoded, const int32_t *fwd, const uint32_t *stream, const int32_t *level,
+                     int width, int height, uint32_t desc_cap, uint32_t roots_x16, const int32_t *link_prev, int linked_or_seeded,
+                     int levels, int order, int dense, int chains, int demoted, uint32_t *out_lockstep, uint32_t *out_rows) {
+	std::vector<JmPic> pics(n_pics);
+	uint32_t n_decoded = 0;
+	for (uint32_t p = 0; p < n_pics; p++) {
+		pics[p] = JmPic(); pics[p].decoded = decoded[p]; pics[p].fwd = fwd[p]; pics[p].stream = stream[p]; pics[p].level = level[p];
+		n_decoded += decoded[p] != 0;
+	}
+	std::vector<int32_t> stale;
+	const uint32_t n_roots = jm_plan_stale(pics.data(), n_pics, n_streams, stale);
+	JmGeom g;
+	jm_geom_init(g, width, height);
+	JmTiles T;
+	jm_tiles_init(T, g);
+	JmReconPolicy pol;
+	pol.levels = levels; pol.order = order; pol.dense = dense; pol.chains = chains; pol.brk = -1; pol.patience = 0; pol.demoted = demoted;
+	JmOrderedPlan plan;
+	std::vector<uint32_t> chain_of;
+	const JmReconKind kind = jm_choose_recon(pics.data(), n_pics, n_streams, n_decoded, n_roots, (uint32_t)g.mb_size, (uint32_t)T.per_picture,
+	                                         desc_cap, roots_x16, link_prev, linked_or_seeded != 0, pol, plan, chain_of);
+	*out_lockstep = kind == JM_RECON_LEVELS ? 0 : plan.lockstep;
+	*out_rows = kind == JM_RECON_LEVELS ? 0 : plan.rows;
+	return (int)kind;
+}
+
 // The index phases (index_tables.h) over ONE stream's bytes with a live stream's flags (JmStream::live_flags / live_limit):
 // per picture start code out_pos / out_end_pos (0xffffffff: held) / out_decoded / out_mb_index, at most `cap`; hdr[0] = valid
 // (-1: a header has begun, hdr[1] = where), hdr[1] = width, hdr[2] = height, hdr[3] = 1 if a header was found in THIS range.

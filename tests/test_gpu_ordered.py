@@ -143,7 +143,7 @@ def test_the_lockstep_width_follows_the_picture_size(hip_lib):
 def test_a_launch_that_flags_itself_is_done_over(hip_lib):
     """JSMPEG_HIP_RECON_BREAK: one picture of the plan never reports, its successor's wait runs out of (shortened)
     patience, the launch flags itself -- the frames are rebuilt level by level before the sync returns, the result is
-    the golden one, and the batch stays with per-level launches"""
+    the golden one, and the batch stays with per-level launches, also after set_reconstruct("auto")"""
     code = r'''
 import hashlib, json, os, sys
 sys.path.insert(0, %r)
@@ -152,7 +152,9 @@ fx = json.load(open(os.path.join(%r, "tests", "golden", "frames_long_gop_p_chain
 es, _ = synth.generate_config(fx["config"], n_frames=fx["n_frames"], **fx["overrides"])
 with jb.Batch(fx["info"]["width"], fx["info"]["height"], 8, 8 * fx["n_frames"] + 4, 8 * (len(es) + 64) + 8192) as b:
     b.upload([es] * 8)
-    for rep in range(2):
+    for rep in range(3):
+        if rep == 2:
+            b.set_reconstruct("auto")
         assert b.decode() == 8 * fx["n_frames"]
         info = b.recon_info()
         print("INFO", rep, info)

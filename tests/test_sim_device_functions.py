@@ -201,6 +201,78 @@ def test_ordered_plan_properties(sim):
         assert lockstep == min(group, min(len({stream[p] for p in seq[c::8] if p >= 0}) for c in range(8)))
 
 
+def choose_recon(sim, n_streams, per_stream, gop, size=(1920, 1080), roots_x16=203, desc_cap=None, link_prev=None, seeded=False,
+                 levels=0, order=-1, dense=-1, chains=0, demoted=0):
+    """jm_choose_recon on a synthetic batch: n_streams streams of per_stream pictures, an intra picture every `gop`, the others
+    predicted from the picture before; -> (kind, lockstep) with kind "levels" / "streams" / "chains" """
+    decoded, fwd, stream, level = [], [], [], []
+    for s_ in range(n_streams):
+        for i in range(per_stream):
+            p = len(decoded)
+            decoded.append(1); stream.append(s_)
+            fwd.append(-1 if i % gop == 0 else p - 1)
+            level.append(i % gop)
+    n = len(decoded)
+    if desc_cap is None:
+        desc_cap = 2 * (n + 4) + 64              # what a batch created for these pictures has (engine.hip batch_alloc)
+    lp = (ctypes.c_int32 * n_streams)(*link_prev) if link_prev is not None else None
+    lock, rows = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    kind = sim.sim_choose_recon(n, n_streams, (ctypes.c_uint8 * n)(*decoded), (ctypes.c_int32 * n)(*fwd), (ctypes.c_uint32 * n)(*stream),
+                                (ctypes.c_int32 * n)(*level), size[0], size[1], desc_cap, roots_x16, lp, int(link_prev is not None or seeded),
+                                levels, order, dense, chains, demoted, ctypes.byref(lock), ctypes.byref(rows))
+    return ("levels", "streams", "chains")[kind], lock.value
+
+
+def test_recon_plan_choice(sim):
+    """jm_choose_recon (recon_plan.h): every rule that picks between one launch per dependency level and the ordered launch
+    over streams or GOP chains -- the expected answers are the engine's rules as they were before the choice became a
+    function of its own"""
+    hd, p720, tiny = (1920, 1080), (1280, 720), (176, 144)
+    cases = [
+        # (what, arguments, kind, lockstep)
+        ("no predicted picture", dict(n_streams=16, per_stream=13, gop=1), "levels", 0),
+        ("cfg2 16 x 13: two streams per class, the auto group (3) capped by the class", dict(n_streams=16, per_stream=13, gop=13), "streams", 2),
+        ("16 x 120 of 1080p: below the wide rule", dict(n_streams=16, per_stream=120, gop=12), "streams", 2),
+        ("64 x 120 of 1080p: wide", dict(n_streams=64, per_stream=120, gop=12), "levels", 0),
+        ("32 x 120 of 1080p: wide", dict(n_streams=32, per_stream=120, gop=12), "levels", 0),
+        ("dense intra roots", dict(n_streams=16, per_stream=13, gop=13, roots_x16=310), "levels", 0),
+        ("dense intra roots, JSMPEG_HIP_RECON_DENSE=1", dict(n_streams=16, per_stream=13, gop=13, roots_x16=400, dense=1), "levels", 0),
+        ("dense intra roots, the dense rule off", dict(n_streams=16, per_stream=13, gop=13, roots_x16=400, dense=0), "streams", 2),
+        ("dense intra roots, 16 levels deep", dict(n_streams=16, per_stream=20, gop=20, roots_x16=400), "streams", 2),
+        ("small pictures: too close in lockstep, chains no better", dict(n_streams=16, per_stream=13, gop=13, size=tiny), "levels", 0),
+        ("small pictures, a forced width", dict(n_streams=16, per_stream=13, gop=13, size=tiny, order=2), "streams", 2),
+        ("a forced width on a wide batch", dict(n_streams=64, per_stream=120, gop=12, order=2), "streams", 2),
+        ("a forced width of 0", dict(n_streams=16, per_stream=13, gop=13, order=0), "levels", 0),
+        ("the levels setting", dict(n_streams=16, per_stream=13, gop=13, levels=1), "levels", 0),
+        ("the levels setting over a forced width", dict(n_streams=16, per_stream=13, gop=13, levels=1, order=2), "levels", 0),
+        ("demoted", dict(n_streams=16, per_stream=13, gop=13, demoted=1), "levels", 0),
+        ("demoted, a forced width", dict(n_streams=16, per_stream=13, gop=13, order=2, demoted=1), "levels", 0),
+        ("demoted, forced chains", dict(n_streams=16, per_stream=13, gop=13, chains=1, demoted=1), "levels", 0),
+        ("the descriptor table too small", dict(n_streams=16, per_stream=13, gop=13, desc_cap=8 * 26 - 1), "levels", 0),
+        ("the descriptor table just large enough", dict(n_streams=16, per_stream=13, gop=13, desc_cap=8 * 26), "streams", 2),
+        ("forced chains", dict(n_streams=16, per_stream=13, gop=13, chains=1), "chains", 2),
+        ("forced chains on a wide batch", dict(n_streams=64, per_stream=120, gop=12, chains=1), "chains", 3),
+        ("forced chains under the levels setting", dict(n_streams=16, per_stream=13, gop=13, chains=1, levels=1), "levels", 0),
+        ("forced chains with links", dict(n_streams=16, per_stream=13, gop=13, chains=1, link_prev=[-1] * 16), "levels", 0),
+        ("linked pairs of streams, a forced width: one stream per class", dict(n_streams=16, per_stream=13, gop=13, order=2,
+                                                                              link_prev=[-1 if s % 2 == 0 else s - 1 for s in range(16)]), "streams", 1),
+        ("linked pairs of streams, auto: too close, no chains", dict(n_streams=16, per_stream=13, gop=13,
+                                                                    link_prev=[-1 if s % 2 == 0 else s - 1 for s in range(16)]), "levels", 0),
+        ("one 720p stream, 192 pictures, GOP 6", dict(n_streams=1, per_stream=192, gop=6, size=p720), "chains", None),
+        ("... with a link", dict(n_streams=1, per_stream=192, gop=6, size=p720, link_prev=[-1]), "levels", 0),
+        ("... with a seed", dict(n_streams=1, per_stream=192, gop=6, size=p720, seeded=True), "levels", 0),
+        ("... a forced width: no chains", dict(n_streams=1, per_stream=192, gop=6, size=p720, order=3), "levels", 0),
+        ("... forced chains", dict(n_streams=1, per_stream=192, gop=6, size=p720, chains=1), "chains", None),
+    ]
+    for what, kw, kind, lockstep in cases:
+        got = choose_recon(sim, **kw)
+        assert got[0] == kind, (what, got)
+        if lockstep is None:
+            assert got[1] >= 3, (what, got)      # 32 GOP chains: four per class, at least three of them in lockstep
+        else:
+            assert got[1] == lockstep, (what, got)
+
+
 def test_ordered_plan_benchmark_shape(sim):
     """64 equal streams x 120 pictures, GOP 12, two streams in lockstep per class: 960 rows, no padding, predecessor exactly
     two places back except where a class moves on to its next pair of streams"""
