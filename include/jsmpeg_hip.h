@@ -195,8 +195,28 @@ int64_t jsmpeg_hip_batch_read_es(jsmpeg_hip_batch_t *b, uint32_t stream, void *o
  * meanwhile), whose report of unwritten macroblocks decides the order of the
  * remaining reconstruct launches.  Returns the number of pictures found or < 0. */
 int jsmpeg_hip_batch_decode(jsmpeg_hip_batch_t *b, void *hip_stream);
-/* Waits for the last decode; returns 0 or < 0. */
+/* Waits for the last decode (or enqueued pass, which it settles); returns 0 or < 0. */
 int jsmpeg_hip_batch_sync(jsmpeg_hip_batch_t *b);
+/* The same pass as a PURE ENQUEUE: start-code index -> a plan built on the device (the parse's sizing, `stale`, the ordered
+ * reconstruct's sequence and descriptors) -> slice parse -> ONE ordered reconstruct launch, all on `hip_stream`, with no host
+ * wait of any kind -- so one host thread keeps any number of batches in flight.  Returns 0: the
+ * pass is enqueued; its results are there once jsmpeg_hip_batch_sync has settled it (every call below that reads results
+ * settles it first: picture_count, picture_info, read_frame(s), frame_hashes, render_rgba*, counters, recon_info, timings,
+ * level_timings, uncovered, stream_info).  sync reports what decode reports -- a table overflow with decode's message --, redoes
+ * a flagged ordered launch level by level, checks GOP chains, and reconstructs a pass the device could not order (one long
+ * stream, badly ragged chains: recon_info status 8) level by level there.  Returns 1: the batch cannot be planned on the
+ * device -- linked or seeded streams, live handles, a batch set to go level by level (set_reconstruct(0),
+ * JSMPEG_HIP_RECON_ORDER=0, or demoted by a flagged ordered launch) -- and jsmpeg_hip_batch_decode ran instead, with the same
+ * results.  < 0: an argument error.  While an enqueued pass is not settled, upload*, attach_device, link_streams, seed_stream,
+ * decode and enqueue on the batch FAIL ("... in flight: call jsmpeg_hip_batch_sync first"); nothing waits behind the caller's
+ * back.  The device plans ONE ordered launch for every batch it can order -- also for the batches decode's engine sends level
+ * by level (all-intra and dense-intra batches, wide shallow ones: 1-3 % faster per level one batch at a time); a host that wants
+ * those per-level launches calls decode (set_reconstruct(0) makes enqueue do so).  timings[1] of an enqueued pass is 0; of a
+ * pass reconstructed at sync (status 8), timings[3] is the level launches' span. */
+int jsmpeg_hip_batch_enqueue(jsmpeg_hip_batch_t *b, void *hip_stream);
+/* 1 if the last pass's work on the device has finished (or there is none), 0 if not; never blocks, never settles (a host
+ * without threads polls this, then calls jsmpeg_hip_batch_sync).  < 0 on error. */
+int jsmpeg_hip_batch_query(jsmpeg_hip_batch_t *b);
 /* A HIP stream of the batch's own (created on first use, destroyed with the batch) to pass as `hip_stream`, for hosts that link
  * no HIP runtime to make one with (the N-API addon's decodeAsync): two batches in flight need a
  * stream EACH -- on the null stream their passes run one behind the other.  Returns it, or NULL (jsmpeg_hip_last_error). */

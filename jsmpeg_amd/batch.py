@@ -22,6 +22,7 @@ class PictureInfo(ctypes.Structure):
 
 BATCH_SYMBOLS = ("jsmpeg_hip_batch_create", "jsmpeg_hip_batch_destroy", "jsmpeg_hip_batch_upload",
                  "jsmpeg_hip_batch_upload_device", "jsmpeg_hip_batch_attach_device", "jsmpeg_hip_batch_decode", "jsmpeg_hip_batch_sync",
+                 "jsmpeg_hip_batch_enqueue", "jsmpeg_hip_batch_query",
                  "jsmpeg_hip_batch_picture_count", "jsmpeg_hip_batch_picture_info", "jsmpeg_hip_batch_geometry",
                  "jsmpeg_hip_batch_frame_pool", "jsmpeg_hip_batch_read_frame", "jsmpeg_hip_batch_read_frames", "jsmpeg_hip_batch_frame_hashes",
                  "jsmpeg_hip_batch_timings", "jsmpeg_hip_batch_level_timings", "jsmpeg_hip_batch_counters", "jsmpeg_hip_batch_recon_info", "jsmpeg_hip_batch_link_streams", "jsmpeg_hip_batch_seed_stream", "jsmpeg_hip_batch_uncovered", "jsmpeg_hip_batch_render_rgba",
@@ -56,6 +57,10 @@ def lib():
         L.jsmpeg_hip_batch_decode.argtypes = [vp, vp]
         L.jsmpeg_hip_batch_sync.restype = ctypes.c_int
         L.jsmpeg_hip_batch_sync.argtypes = [vp]
+        L.jsmpeg_hip_batch_enqueue.restype = ctypes.c_int
+        L.jsmpeg_hip_batch_enqueue.argtypes = [vp, vp]
+        L.jsmpeg_hip_batch_query.restype = ctypes.c_int
+        L.jsmpeg_hip_batch_query.argtypes = [vp]
         L.jsmpeg_hip_batch_picture_count.restype = u32
         L.jsmpeg_hip_batch_picture_count.argtypes = [vp]
         L.jsmpeg_hip_batch_picture_info.restype = ctypes.c_int
@@ -199,6 +204,16 @@ class Batch:
 
     def sync(self):
         self._ok(self.L.jsmpeg_hip_batch_sync(self.h))
+
+    def enqueue(self, stream=None):
+        """The pass as a pure enqueue on `stream` (planned on the device, no host wait): 0.  1: the batch cannot be planned
+        on the device (linked / seeded streams, set to go level by level) and decode ran instead.  Results after sync()
+        (or any reader, which settles the pass first); upload / decode / enqueue before that raise."""
+        return self._ok(self.L.jsmpeg_hip_batch_enqueue(self.h, stream))
+
+    def query(self):
+        """True once the last pass's work on the device has finished; never waits, never settles"""
+        return bool(self._ok(self.L.jsmpeg_hip_batch_query(self.h)))
 
     @property
     def picture_count(self):

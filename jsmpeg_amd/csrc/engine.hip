@@ -27,6 +27,9 @@ extern "C" int jsmpeg_hip_device_count(void) {
 	return n;
 }
 
+/* uploads, decode and enqueue on a batch whose enqueued pass is not settled fail with this (include/jsmpeg_hip.h) */
+static const char *const k_in_flight = "a pass of this batch is in flight (jsmpeg_hip_batch_enqueue): call jsmpeg_hip_batch_sync first";
+
 /* ------------------------------------------------------------ shared state */
 
 static JmVlcLuts *g_luts_dev[16] = { nullptr };
@@ -55,7 +58,7 @@ void batch_free(jsmpeg_hip_batch_t *b) {
 	hipFree(b->d_es); hipFree(b->d_streams); hipFree(b->d_scan_state); hipFree(b->d_sc_pos);
 	hipFree(b->d_sc_code); hipFree(b->d_sc_owner); hipFree(b->d_pic_sc); hipFree(b->d_slice_sc); hipFree(b->d_slice_order); hipFree(b->d_order_hist); hipFree(b->d_counters);
 	hipFree(b->d_pics); hipFree(b->d_desc); hipFree(b->d_covered); hipFree(b->d_mb); hipFree(b->d_tokens);
-	hipFree(b->d_done); hipFree(b->d_rstatus);
+	hipFree(b->d_done); hipFree(b->d_rstatus); hipFree(b->d_plan); hipFree(b->d_plan_u32);
 	if (b->h_rstatus) hipHostFree(b->h_rstatus);
 	hipFree(b->d_pool_alloc); hipFree(b->d_hashes); hipFree(b->d_dbg); hipFree(b->d_rgba);
 	hipFree(b->d_ts); hipFree(b->d_ts_rec); hipFree(b->d_ts_es_off); hipFree(b->d_ts_cand); hipFree(b->d_ts_writes); hipFree(b->d_ts_begin); hipFree(b->d_ts_len); hipFree(b->d_ts_small);
@@ -118,6 +121,12 @@ static int batch_alloc(jsmpeg_hip_batch_t *b) {
 	HIP_TRY(hipHostGetDevicePointer(&b->h_pics_dev, b->h_pics, 0));
 	for (auto &e : b->ev) HIP_TRY(hipEventCreate(&e));
 	for (auto &e : b->ev_level) HIP_TRY(hipEventCreate(&e));
+	/* the device plan of enqueued passes: the plan block, and the planner's scratch -- dec, chain_id, stale, cstart, cend
+	 * [max_pictures] each, ustart, uend [max_streams], seq [8 rows_cap] */
+	const uint32_t mp = std::max(1u, c.max_pictures), ms = std::max(1u, c.max_streams);
+	b->rows_cap = (uint32_t)((uint64_t)c.max_pictures * (100 + 8) / 800);
+	HIP_TRY(jm_malloc(&b->d_plan, sizeof(JmDevPlan)));
+	HIP_TRY(jm_malloc(&b->d_plan_u32, sizeof(uint32_t) * (5 * (size_t)mp + 2 * (size_t)ms + 8 * (size_t)b->rows_cap + 8)));
 	return 0;
 }
 
@@ -219,6 +228,7 @@ extern "C" int jsmpeg_hip_batch_upload(jsmpeg_hip_batch_t *b, uint32_t n_streams
                                        const uint64_t *es_bytes) {
 	g_err[0] = 0;
 	if (!b) return fail("null batch");
+	if (b->enq_pending) return fail("upload: %s", k_in_flight);
 	HIP_TRY(hipSetDevice(b->device));
 	if (batch_layout(b, n_streams, es_bytes) != 0) return -1;
 	/* gaps (and everything else) 0xff: can never complete a 00 00 01 */
@@ -272,6 +282,7 @@ static int upload_ts_impl(jsmpeg_hip_batch_t *b, uint32_t n_streams, const uint8
                           const uint32_t *n_writes, const uint64_t *write_bytes, uint32_t stream_id) {
 	g_err[0] = 0;
 	if (!b || (n_streams && (!ts || !ts_bytes))) return fail("null argument");
+	if (b->enq_pending) return fail("upload_ts: %s", k_in_flight);
 	if (n_streams > b->cfg.max_streams) return fail("%u streams > max_streams %u", n_streams, b->cfg.max_streams);
 	if (stream_id == 0 || stream_id > 255) return fail("stream id %u out of range", stream_id);
 	HIP_TRY(hipSetDevice(b->device));
@@ -397,6 +408,7 @@ extern "C" int jsmpeg_hip_batch_upload_device(jsmpeg_hip_batch_t *b, const void 
                                               void *hip_stream) {
 	g_err[0] = 0;
 	if (!b) return fail("null batch");
+	if (b->enq_pending) return fail("upload_device: %s", k_in_flight);
 	HIP_TRY(hipSetDevice(b->device));
 	hipStream_t st = (hipStream_t)hip_stream;
 	std::vector<uint64_t> lens(n_streams);
@@ -431,6 +443,7 @@ extern "C" int jsmpeg_hip_batch_attach_device(jsmpeg_hip_batch_t *b, const void 
                                               void *hip_stream) {
 	g_err[0] = 0;
 	if (!b) return fail("null batch");
+	if (b->enq_pending) return fail("attach_device: %s", k_in_flight);
 	HIP_TRY(hipSetDevice(b->device));
 	hipStream_t st = (hipStream_t)hip_stream;
 	if (n_streams > b->cfg.max_streams) return fail("%u streams > max_streams %u", n_streams, b->cfg.max_streams);
@@ -616,11 +629,19 @@ static int enqueue_index(jsmpeg_hip_batch_t *b, hipStream_t st) {
 	return 0;
 }
 
-struct ParseSizing { uint64_t long_slices, crit_bytes, crit_pics; };    /* what the parse's launch wants to know of the pictures */
+/* The walk over the picture table (enqueue_plan.h jm_walk_picture: one source with the device planner): decoded pictures,
+ * their slices, and what the parse's launch wants to know of them (ps: the estimate of long slices, bytes per macroblock). */
+static void batch_walk(jsmpeg_hip_batch_t *b, JmParseSizing &ps) {
+	JmWalkSums w = { 0, 0, 0, 0, 0, 0, 0 };
+	const uint32_t lanes = std::min(b->h_counters[4], b->sc_cap);
+	for (uint32_t p = 0; p < b->n_pics; p++) jm_walk_picture(b->h_pics, b->n_pics, p, b->h_streams.data(), b->n_streams, lanes, b->es_bytes, w);
+	b->n_decoded = (uint32_t)w.n_decoded; b->n_slices = (uint32_t)w.n_slices;
+	jm_parse_sizing_from_walk(w, lanes, b->es_bytes, b->g.mb_size, ps, &b->roots_x16);
+}
 
 /* The decode's one host wait: the index's counters and picture table, and ONE walk over the table for everything the parse's
  * launch and the reconstruct's plan want to know (it was three; the passes did not notice). */
-static int collect_index(jsmpeg_hip_batch_t *b, hipStream_t st, ParseSizing &ps, HostTrace &tr) {
+static int collect_index(jsmpeg_hip_batch_t *b, hipStream_t st, JmParseSizing &ps, HostTrace &tr) {
 	HIP_TRY(hipEventSynchronize(b->ev_idx));
 	tr.mark("index-done");
 	if (b->h_counters[2]) return fail("start-code / picture table overflow: %u start codes, %u pictures (max_pictures %u)",
@@ -638,28 +659,13 @@ static int collect_index(jsmpeg_hip_batch_t *b, hipStream_t st, ParseSizing &ps,
 	 * picture's bytes / its slices against the batch's -- the slices come longest first, jm_launch_parse gives that many fewer
 	 * lanes per wavefront when the pass is of a size where it pays), and the compressed bytes per macroblock of the pictures
 	 * without a forward reference (the reconstruct's dense intra rule) */
-	ps = ParseSizing{ 0, 0, 0 };
-	uint64_t root_bytes = 0, roots = 0;
-	const uint64_t lanes = std::min(b->h_counters[4], b->sc_cap);
-	for (uint32_t p = 0; p < b->n_pics; p++) {
-		const JmPic &pic = b->h_pics[p];
-		if (!pic.decoded) continue;
-		b->n_decoded++; b->n_slices += pic.n_slices;
-		if (pic.stream >= b->n_streams) continue;
-		const uint32_t end = p + 1 < b->n_pics && b->h_pics[p + 1].stream == pic.stream ? b->h_pics[p + 1].pos : b->h_streams[pic.stream].es_end;
-		const uint64_t bytes = end > pic.pos ? end - pic.pos : 0;
-		if (pic.fwd < 0) { root_bytes += bytes; roots++; }
-		if (!pic.n_slices) continue;
-		if (bytes * 2 * lanes >= (uint64_t)3 * b->es_bytes * pic.n_slices) ps.long_slices += pic.n_slices;   /* >= 1.5 x the mean slice */
-		if (bytes * lanes >= (uint64_t)4 * b->es_bytes * pic.n_slices) { ps.crit_bytes += bytes; ps.crit_pics++; }   /* >= 4 x: coded video's intra pictures */
-	}
-	b->roots_x16 = roots ? (uint32_t)std::min<uint64_t>(root_bytes * 16 / (roots * (uint64_t)std::max(1, b->g.mb_size)), 0xffffffffu) : 0u;
+	batch_walk(b, ps);
 	if (b->live && live_assign_slots(b->live) < 0) return -1;      /* live streams: which pool slot each picture of this pass is written to */
 	return 0;
 }
 
 /* ---- 3. slice parse: every slice of the batch at once ---- */
-static int enqueue_parse(jsmpeg_hip_batch_t *b, hipStream_t st, const ParseSizing &ps, HostTrace &tr) {
+static int enqueue_parse(jsmpeg_hip_batch_t *b, hipStream_t st, const JmParseSizing &ps, HostTrace &tr) {
 	if (b->n_pics) HIP_TRY(hipMemsetAsync(b->d_covered, 0, sizeof(uint32_t) * b->n_pics, st));
 	if (++b->epoch == 0) {
 		HIP_TRY(hipMemsetAsync(b->d_mb, 0, sizeof(JmMbRec) * (size_t)b->mb_pictures * b->g.mb_size, st));
@@ -674,18 +680,14 @@ static int enqueue_parse(jsmpeg_hip_batch_t *b, hipStream_t st, const ParseSizin
 	pb.cu_order = b->d_order_hist + 2 * JM_ORDER_BINS + 16;
 	pb.slice_sc = b->d_slice_order;             /* (ordered by step 2, beside the host's turn-around) */
 	pb.n_lanes = std::min(b->h_counters[4], b->sc_cap);   /* a lane per slice code (not per start code) */
-	pb.long_slices = pb.n_lanes ? (uint32_t)std::min<uint64_t>(ps.long_slices + ps.long_slices / 8, pb.n_lanes) : 0;   /* + 1/8: the estimate is by picture, the order by slice */
-	pb.bytes_per_mb_x16 = 0; pb.t_cold = 0;
-	{   /* compressed bytes per macroblock of the decoded pictures: what the parse's header-step threshold follows */
-		const uint64_t n_dec = b->n_decoded;
-		if (n_dec) pb.bytes_per_mb_x16 = (uint32_t)std::min<uint64_t>(1u << 20, (uint64_t)b->es_bytes * 16 / (n_dec * (uint64_t)std::max(1, b->g.mb_size)));
-		/* ... unless the pass has pictures whose slices are several times the mean (coded video: an intra picture is 10-30 x a
-		 * predicted one): the pass then lasts as long as THEIR slices' walk, and the figure that sets the threshold and the ring's
-		 * service form is theirs -- encoder-made 1080p at 16 Mbit/s (8 bytes per macroblock over all, 57 in the intra pictures):
-		 * parse 7.04 -> 6.60 ms with the dense settings (profiles/r06l_tcold_enc.txt); the generator's configurations have no such
-		 * pictures (intra ~2 x predicted) and keep theirs */
-		if (ps.crit_pics) pb.bytes_per_mb_x16 = std::max(pb.bytes_per_mb_x16, (uint32_t)std::min<uint64_t>(1u << 20, ps.crit_bytes * 16 / (ps.crit_pics * (uint64_t)std::max(1, b->g.mb_size))));
-	}
+	/* + 1/8 on the estimate of long slices: it is by picture, the order by slice.  The compressed bytes per macroblock of the
+	 * decoded pictures set the parse's header-step threshold -- unless the pass has pictures whose slices are several times the
+	 * mean (coded video: an intra picture is 10-30 x a predicted one): the pass then lasts as long as THEIR slices' walk, and the
+	 * figure that sets the threshold and the ring's service form is theirs -- encoder-made 1080p at 16 Mbit/s (8 bytes per
+	 * macroblock over all, 57 in the intra pictures): parse 7.04 -> 6.60 ms with the dense settings (profiles/r06l_tcold_enc.txt);
+	 * the generator's configurations have no such pictures (intra ~2 x predicted) and keep theirs (batch_walk) */
+	pb.long_slices = ps.long_slices; pb.bytes_per_mb_x16 = ps.bytes_per_mb_x16; pb.t_cold = 0;
+	pb.plan = nullptr;
 	pb.debug_flags = b->debug_flags;
 	pb.dbg = nullptr;
 	if (pb.debug_flags & 4) {   /* diagnostics: per-slice abort record, parked in the (unused) hash buffer's neighbour */
@@ -738,6 +740,8 @@ static int enqueue_ordered(jsmpeg_hip_batch_t *b, const JmOrderedPlan &plan, con
 extern "C" int jsmpeg_hip_batch_decode(jsmpeg_hip_batch_t *b, void *hip_stream) {
 	g_err[0] = 0;
 	if (!b) return fail("null batch");
+	if (b->enq_pending) return fail("decode: %s", k_in_flight);
+	b->enqueued = false; b->enq_failed = false;
 	HostTrace tr(b->trace);
 	HIP_TRY(hipSetDevice(b->device));
 	hipStream_t st = (hipStream_t)hip_stream;
@@ -747,7 +751,7 @@ extern "C" int jsmpeg_hip_batch_decode(jsmpeg_hip_batch_t *b, void *hip_stream) 
 	if (b->n_streams == 0) return 0;
 	if (enqueue_index(b, st) < 0) return -1;
 	tr.mark("index-enqueued");
-	ParseSizing ps;
+	JmParseSizing ps;
 	if (collect_index(b, st, ps, tr) < 0 || enqueue_parse(b, st, ps, tr) < 0) return -1;
 
 	/* The reconstruct plan.  A picture comes after its forward reference -- and, if it leaves macroblocks UNWRITTEN, after
@@ -777,6 +781,155 @@ extern "C" int jsmpeg_hip_batch_decode(jsmpeg_hip_batch_t *b, void *hip_stream) 
 	tr.mark("levels-enqueued");
 	b->timed = true;
 	return (int)b->n_pics;
+}
+
+/* ---- the pass as a pure enqueue: index, device plan, parse, ordered reconstruct -- the host reads nothing back ---- */
+
+extern "C" int jsmpeg_hip_batch_enqueue(jsmpeg_hip_batch_t *b, void *hip_stream) {
+	g_err[0] = 0;
+	if (!b) return fail("null batch");
+	if (b->enq_pending) return fail("enqueue: %s", k_in_flight);
+	b->enq_failed = false;
+	/* what the device does not plan: live handles, linked / seeded streams, batches set to go level by level -- the blocking decode */
+	if (b->live || !b->link_prev.empty() || !b->seeded.empty() || b->recon.levels || b->recon.demoted || b->recon.order == 0) {
+		b->enqueued = false;
+		return jsmpeg_hip_batch_decode(b, hip_stream) < 0 ? -1 : 1;
+	}
+	HIP_TRY(hipSetDevice(b->device));
+	hipStream_t st = (hipStream_t)hip_stream;
+	b->stream = st;
+	b->timed = false; b->enqueued = true;
+	b->n_sc = b->n_pics = b->n_levels = b->n_decoded = b->n_slices = b->n_slice_codes = 0;
+	b->n_level_ev = 0; b->ordered = false; b->stats_pending = false; b->last_group = 0; b->ordered_status = 0; b->ordered_waits = 0;
+	b->chain_heads.clear();
+	if (b->n_streams == 0) return 0;
+	if (enqueue_index(b, st) < 0) return -1;
+	/* ---- the plan, on the device, behind the index and the slice order ---- */
+	const uint32_t mp = std::max(1u, b->cfg.max_pictures), ms = std::max(1u, b->cfg.max_streams);
+	JmPlanArgs a;
+	a.counters = b->d_counters; a.pics = b->d_pics; a.streams = b->d_streams;
+	a.n_streams = b->n_streams; a.es_bytes = b->es_bytes; a.sc_cap = b->sc_cap; a.pic_cap = b->cfg.max_pictures;
+	a.mb_size = b->g.mb_size; a.debug_flags = b->debug_flags;
+	a.ov = jm_parse_overrides();
+	/* the reconstruct: jm_choose_recon's group and the kinds it tries -- the engine's own choice (by streams, else by GOP
+	 * chains), JSMPEG_HIP_RECON_ORDER=n (by streams, n in lockstep, no distance rule), JSMPEG_HIP_RECON_CHAINS (chains only) */
+	const bool own = b->recon.order < 0;
+	a.tiles_per_picture = jm_recon_tiles_per_picture(b->g);
+	a.group = own ? 1 + (JM_ORDER_DISTANCE + a.tiles_per_picture - 1) / a.tiles_per_picture : (uint32_t)b->recon.order;
+	a.try_streams = !b->recon.chains; a.try_chains = own || b->recon.chains;
+	a.streams_forced = !own; a.chains_forced = b->recon.chains;
+	a.brk = b->recon.brk;
+	a.rows_cap = b->rows_cap;
+	uint32_t *u = b->d_plan_u32;
+	a.dec = u; a.chain_id = u + mp; a.stale = (int32_t *)(u + 2 * (size_t)mp); a.cstart = u + 3 * (size_t)mp; a.cend = u + 4 * (size_t)mp;
+	a.ustart = u + 5 * (size_t)mp; a.uend = a.ustart + ms; a.seq = a.uend + ms;
+	a.plan = b->d_plan; a.covered = b->d_covered; a.done = b->d_done; a.status = b->d_rstatus;
+	JmPlanDescBufs d;
+	d.desc = b->d_desc; d.tokens = b->d_tokens; d.mb = b->d_mb; d.pool = b->d_pool; d.frame_bytes = b->g.frame_bytes;
+	HIP_TRY(jm_launch_plan(a, d, st));
+	/* (index_ms runs to the end of the plan: an enqueued pass has no host turn-around, timings[1] is 0) */
+	HIP_TRY(hipEventRecord(b->ev[1], st));
+	if (++b->epoch == 0) {
+		HIP_TRY(hipMemsetAsync(b->d_mb, 0, sizeof(JmMbRec) * (size_t)b->mb_pictures * b->g.mb_size, st));
+		b->epoch = 1;
+	}
+	HIP_TRY(hipEventRecord(b->ev[2], st));
+	/* ---- the parse, sized by the plan ---- */
+	JmParseBufs pb;
+	memset(&pb, 0, sizeof pb);
+	pb.es = b->es_view; pb.sc_pos = b->d_sc_pos; pb.sc_code = b->d_sc_code; pb.sc_owner = b->d_sc_owner;
+	pb.pics = b->d_pics; pb.streams = b->d_streams; pb.luts = b->d_luts; pb.mb = b->d_mb; pb.tokens = b->d_tokens;
+	pb.mb_size = b->g.mb_size; pb.epoch = b->epoch; pb.covered = b->d_covered;
+	pb.ticket = b->d_order_hist + 2 * JM_ORDER_BINS;
+	pb.slice_sc = b->d_slice_order;
+	pb.debug_flags = b->debug_flags & ~4;        /* (the abort records of JSMPEG_HIP_DEBUG=4 are the blocking decode's) */
+	pb.plan = b->d_plan;
+	HIP_TRY(jm_launch_parse_planned(pb, st));
+	HIP_TRY(hipEventRecord(b->ev[3], st));
+	/* ---- ONE ordered reconstruct launch over every slot the batch can have: the plan's pictures, padding behind them ---- */
+	HIP_TRY(hipEventRecord(b->ev_level[0], st));
+	JmReconBufs rb = recon_bufs(b);
+	rb.desc = b->d_desc; rb.n_level_pics = 8 * b->rows_cap;
+	rb.need = 1; rb.status = b->d_rstatus; rb.done = b->d_done; rb.patience = b->recon.patience;
+	HIP_TRY(jm_launch_recon(rb, st));
+	b->n_level_ev = 1;
+	HIP_TRY(hipEventRecord(b->ev_level[1], st));
+	HIP_TRY(hipEventRecord(b->ev[4], st));
+	b->enq_pending = true;
+	return 0;
+}
+
+/* 1: the last pass's work on the device has finished (or there is none), 0: not yet.  Never waits, never settles. */
+extern "C" int jsmpeg_hip_batch_query(jsmpeg_hip_batch_t *b) {
+	g_err[0] = 0;
+	if (!b) return fail("null batch");
+	if (!b->enq_pending && !b->timed) return 1;
+	const hipError_t e = hipEventQuery(b->ev[4]);
+	if (e == hipSuccess) return 1;
+	if (e == hipErrorNotReady) return 0;
+	return fail("hipEventQuery: %s", hipGetErrorString(e));
+}
+
+static int batch_settle(jsmpeg_hip_batch_t *b);
+
+/* An enqueued pass once its stream has drained: what decode's host learns before the parse -- the counts, the overflow --
+ * and the plan's outcome: an ordered launch is checked by batch_settle like decode's (flagged: done over level by level; by
+ * GOP chains: the chain heads against the parse's counts), a pass the device could not order is reconstructed here, level by
+ * level (status 8). */
+static int settle_enqueued_pass(jsmpeg_hip_batch_t *b) {
+	int rc = 0;
+	do {
+		HIP_TRY(hipSetDevice(b->device));
+		HIP_TRY(hipStreamSynchronize(b->stream));
+		HIP_TRY(hipMemcpy(&b->h_plan, b->d_plan, sizeof(JmDevPlan), hipMemcpyDeviceToHost));
+		if (b->h_counters[2]) { rc = fail("start-code / picture table overflow: %u start codes, %u pictures (max_pictures %u)",
+		                                  b->h_counters[0], b->h_counters[1], b->cfg.max_pictures); break; }
+		b->n_sc = b->h_counters[0]; b->n_pics = b->h_counters[1]; b->n_levels = b->h_counters[3];
+		b->n_slice_codes = std::min(b->h_counters[4], b->sc_cap);
+		JmParseSizing ps;
+		batch_walk(b, ps);
+		if (b->n_pics) HIP_TRY(hipMemcpy(b->h_covered, b->d_covered, sizeof(uint32_t) * b->n_pics, hipMemcpyDeviceToHost));
+		HIP_TRY(hipEventRecord(b->ev_cov, b->stream));
+		b->timed = true;
+		if (b->h_plan.kind == JM_PLAN_HOST) {
+			if (!b->n_decoded) break;
+			std::vector<int32_t> stale;
+			const uint32_t n_roots = batch_plan_stale(b, stale);
+			HostTrace tr(false);
+			b->n_level_ev = 0;
+			if (recon_by_levels(b, stale, n_roots, b->stream, tr) < 0) { rc = -1; break; }
+			/* (ev[4] stays where the enqueue put it: timings reports this reconstruct from the level events, without the time the
+			 * host took to call sync) */
+			HIP_TRY(hipEventRecord(b->ev_level[b->n_level_ev], b->stream));
+			HIP_TRY(hipStreamSynchronize(b->stream));
+			b->ordered_status = 8;               /* planned on the host at sync */
+			break;
+		}
+		HIP_TRY(hipMemcpy(b->h_rstatus, b->d_rstatus, sizeof(uint32_t) * JM_RECON_STATUS_WORDS, hipMemcpyDeviceToHost));
+		b->ordered = true; b->stats_pending = true; b->last_group = b->h_plan.lockstep;
+		if (b->h_plan.kind == JM_PLAN_CHAINS) {
+			/* the pictures whose `stale` frame lies in another chain did not wait for it (enqueue_plan.h jm_plan_slot_waits) */
+			std::vector<int32_t> stale;
+			std::vector<uint32_t> chain_of;
+			batch_plan_stale(b, stale);
+			jm_plan_chains(b->h_pics, b->n_pics, b->n_streams, chain_of, nullptr);
+			for (uint32_t p = 0; p < b->n_pics; p++)
+				if (chain_of[p] != JM_NONE && stale[p] >= 0 && chain_of[stale[p]] != chain_of[p]) b->chain_heads.push_back(p);
+		}
+		rc = batch_settle(b);
+	} while (0);
+	return rc;
+}
+static int batch_settle_enqueued(jsmpeg_hip_batch_t *b) {
+	if (!b->enq_pending) return 0;
+	b->enq_pending = false;
+	const int rc = settle_enqueued_pass(b);      /* (every failure in there -- HIP_TRY's included -- lands here) */
+	if (rc < 0) {
+		b->enq_failed = true;
+		snprintf(b->enq_err, sizeof b->enq_err, "%s", g_err);
+		b->n_pics = 0;
+	}
+	return rc;
 }
 
 /* What is left of a decode once its stream has drained: the ordered launch's status (a launch that gave a wait up, or
@@ -837,14 +990,25 @@ static int batch_settle_pending(jsmpeg_hip_batch_t *b) {
 extern "C" int jsmpeg_hip_batch_sync(jsmpeg_hip_batch_t *b) {
 	g_err[0] = 0;
 	if (!b) return fail("null batch");
+	if (b->enq_pending) {
+		if (batch_settle_enqueued(b) < 0) { b->enq_failed = false; return -1; }
+	} else if (b->enq_failed) {
+		b->enq_failed = false;                   /* settled by a reader that failed: sync reports it (once, as decode reports it) */
+		return fail("%s", b->enq_err);
+	}
 	HIP_TRY(hipSetDevice(b->device));
 	HIP_TRY(hipStreamSynchronize(b->stream));
 	return batch_settle(b);
 }
 
-extern "C" uint32_t jsmpeg_hip_batch_picture_count(jsmpeg_hip_batch_t *b) { return b ? b->n_pics : 0; }
+extern "C" uint32_t jsmpeg_hip_batch_picture_count(jsmpeg_hip_batch_t *b) {
+	if (!b) return 0;
+	batch_settle_enqueued(b);          /* (an enqueued pass: its count, never the pass before's) */
+	return b->n_pics;
+}
 
 extern "C" int jsmpeg_hip_batch_picture_info(jsmpeg_hip_batch_t *b, uint32_t picture, jsmpeg_hip_picture_info_t *out) {
+	if (b && batch_settle_enqueued(b) < 0) return -1;
 	if (!b || !out || picture >= b->n_pics) return fail("bad picture index");
 	const JmPic &p = b->h_pics[picture];
 	out->stream = p.stream;
@@ -856,6 +1020,7 @@ extern "C" int jsmpeg_hip_batch_picture_info(jsmpeg_hip_batch_t *b, uint32_t pic
 extern "C" int jsmpeg_hip_batch_stream_info(jsmpeg_hip_batch_t *b, uint32_t stream, int32_t *width, int32_t *height, float *frame_rate) {
 	g_err[0] = 0;
 	if (!b || stream >= b->n_streams) return fail("bad stream index");
+	if (batch_settle_enqueued(b) < 0) return -1;
 	HIP_TRY(hipSetDevice(b->device));
 	HIP_TRY(hipStreamSynchronize(b->stream));
 	JmStream s;
@@ -883,6 +1048,7 @@ extern "C" void *jsmpeg_hip_batch_frame_pool(jsmpeg_hip_batch_t *b) { return b ?
 
 extern "C" int jsmpeg_hip_batch_read_frame(jsmpeg_hip_batch_t *b, uint32_t picture, void *y, void *cr, void *cb) {
 	g_err[0] = 0;
+	if (b && batch_settle_enqueued(b) < 0) return -1;
 	if (!b || picture >= b->n_pics) return fail("bad picture index");
 	HIP_TRY(hipSetDevice(b->device));
 	HIP_TRY(hipStreamSynchronize(b->stream));
@@ -896,6 +1062,7 @@ extern "C" int jsmpeg_hip_batch_read_frame(jsmpeg_hip_batch_t *b, uint32_t pictu
 
 extern "C" int jsmpeg_hip_batch_read_frames(jsmpeg_hip_batch_t *b, uint32_t first, uint32_t count, void *host, uint64_t stride) {
 	g_err[0] = 0;
+	if (b && batch_settle_enqueued(b) < 0) return -1;
 	if (!b || (count && !host) || (uint64_t)first + count > b->n_pics) return fail("bad picture range %u + %u of %u", first, count, b ? b->n_pics : 0u);
 	const size_t planes = (size_t)b->g.luma_bytes + 2 * (size_t)b->g.chroma_bytes;
 	if (count && stride < planes) return fail("stride %llu < the %llu bytes of a picture's planes", (unsigned long long)stride, (unsigned long long)planes);
@@ -915,6 +1082,7 @@ extern "C" int jsmpeg_hip_batch_read_frames(jsmpeg_hip_batch_t *b, uint32_t firs
 extern "C" int jsmpeg_hip_batch_frame_hashes(jsmpeg_hip_batch_t *b, uint64_t *out) {
 	g_err[0] = 0;
 	if (!b || !out) return fail("null argument");
+	if (batch_settle_enqueued(b) < 0) return -1;
 	HIP_TRY(hipSetDevice(b->device));
 	if (!b->n_pics) return 0;
 	if (b->ordered) { HIP_TRY(hipStreamSynchronize(b->stream)); if (batch_settle(b) < 0) return -1; }
@@ -931,6 +1099,7 @@ extern "C" int jsmpeg_hip_batch_render_rgba(jsmpeg_hip_batch_t *b, uint32_t firs
                                             void *dev_rgba, void *hip_stream) {
 	g_err[0] = 0;
 	if (!b || !dev_rgba) return fail("null argument");
+	if (batch_settle_enqueued(b) < 0) return -1;
 	if ((uint64_t)first_picture + count > b->n_pics) return fail("picture range [%u, %u) outside the %u decoded pictures", first_picture, first_picture + count, b->n_pics);
 	HIP_TRY(hipSetDevice(b->device));
 	if (batch_settle_pending(b) < 0) return -1;
@@ -948,6 +1117,7 @@ extern "C" int jsmpeg_hip_batch_render_rgba_gl(jsmpeg_hip_batch_t *b, uint32_t f
                                                void *dev_rgba, void *hip_stream) {
 	g_err[0] = 0;
 	if (!b || !dev_rgba) return fail("null argument");
+	if (batch_settle_enqueued(b) < 0) return -1;
 	if ((uint64_t)first_picture + count > b->n_pics) return fail("picture range [%u, %u) outside the %u decoded pictures", first_picture, first_picture + count, b->n_pics);
 	HIP_TRY(hipSetDevice(b->device));
 	if (batch_settle_pending(b) < 0) return -1;
@@ -963,6 +1133,7 @@ extern "C" int jsmpeg_hip_batch_render_rgba_gl(jsmpeg_hip_batch_t *b, uint32_t f
 extern "C" int jsmpeg_hip_batch_read_rgba_gl(jsmpeg_hip_batch_t *b, uint32_t picture, void *host_rgba) {
 	g_err[0] = 0;
 	if (!b || !host_rgba) return fail("null argument");
+	if (batch_settle_enqueued(b) < 0) return -1;
 	if (picture >= b->n_pics) return fail("bad picture index");
 	HIP_TRY(hipSetDevice(b->device));
 	const size_t bytes = (size_t)b->cfg.width * b->cfg.height * 4;
@@ -977,6 +1148,7 @@ extern "C" int jsmpeg_hip_batch_read_rgba_gl(jsmpeg_hip_batch_t *b, uint32_t pic
 extern "C" int jsmpeg_hip_batch_read_rgba(jsmpeg_hip_batch_t *b, uint32_t picture, void *host_rgba) {
 	g_err[0] = 0;
 	if (!b || !host_rgba) return fail("null argument");
+	if (batch_settle_enqueued(b) < 0) return -1;
 	if (picture >= b->n_pics) return fail("bad picture index");
 	HIP_TRY(hipSetDevice(b->device));
 	const size_t bytes = (size_t)b->cfg.width * b->cfg.height * 4;
@@ -989,16 +1161,25 @@ extern "C" int jsmpeg_hip_batch_read_rgba(jsmpeg_hip_batch_t *b, uint32_t pictur
 
 extern "C" int jsmpeg_hip_batch_timings(jsmpeg_hip_batch_t *b, float out_ms[5]) {
 	g_err[0] = 0;
+	if (b && batch_settle_enqueued(b) < 0) return -1;
 	if (!b || !b->timed) return fail("no timed decode");
 	HIP_TRY(hipSetDevice(b->device));
 	HIP_TRY(hipEventSynchronize(b->ev[4]));
 	for (int i = 0; i < 4; i++) HIP_TRY(hipEventElapsedTime(&out_ms[i], b->ev[i], b->ev[i + 1]));
+	if (b->enqueued) out_ms[1] = 0.f;      /* an enqueued pass: no host turn-around (ev[1] / ev[2] stand side by side behind the plan) */
+	if (b->enqueued && b->ordered_status == 8 && b->n_level_ev) {
+		/* reconstructed at sync: the level launches' own span (not the host's time before it called sync) */
+		HIP_TRY(hipEventSynchronize(b->ev_level[b->n_level_ev]));
+		HIP_TRY(hipEventElapsedTime(&out_ms[3], b->ev_level[0], b->ev_level[b->n_level_ev]));
+		out_ms[4] = out_ms[0] + out_ms[1] + out_ms[2] + out_ms[3];
+	}
 	HIP_TRY(hipEventElapsedTime(&out_ms[4], b->ev[0], b->ev[4]));
 	return 0;
 }
 
 extern "C" int jsmpeg_hip_batch_level_timings(jsmpeg_hip_batch_t *b, float *out_ms, uint32_t cap) {
 	g_err[0] = 0;
+	if (b && batch_settle_enqueued(b) < 0) return -1;
 	if (!b || !b->timed || !out_ms) return fail("no timed decode");
 	HIP_TRY(hipSetDevice(b->device));
 	HIP_TRY(hipEventSynchronize(b->ev[4]));
@@ -1010,6 +1191,7 @@ extern "C" int jsmpeg_hip_batch_level_timings(jsmpeg_hip_batch_t *b, float *out_
 
 extern "C" int jsmpeg_hip_batch_counters(jsmpeg_hip_batch_t *b, uint64_t out[8]) {
 	if (!b) return fail("null batch");
+	if (batch_settle_enqueued(b) < 0) return -1;
 	if (b->ordered || b->stats_pending) { HIP_TRY(hipSetDevice(b->device)); HIP_TRY(hipStreamSynchronize(b->stream)); if (batch_settle(b) < 0) return -1; }
 	out[0] = b->n_sc; out[1] = b->n_pics; out[2] = b->n_decoded; out[3] = b->n_levels; out[4] = b->n_slices;
 	out[5] = (uint64_t)b->g.mb_size;
@@ -1021,6 +1203,7 @@ extern "C" int jsmpeg_hip_batch_counters(jsmpeg_hip_batch_t *b, uint64_t out[8])
 extern "C" int jsmpeg_hip_batch_link_streams(jsmpeg_hip_batch_t *b, const int32_t *prev, uint32_t n) {
 	g_err[0] = 0;
 	if (!b) return fail("null batch");
+	if (b->enq_pending) return fail("link_streams: %s", k_in_flight);     /* (settling the pass reads the links) */
 	if (!prev) { b->link_prev.clear(); return 0; }
 	if (n != b->n_streams) return fail("link: %u entries for %u uploaded streams", n, b->n_streams);
 	for (uint32_t s = 0; s < n; s++)
@@ -1032,6 +1215,7 @@ extern "C" int jsmpeg_hip_batch_link_streams(jsmpeg_hip_batch_t *b, const int32_
 extern "C" int jsmpeg_hip_batch_seed_stream(jsmpeg_hip_batch_t *b, uint32_t stream, const void *dev_frame_last, const void *dev_frame_before_last) {
 	g_err[0] = 0;
 	if (!b) return fail("null batch");
+	if (b->enq_pending) return fail("seed_stream: %s", k_in_flight);
 	if (stream >= b->n_streams) return fail("seed: stream %u of %u", stream, b->n_streams);
 	if (b->seeded.size() != b->n_streams) { b->seeded.assign(b->n_streams, 0); b->seed_frames.assign(2 * (size_t)b->n_streams, nullptr); }
 	b->seeded[stream] = (uint8_t)((dev_frame_last ? 1 : 0) | (dev_frame_before_last ? 2 : 0));
@@ -1043,6 +1227,7 @@ extern "C" int jsmpeg_hip_batch_seed_stream(jsmpeg_hip_batch_t *b, uint32_t stre
 extern "C" int jsmpeg_hip_batch_uncovered(jsmpeg_hip_batch_t *b, uint8_t *out, uint32_t cap) {
 	g_err[0] = 0;
 	if (!b || !out) return fail("null argument");
+	if (batch_settle_enqueued(b) < 0) return -1;
 	HIP_TRY(hipSetDevice(b->device));
 	HIP_TRY(hipStreamSynchronize(b->stream));
 	if (batch_settle(b) < 0) return -1;
@@ -1055,6 +1240,7 @@ extern "C" int jsmpeg_hip_batch_uncovered(jsmpeg_hip_batch_t *b, uint8_t *out, u
 extern "C" int jsmpeg_hip_batch_recon_info(jsmpeg_hip_batch_t *b, uint32_t out[4]) {
 	g_err[0] = 0;
 	if (!b || !out) return fail("null argument");
+	if (batch_settle_enqueued(b) < 0) return -1;
 	if (b->ordered || b->stats_pending) { HIP_TRY(hipSetDevice(b->device)); HIP_TRY(hipStreamSynchronize(b->stream)); if (batch_settle(b) < 0) return -1; }
 	out[0] = b->n_level_ev; out[1] = b->last_group; out[2] = b->ordered_waits; out[3] = b->ordered_status;
 	return 0;
@@ -1065,6 +1251,7 @@ extern "C" int jsmpeg_hip_batch_recon_info(jsmpeg_hip_batch_t *b, uint32_t out[4
 extern "C" int jsmpeg_hip_batch_debug_read(jsmpeg_hip_batch_t *b, int what, void *dst, uint64_t offset, uint64_t bytes) {
 	g_err[0] = 0;
 	if (!b) return fail("null batch");
+	if (batch_settle_enqueued(b) < 0) return -1;
 	HIP_TRY(hipSetDevice(b->device));
 	HIP_TRY(hipStreamSynchronize(b->stream));
 	const uint8_t *src = nullptr;

@@ -147,6 +147,16 @@ struct jsmpeg_hip_batch_t {
 	                                number -- the table is sized for the start codes a pass can SEE --, the rest in a second copy when there are more) */
 	std::vector<uint32_t> slot;
 	struct jsmpeg_hip_live_t *live;
+	/* ENQUEUED passes (jsmpeg_hip_batch_enqueue): planned on the device (enqueue_plan.h), settled by the next call that reads
+	 * results (batch_settle_enqueued).  rows_cap: rows of the ordered launch's grid (max_pictures with jm_plan_ordered's 8 %
+	 * of slack); d_plan: the plan block; d_plan_u32: the planner's scratch (JmPlanArgs) */
+	uint32_t rows_cap;
+	JmDevPlan *d_plan, h_plan;
+	uint32_t *d_plan_u32;
+	bool enq_pending;            /* a pass is enqueued and not settled yet */
+	bool enqueued;               /* the last pass was enqueued (timings: no host turn-around) */
+	bool enq_failed;             /* ... and settling it failed: sync reports enq_err once */
+	char enq_err[512];
 };
 int live_assign_slots(struct jsmpeg_hip_live_t *l);    /* the live front end's turn inside a decode: once the picture table is on the host */
 static inline uint8_t *frame_of(const jsmpeg_hip_batch_t *b, uint32_t p) {

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "enqueue_plan.h"
 #include "mpeg1_dev.h"
 #include "vlc_lut.h"
 
@@ -110,8 +111,15 @@ struct JmParseBufs {
 	                                the next hb1 take hl1 each from head_first[1], the rest lanes_per_wave each from head_first[2] */
 	int debug_flags;             /* diagnostics only: 4 = per-slice abort records, 8 = always 64 slices per wavefront */
 	uint32_t *dbg;               /* diagnostics only: 4 words per start-code entry, or null */
+	const JmDevPlan *plan;       /* null: the launch's sizing above (jm_launch_parse); else jm_launch_parse_planned's kernels read n_sc, n_lanes and
+	                                the sizing from this plan block in device memory (k_plan), and the fields above are not looked at */
 };
 hipError_t jm_launch_parse(const JmParseBufs &b, hipStream_t st);
+/* The parse of an enqueued pass: sized on the device (b.plan, written by jm_launch_plan), always the ticketed grid that fills
+ * the GPU; both service forms are launched, the one the plan did not choose leaves at once.  b.ticket is required. */
+hipError_t jm_launch_parse_planned(const JmParseBufs &b, hipStream_t st);
+/* the host's reading of the parse's tuning overrides (JSMPEG_HIP_PARSE_*, _T_COLD): what jm_plan_parse applies */
+JmParseOverrides jm_parse_overrides();
 
 /* One picture of a reconstruct launch: everything a workgroup needs to start, as device addresses, in two scalar
  * loads (no pointer arithmetic on picture / stream numbers in the kernel, and fewer scalar registers held). */
@@ -157,6 +165,19 @@ struct JmReconBufs {
 hipError_t jm_launch_recon(const JmReconBufs &b, hipStream_t st);
 /* workgroups (tiles) k_recon takes per picture of this geometry */
 uint32_t jm_recon_tiles_per_picture(const JmGeom &g);
+
+/* The device plan of an enqueued pass (enqueue_plan.h): one workgroup behind the index and the slice order, everything the
+ * parse and the ordered reconstruct launch need, the descriptors of all 8 x rows_cap slots of that launch included (padding:
+ * dst == null).  Descriptor addresses: picture p's tokens at tokens + tok_off, records at mb + mb_index x mb_size, frame at
+ * pool + p x frame_bytes, matrices in streams[stream].intra_q. */
+struct JmPlanDescBufs {
+	JmReconDesc *desc;
+	const uint16_t *tokens;
+	const JmMbRec *mb;
+	uint8_t *pool;
+	uint64_t frame_bytes;
+};
+hipError_t jm_launch_plan(const JmPlanArgs &a, const JmPlanDescBufs &d, hipStream_t st);
 
 /* 64-bit content hash of each frame's 1.5 * coded_size plane bytes; slots (device memory, or null): frame f is pool slot slots[f] */
 hipError_t jm_launch_hash(const uint8_t *pool, uint64_t frame_bytes, uint32_t hashed_bytes, uint32_t n_frames,

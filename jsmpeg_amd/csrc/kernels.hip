@@ -524,12 +524,7 @@ hipError_t jm_launch_order(const JmOrderBufs &b, hipStream_t st) {
  * [32][64]-dword token ring tile in LDS (slice_parse.h) and schedules itself:
  * at every turn it runs the step kinds enough of its lanes are waiting for.
  * ---------------------------------------------------------------------- */
-#ifndef JM_PARSE_WG
-#define JM_PARSE_WG 512   /* 8 wavefronts share one copy of the tables: 2 workgroups = 16 wavefronts per CU */
-#endif
-#define JM_PARSE_WAVES (JM_PARSE_WG / 64)
-#define JM_PARSE_FILL_WAVES 4096u   /* wavefronts that fill the GPU for this kernel: 256 CUs x 16 */
-#define JM_PARSE_RESIDENT_WGS (JM_PARSE_FILL_WAVES / JM_PARSE_WAVES)
+/* (JM_PARSE_WG, the wavefronts that fill the GPU and the workgroups it holds: enqueue_plan.h, which the rules share) */
 
 /* SPLIT: the ring service in two halves a turn apart (slice_parse.h jm_lane_request / jm_lane_land).  Two kernels, not a
  * run-time switch: with both forms in one body the compiler keeps the requested chunks in one set of registers and copies
@@ -712,124 +707,66 @@ static __device__ __forceinline__ void jm_parse_body(const JmParseBufs &b) {
 __global__ __launch_bounds__(JM_PARSE_WG) void k_parse(JmParseBufs b) { jm_parse_body<false>(b); }
 __global__ __launch_bounds__(JM_PARSE_WG) void k_parse_split(JmParseBufs b) { jm_parse_body<true>(b); }
 
+/* The parse of an enqueued pass: the same body, its sizing read from the plan block the device planner wrote (k_plan) --
+ * the host never saw the counts.  Both service forms are launched; the one the plan did not choose leaves here, before it
+ * has touched the tables or the ticket. */
+template <bool SPLIT>
+static __device__ __forceinline__ void jm_parse_planned(const JmParseBufs &b_in) {
+	const JmDevPlan &P = *b_in.plan;
+	if (P.parse.split_service != (SPLIT ? 1u : 0u) || P.parse.n_batches == 0) return;
+	JmParseBufs b = b_in;
+	b.n_sc = P.n_sc; b.n_lanes = P.parse.n_lanes; b.n_batches = P.parse.n_batches;
+	b.lanes_per_wave = P.parse.lanes_per_wave; b.t_cold = P.parse.t_cold; b.prio_batches = P.parse.prio_batches;
+	b.head_batches[0] = P.parse.head_batches[0]; b.head_batches[1] = P.parse.head_batches[1];
+	b.head_lanes[0] = P.parse.head_lanes[0]; b.head_lanes[1] = P.parse.head_lanes[1];
+	b.head_first[1] = P.parse.head_first[1]; b.head_first[2] = P.parse.head_first[2];
+	jm_parse_body<SPLIT>(b);
+}
+__global__ __launch_bounds__(JM_PARSE_WG) void k_parse_planned(JmParseBufs b) { jm_parse_planned<false>(b); }
+__global__ __launch_bounds__(JM_PARSE_WG) void k_parse_split_planned(JmParseBufs b) { jm_parse_planned<true>(b); }
+
 extern "C" int jsmpeg_hip_debug_parse_plan(uint32_t n_slices, uint32_t long_slices, uint32_t bytes_per_mb_x16, int with_tickets, uint32_t out[12]);
 /* What a pass's launch is: everything jm_launch_parse decides, as host arithmetic without a HIP call (jm_launch_parse is this
  * + the fills + the launch; tests/test_parse_plan.py reads the rules through jsmpeg_hip_debug_parse_plan on a machine without
  * a GPU).  b.n_lanes != 0; `have_ticket`: the caller gave a ticket counter.  Returns the workgroups; *use_ticket: the
  * wavefronts draw further batches by ticket. */
 uint32_t jm_plan_parse(JmParseBufs &b, bool have_ticket, bool *use_ticket) {
-	/* slices per wavefront: 64, except for small batches (fewer than 512 full wavefronts: half the SIMDs would stand
-	 * idle while a few wavefronts walk 64 slices each) -- there the smallest power of two that still keeps the pass
-	 * within 4096 wavefronts, down to ONE slice per wavefront for a single picture (measured, MI355X: one 1080p
-	 * picture 1.31 -> 0.69 ms per decode(), one 720p stream of 360 pictures 1.48 -> 1.30 ms of parse; batches of 512+
-	 * wavefronts are fastest at 64) */
-	uint32_t lanes = 64;
-	if (b.n_lanes <= 512u * 64u) {
-		/* ... within 2048 wavefronts, two per SIMD: a wavefront walks faster the fewer others share its SIMD (late round 3,
-		 * profiles/r03_parse_head.txt: all-intra 1080p 16 x 24 pictures 2.15 -> 1.66 ms of parse at 16 instead of 8 slices per
-		 * wavefront, 4 x 24 1.55 -> 1.41 at 4 instead of 2, 320x240 4 x 300 0.58 -> 0.46 at 16 instead of 8) */
-		lanes = 1;
-		while (lanes < 64 && (uint64_t)lanes * (JM_PARSE_FILL_WAVES / 2) < b.n_lanes) lanes <<= 1;
-	}
-	if (b.debug_flags & 8) lanes = 64;
-	bool lanes_forced = false;
-	{ static const int forced = getenv("JSMPEG_HIP_PARSE_LANES") ? atoi(getenv("JSMPEG_HIP_PARSE_LANES")) : 0;   /* tuning only */
-	  if (forced >= 1 && forced <= 64) { lanes = (uint32_t)forced; lanes_forced = true; } }
-	b.lanes_per_wave = lanes;
-	/* The header step's queue threshold (slice_parse.h jm_run_cold).  The step is the longest of the turn; the denser the
-	 * content, the smaller the share of a lane's steps that are header steps and the less it pays to let them queue.
-	 * Measured on the box (profiles/r05_parse_notes.md; late round 5, the carried-window kernel): the 2160p configuration
-	 * (17 bytes per macroblock over its I and P pictures) 64 x 24 at 24 / 16 / 12 / 8: 5.20 / 5.08 / 5.11 / 5.26 ms, 16 x 24 at
-	 * 24 / 12: 4.15 / 4.08; 320x240 intra (21 bytes) at 16 / 12 / 8: 0.69 / 0.69 / 0.71; cfg2 and cfg1 (8 bytes per macroblock)
-	 * are fastest at 24 (cfg2: 2.97 / 2.83 / 2.85 / 2.99 at 12 / 24 / 32 / 40).  So: 14 from 12 bytes per macroblock up.
-	 * (until late in round 5 the cut was at 20 bytes, which the 2160p configuration as generated never reached) */
-	b.t_cold = JM_T_COLD;
-	if (b.bytes_per_mb_x16 >= JM_T_COLD_DENSE_X16) b.t_cold = JM_T_COLD_DENSE;
-	{ static const int forced = getenv("JSMPEG_HIP_T_COLD") ? atoi(getenv("JSMPEG_HIP_T_COLD")) : 0;   /* tuning only */
-	  if (forced >= 1 && forced <= 64) b.t_cold = (uint32_t)forced; }
-	b.cold_threshold = (int)((b.t_cold * lanes + 63) / 64);
-	/* The ring service in two halves (slice_parse.h jm_lane_request / jm_lane_land: a refill's memory latency behind a turn of
-	 * work) where the wavefronts with the longest slices walk alone for much of the pass -- dense content, by the same
-	 * figure: 2160p 64 x 24 5.66 -> 5.20 ms, 320x240 intra 64 x 300 0.755 -> 0.70, 2160p 16 x 24 and one 720p stream
-	 * unchanged; cfg2 (sparse, the issue port full to the end) measured 2-3 % slower with it (2.55 -> 2.62, four
-	 * alternating pairs: profiles/r05z_parse_split_service.txt) and keeps the one-piece service */
-	b.split_service = b.bytes_per_mb_x16 >= JM_T_COLD_DENSE_X16 ? 1u : 0u;
-	if (const char *e = getenv("JSMPEG_HIP_PARSE_SPLIT")) b.split_service = atoi(e) ? 1u : 0u;   /* tuning / tests (looked up per launch: tests switch it inside a process) */
-	/* Mid-size passes with a few LONG slices (16 x 24 pictures of 4K: the 8 % of the slices that belong to intra pictures
-	 * are three times the others): the pass lasts as long as the wavefront that holds the longest slices walks, and a
-	 * wavefront with one or two slices walks about twice as fast as one with 16+ (its turns run only the step kinds those
-	 * lanes need).  The slices come longest first, so: the first `long_slices` of them at a few per wavefront, the rest at
-	 * `lanes`. */
-	b.head_batches[0] = b.head_batches[1] = 0; b.head_lanes[0] = b.head_lanes[1] = 1;
-	b.head_first[0] = b.head_first[1] = b.head_first[2] = 0;
-	uint32_t H = b.long_slices, seg_a = 0;
-	bool forced = false;
-	if (const char *e = getenv("JSMPEG_HIP_PARSE_HEAD")) {   /* tests / tuning: "a,l0,h,l1" = the first a slices l0 per wavefront, up to slice h l1 per wavefront */
+	/* (the rules themselves: enqueue_plan.h jm_plan_parse_rules, which an enqueued pass's planner runs on the device) */
+	JmParseSizing z;
+	z.n_lanes = b.n_lanes; z.long_slices = b.long_slices; z.bytes_per_mb_x16 = b.bytes_per_mb_x16; z.debug_flags = b.debug_flags;
+	const uint32_t groups = jm_plan_parse_rules(z, jm_parse_overrides(), have_ticket, use_ticket);
+	b.lanes_per_wave = z.lanes_per_wave; b.cold_threshold = z.cold_threshold; b.t_cold = z.t_cold; b.split_service = z.split_service;
+	b.prio_batches = z.prio_batches; b.n_batches = z.n_batches;
+	for (int i = 0; i < 2; i++) { b.head_batches[i] = z.head_batches[i]; b.head_lanes[i] = z.head_lanes[i]; }
+	for (int i = 0; i < 3; i++) b.head_first[i] = z.head_first[i];
+	return groups;
+}
+
+/* What the rules take from the environment.  Slices per wavefront (1 .. 64): measured, MI355X -- one 1080p picture 1.31 -> 0.69
+ * ms per decode() at ONE slice per wavefront, one 720p stream of 360 pictures 1.48 -> 1.30 ms of parse; the header step's
+ * threshold (profiles/r05_parse_notes.md: 14 from 12 bytes per macroblock up, 24 below); the ring service in two halves for
+ * dense content (2160p 64 x 24 5.66 -> 5.20 ms; cfg2 2-3 % slower with it, profiles/r05z_parse_split_service.txt); the head of
+ * long slices at a few per wavefront (profiles/r03_parse_head.txt: 16 x 24 of 4K 6.36 -> 5.08 ms); the grid of passes without
+ * tickets (profiles/r05ae_parse_grids.txt).  LANES, T_COLD, PRIO, RESIDENT and EVEN are read once per process (tuning only);
+ * SPLIT and HEAD per launch (tests switch them inside a process). */
+JmParseOverrides jm_parse_overrides() {
+	JmParseOverrides o;
+	static const int lanes = getenv("JSMPEG_HIP_PARSE_LANES") ? atoi(getenv("JSMPEG_HIP_PARSE_LANES")) : 0;
+	static const int t_cold = getenv("JSMPEG_HIP_T_COLD") ? atoi(getenv("JSMPEG_HIP_T_COLD")) : 0;
+	static const int prio = getenv("JSMPEG_HIP_PARSE_PRIO") ? atoi(getenv("JSMPEG_HIP_PARSE_PRIO")) : -1;
+	static const uint32_t resident = getenv("JSMPEG_HIP_PARSE_RESIDENT") ? (uint32_t)atoi(getenv("JSMPEG_HIP_PARSE_RESIDENT")) : JM_PARSE_RESIDENT_WGS;
+	static const int even = getenv("JSMPEG_HIP_PARSE_EVEN") ? atoi(getenv("JSMPEG_HIP_PARSE_EVEN")) : 1;
+	o.lanes = lanes; o.t_cold = t_cold; o.prio = prio; o.resident = resident; o.even = even;
+	o.split = -1;
+	if (const char *e = getenv("JSMPEG_HIP_PARSE_SPLIT")) o.split = atoi(e) ? 1 : 0;
+	o.head_set = 0; o.head_a = 0; o.head_l0 = 1; o.head_h = 0; o.head_l1 = 1;
+	if (const char *e = getenv("JSMPEG_HIP_PARSE_HEAD")) {   /* "a,l0,h,l1" = the first a slices l0 per wavefront, up to slice h l1 per wavefront */
 		unsigned a = 0, l0 = 1, h = 0, l1 = 1;
 		if (sscanf(e, "%u,%u,%u,%u", &a, &l0, &h, &l1) == 4 && l0 >= 1 && l0 <= 64 && l1 >= 1 && l1 <= 64 && a <= h) {
-			H = std::min<uint32_t>(h, b.n_lanes); seg_a = std::min<uint32_t>(a, H); seg_a -= seg_a % l0;
-			b.head_lanes[0] = l0; b.head_lanes[1] = l1; forced = true;
+			o.head_set = 1; o.head_a = a; o.head_l0 = l0; o.head_h = h; o.head_l1 = l1;
 		}
 	}
-	if (!forced) {
-		/* measured (profiles/r03_parse_head.txt; 16 / 8 streams x 24 pictures of 4K, one 720p stream of 360 pictures): what
-		 * a wavefront's walk costs grows with its slices (1 .. ~16: more step kinds per turn) AND with the wavefronts that
-		 * share its SIMD.  So: as few long slices per wavefront as keeps the whole pass at two (then three) wavefronts per
-		 * SIMD, the short ones packed as tightly as that needs.  16 x 24 of 4K: 4 + 64 per wavefront, parse 6.36 -> 5.08 ms;
-		 * 8 x 24: 2 + 64, 5.77 -> 4.0; one 720p stream: 1 + 32, 0.97 -> 0.8 */
-		uint32_t lh = 0, lt = 0;
-		if (H > 0 && (uint64_t)H * 3 <= b.n_lanes && !(b.debug_flags & 8) && !lanes_forced) {
-			for (uint32_t w = JM_PARSE_FILL_WAVES / 2; w <= JM_PARSE_FILL_WAVES * 3 / 4 && !lh; w += JM_PARSE_FILL_WAVES / 4)
-				for (uint32_t l = 1; l <= 16 && !lh; l <<= 1) {
-					const uint32_t head_w = (H + l - 1) / l;
-					if (head_w > w * 3 / 4) continue;
-					for (uint32_t t = 16; t <= 64; t <<= 1)
-						if (t > l && (b.n_lanes - H + t - 1) / t <= w - head_w) { lh = l; lt = t; break; }
-				}
-		}
-		if (lh) {
-			seg_a = H - H % lh;
-			b.head_lanes[0] = b.head_lanes[1] = lh;
-			lanes = lt;
-			b.lanes_per_wave = lanes;
-			b.cold_threshold = (int)((b.t_cold * lanes + 63) / 64);
-		} else H = 0;
-	}
-	if (H) {
-		b.head_batches[0] = seg_a / b.head_lanes[0];
-		b.head_first[1] = seg_a;
-		b.head_batches[1] = (H - seg_a + b.head_lanes[1] - 1) / b.head_lanes[1];
-		b.head_first[2] = std::min<uint32_t>(seg_a + b.head_batches[1] * b.head_lanes[1], b.n_lanes);
-	}
-	b.n_batches = b.head_batches[0] + b.head_batches[1] + (b.n_lanes - b.head_first[2] + lanes - 1) / lanes;
-	b.prio_batches = 0;
-	{ static const int prio = getenv("JSMPEG_HIP_PARSE_PRIO") ? atoi(getenv("JSMPEG_HIP_PARSE_PRIO")) : -1;   /* tuning: < 0 the rule, else that many batches */
-	  if (prio >= 0) b.prio_batches = (uint32_t)prio;
-	  else if (b.long_slices) b.prio_batches = b.head_batches[0] + b.head_batches[1] ? b.head_batches[0] + b.head_batches[1] : (b.long_slices + lanes - 1) / lanes; }
-	/* as many workgroups as there are batches -- or, for large passes, as the GPU holds at a time (2 per CU: 80 KB of
-	 * LDS each), their wavefronts drawing further batches by ticket */
-	uint32_t groups = (b.n_batches + JM_PARSE_WAVES - 1) / JM_PARSE_WAVES;
-	static const uint32_t resident = getenv("JSMPEG_HIP_PARSE_RESIDENT") ? (uint32_t)atoi(getenv("JSMPEG_HIP_PARSE_RESIDENT"))
-	                                                                      : JM_PARSE_RESIDENT_WGS;   /* tests: the ticket path on small inputs */
-	*use_ticket = groups > resident && resident >= 1 && have_ticket;
-	if (*use_ticket) groups = resident;
-	else {
-		/* A pass without tickets of MORE than one workgroup per CU but fewer than two: the dispatcher gives every CU one
-		 * workgroup and some a second -- sixteen wavefronts there, eight elsewhere, and the pass lasts as long as the CUs with
-		 * sixteen.  Launched as TWO workgroups per CU (batch = slot x workgroups + workgroup: the wavefronts without a batch
-		 * leave at once) every CU holds the same 2 x n_batches / 512 wavefronts: 320x240 intra 40 x 300 0.49 -> 0.425 ms, 2160p
-		 * 48 x 24 4.55 -> 4.24, 64 x 24 (3240 batches: 405 workgroups -> 512 of 6.3 wavefronts) 5.02 -> 4.93, 720p 32 x 120 the
-		 * same.  And the smallest passes -- at most a batch per CU: one picture's 68 slices, a wavefront each -- take a
-		 * WORKGROUP per batch: the wavefront has its CU's LDS and issue ports to itself (a decode() of one 1080p picture 0.530 ->
-		 * 0.495 ms, 720p 0.355 -> 0.341).  Between the two (fewer than one workgroup per CU, several batches each) spreading
-		 * changes nothing (2160p 8 / 16 / 32 x 24, one 720p stream: +-0.5 %).  JSMPEG_HIP_PARSE_EVEN=0: the packed grid, =2:
-		 * everything spread (measurements, profiles/r05ae_parse_grids.txt) */
-		static const int even = getenv("JSMPEG_HIP_PARSE_EVEN") ? atoi(getenv("JSMPEG_HIP_PARSE_EVEN")) : 1;
-		if (even && groups > resident / 2 && groups < resident) groups = resident;
-		else if (even && b.n_batches <= resident / 2) groups = b.n_batches;
-		else if (even >= 2 && groups < resident / 2) groups = resident / 2;
-	}
-	return groups;
+	return o;
 }
 
 /* diagnostics / tests (no GPU needed): the launch a pass of `n_slices` slices would get -- out[0] kernel (0 k_parse, 1
@@ -868,6 +805,65 @@ hipError_t jm_launch_parse(const JmParseBufs &b_in, hipStream_t st) {
 	                   b.split_service ? "_split" : "", b.n_lanes, b.lanes_per_wave, b.n_batches, groups, b.ticket ? " + tickets" : "", b.t_cold, b.bytes_per_mb_x16); }
 	if (b.split_service) hipLaunchKernelGGL(k_parse_split, dim3(groups), dim3(JM_PARSE_WG), 0, st, b);
 	else hipLaunchKernelGGL(k_parse, dim3(groups), dim3(JM_PARSE_WG), 0, st, b);
+	return hipGetLastError();
+}
+
+hipError_t jm_launch_parse_planned(const JmParseBufs &b_in, hipStream_t st) {
+	if (!b_in.plan || !b_in.ticket) return hipErrorInvalidValue;
+	JmParseBufs b = b_in;
+	b.cu_order = nullptr;
+	hipError_t e = hipMemsetAsync(b.ticket, 0, sizeof(uint32_t), st);
+	if (e != hipSuccess) return e;
+	/* the grid of the large passes: as many workgroups as the GPU holds, their wavefronts drawing further batches by ticket
+	 * (a small pass leaves most of them with nothing: their first batch is past the last) */
+	const uint32_t resident = jm_parse_overrides().resident;
+	const uint32_t groups = resident >= 1 ? resident : JM_PARSE_RESIDENT_WGS;
+	hipLaunchKernelGGL(k_parse_planned, dim3(groups), dim3(JM_PARSE_WG), 0, st, b);
+	hipLaunchKernelGGL(k_parse_split_planned, dim3(groups), dim3(JM_PARSE_WG), 0, st, b);
+	return hipGetLastError();
+}
+
+/* ------------------------------------------------------------------------
+ * The device plan of an enqueued pass (enqueue_plan.h): one workgroup.
+ * ---------------------------------------------------------------------- */
+struct JmDevExec {
+	uint32_t nt;
+	template <class F> __device__ __forceinline__ void par(F f) { f((uint32_t)threadIdx.x, nt); __syncthreads(); }
+	__device__ __forceinline__ void add64(uint64_t *p, uint64_t v) { atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v); }
+};
+
+__global__ __launch_bounds__(JM_PLAN_THREADS) void k_plan(JmPlanArgs a, JmPlanDescBufs d) {
+	__shared__ JmPlanShared s;
+	JmDevExec x{ JM_PLAN_THREADS };
+	jm_plan_run(x, a, s);
+	if (threadIdx.x == 0) jm_plan_finish(a, s);
+	/* the descriptors of every slot of the launch (engine.hip fill_desc / enqueue_ordered), padding where no picture is */
+	const uint32_t n_slots = 8 * a.rows_cap;
+	for (uint32_t k = threadIdx.x; k < n_slots; k += JM_PLAN_THREADS) {
+		JmReconDesc D;
+		const uint32_t r = jm_plan_slot(a, s, k);
+		if (r == JM_NONE) {
+			D.tok = nullptr; D.mb = nullptr; D.dst = nullptr; D.fwd = nullptr; D.stale = nullptr; D.qm = nullptr;
+			D.done_pic = D.wait_fwd = D.wait_stale = D.pad_ = 0;
+		} else {
+			const uint32_t p = a.dec[r];
+			const JmPic pic = a.pics[p];
+			const int32_t stale = a.stale[p];
+			D.tok = d.tokens + pic.tok_off;
+			D.mb = d.mb + (size_t)pic.mb_index * (uint32_t)a.mb_size;
+			D.dst = d.pool + (uint64_t)p * d.frame_bytes;
+			D.fwd = pic.fwd >= 0 ? d.pool + (uint64_t)pic.fwd * d.frame_bytes : nullptr;
+			D.stale = stale >= 0 ? d.pool + (uint64_t)stale * d.frame_bytes : nullptr;
+			D.qm = reinterpret_cast<const uint8_t *>(a.streams + pic.stream) + offsetof(JmStream, intra_q);
+			jm_plan_slot_waits(a.pics, a.dec, a.stale, a.chain_id, s.kind, r, (int32_t)k == a.brk, D.done_pic, D.wait_fwd, D.wait_stale);
+			D.pad_ = 0;
+		}
+		d.desc[k] = D;
+	}
+}
+
+hipError_t jm_launch_plan(const JmPlanArgs &a, const JmPlanDescBufs &d, hipStream_t st) {
+	hipLaunchKernelGGL(k_plan, dim3(1), dim3(JM_PLAN_THREADS), 0, st, a, d);
 	return hipGetLastError();
 }
 

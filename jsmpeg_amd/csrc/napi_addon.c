@@ -30,6 +30,9 @@
  *   batchUploadTS(handle, [Uint8Array TS, ...], streamId = 0xE0)    jsmpeg_hip_batch_upload_ts (device demux, ts.js semantics)
  *   batchDecode(handle) -> pictures                                  jsmpeg_hip_batch_decode + _sync
  *   batchDecodeAsync(handle) -> Promise<pictures>                    the same on a thread of libuv's pool (two batches in flight)
+ *   batchEnqueue(handle) -> 0 | 1                                    jsmpeg_hip_batch_enqueue on the batch's own stream (no wait)
+ *   batchQuery(handle) -> 0 | 1                                      jsmpeg_hip_batch_query (never waits)
+ *   batchSync(handle) -> pictures                                    jsmpeg_hip_batch_sync + _picture_count
  *   batchSetReconstruct(handle, plan)                                jsmpeg_hip_batch_set_reconstruct (0 level by level, 1 the engine's choice)
  *   batchPictureInfo(handle, p) -> {stream, esOffset, type, decoded, level, forward}
  *   batchTsWrites(handle, stream) -> [{pts, offset, length}, ...]   jsmpeg_hip_batch_ts_writes
@@ -514,6 +517,44 @@ static napi_value fn_batch_decode_async(napi_env env, napi_callback_info info) {
 		return NULL;
 	}
 	return promise;
+}
+
+/* batchEnqueue(handle) -> 0 | 1: the pass as a pure enqueue on the batch's own stream (jsmpeg_hip_batch_enqueue: planned on the
+ * device, the calling thread never waits; 1: the batch is not planned on the device and the blocking decode ran).  With
+ * batchQuery polled from the event loop and batchSync once it says 1, a Node host keeps any number of batches in flight
+ * without a thread of libuv's pool (HIPBatch.prototype.enqueue). */
+static napi_value fn_batch_enqueue(napi_env env, napi_callback_info info) {
+	size_t argc = 1;
+	napi_value argv[1], out;
+	NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+	jsmpeg_hip_batch_t *b = batch_arg(env, argv[0]);
+	if (!b) return NULL;
+	void *st = jsmpeg_hip_batch_own_stream(b);
+	const int rc = st ? jsmpeg_hip_batch_enqueue(b, st) : -1;
+	if (rc < 0) { napi_throw_error(env, NULL, jsmpeg_hip_last_error()); return NULL; }
+	NAPI_OK(napi_create_int32(env, rc, &out));
+	return out;
+}
+static napi_value fn_batch_query(napi_env env, napi_callback_info info) {
+	size_t argc = 1;
+	napi_value argv[1], out;
+	NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+	jsmpeg_hip_batch_t *b = batch_arg(env, argv[0]);
+	if (!b) return NULL;
+	const int rc = jsmpeg_hip_batch_query(b);
+	if (rc < 0) { napi_throw_error(env, NULL, jsmpeg_hip_last_error()); return NULL; }
+	NAPI_OK(napi_create_int32(env, rc, &out));
+	return out;
+}
+static napi_value fn_batch_sync(napi_env env, napi_callback_info info) {
+	size_t argc = 1;
+	napi_value argv[1], out;
+	NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+	jsmpeg_hip_batch_t *b = batch_arg(env, argv[0]);
+	if (!b) return NULL;
+	if (jsmpeg_hip_batch_sync(b) < 0) { napi_throw_error(env, NULL, jsmpeg_hip_last_error()); return NULL; }
+	NAPI_OK(napi_create_uint32(env, jsmpeg_hip_batch_picture_count(b), &out));
+	return out;
 }
 
 /* batchSetReconstruct(handle, plan): 0 = level by level, 1 = the engine's choice (jsmpeg_hip_batch_set_reconstruct) */
@@ -1051,7 +1092,7 @@ static napi_value init(napi_env env, napi_value exports) {
 		{ "decode", fn_decode }, { "getPlanes", fn_get_planes }, { "renderRGBA", fn_render_rgba },
 		{ "deviceCount", fn_device_count }, { "lastError", fn_last_error }, { "liveDecoders", fn_live_decoders },
 		{ "batchCreate", fn_batch_create }, { "batchDestroy", fn_batch_destroy }, { "batchUpload", fn_batch_upload },
-		{ "batchUploadTS", fn_batch_upload_ts }, { "batchDecode", fn_batch_decode }, { "batchDecodeAsync", fn_batch_decode_async }, { "batchSetReconstruct", fn_batch_set_reconstruct }, { "batchPictureInfo", fn_batch_picture_info },
+		{ "batchUploadTS", fn_batch_upload_ts }, { "batchDecode", fn_batch_decode }, { "batchDecodeAsync", fn_batch_decode_async }, { "batchEnqueue", fn_batch_enqueue }, { "batchQuery", fn_batch_query }, { "batchSync", fn_batch_sync }, { "batchSetReconstruct", fn_batch_set_reconstruct }, { "batchPictureInfo", fn_batch_picture_info },
 		{ "batchTsWrites", fn_batch_ts_writes }, { "batchReadPlanes", fn_batch_read_planes }, { "batchReadFrames", fn_batch_read_frames }, { "batchReadRGBA", fn_batch_read_rgba },
 		{ "batchGeometry", fn_batch_geometry }, { "batchStreamInfo", fn_batch_stream_info }, { "batchTimings", fn_batch_timings }, { "batchFrameHashes", fn_batch_frame_hashes },
 		{ "mp2Create", fn_mp2_create }, { "mp2Destroy", fn_mp2_destroy }, { "mp2BufferWrite", fn_mp2_buffer_write },

@@ -144,8 +144,41 @@ function install(JSMpeg, options) {
       (n) => { this.decoding = false; this.pictures = n; return n; },
       (e) => { this.decoding = false; throw e; });
   };
+  // The same pass WITHOUT a thread: enqueued from this thread (jsmpeg_hip_batch_enqueue: planned on the device, nothing
+  // waits), then polled from the event loop (batchQuery: setImmediate for the first turns, 1 ms timers after) and settled once
+  // the device is through -- a Promise of the picture count, like decodeAsync(), but no thread of libuv's pool is taken: one
+  // event loop keeps any number of batches in flight (INTEGRATION.md section 5).  The same rule while it is pending: every
+  // other call on the batch throws.
+  HIPBatch.prototype.enqueue = function () {
+    if (this.decoding) return Promise.reject(new Error('JSMpeg.HIPBatch: a decode of this batch is in flight'));
+    try {
+      this.native.batchEnqueue(this.handle);
+    } catch (e) {
+      return Promise.reject(e);
+    }
+    this.decoding = true;
+    return new Promise((resolve, reject) => {
+      let turns = 0;
+      const poll = () => {
+        try {
+          if (!this.native.batchQuery(this.handle)) {
+            if (++turns < 64) setImmediate(poll); else setTimeout(poll, 1);
+            return;
+          }
+          const n = this.native.batchSync(this.handle);
+          this.decoding = false;
+          this.pictures = n;
+          resolve(n);
+        } catch (e) {
+          this.decoding = false;
+          reject(e);
+        }
+      };
+      poll();
+    });
+  };
   HIPBatch.prototype._idle = function (what) {
-    if (this.decoding) throw new Error('JSMpeg.HIPBatch.' + what + ': a decodeAsync() of this batch is in flight');
+    if (this.decoding) throw new Error('JSMpeg.HIPBatch.' + what + ': a decodeAsync() / enqueue() of this batch is in flight');
   };
   HIPBatch.prototype.pictureInfo = function (p) { return this.native.batchPictureInfo(this.handle, p); };
   HIPBatch.prototype.timings = function () { return this.native.batchTimings(this.handle); };

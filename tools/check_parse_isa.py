@@ -22,7 +22,8 @@ def kernel_isa(defs=()):
                                *defs, os.path.join(ROOT, "jsmpeg_amd", "csrc", "kernels.hip")], stderr=subprocess.DEVNULL)
         text = open(out).read()
     out = {}
-    for sym in ("_Z7k_parse11JmParseBufs", "_Z13k_parse_split11JmParseBufs"):
+    for sym in ("_Z7k_parse11JmParseBufs", "_Z13k_parse_split11JmParseBufs",
+                "_Z15k_parse_planned11JmParseBufs", "_Z21k_parse_split_planned11JmParseBufs"):
         m = re.search(r"^%s:.*?^\s*\.size\s+%s" % (sym, sym), text, re.S | re.M)
         assert m, sym + " not found in the assembly"
         out[sym] = m.group(0).splitlines()
