@@ -709,6 +709,50 @@ int jsmpeg_hip_mp2_live_stream_info(jsmpeg_hip_mp2_live_t *a, uint32_t stream, j
  * matrixing, [6] windowing + the tables' way back. */
 int jsmpeg_hip_mp2_live_timings(jsmpeg_hip_mp2_live_t *a, float out_ms[7]);
 
+/* ------------------------------------------------------------------ part 7
+ * Decoded pictures as resized RGB TENSORS on the device, for hosts that feed a model (one kernel, jsmpeg_amd/csrc/tensor_plan.h).
+ * Row k of the tensor, from the picture's planes (no full-size intermediate):
+ *   RGB       display pixel (x, y): Y[y * coded_width + x], chroma at [(y >> 1) * (coded_width >> 1) + (x >> 1)], the Canvas2D
+ *             integer BT.601 of jsmpeg_hip_batch_render_rgba.  Even widths: exactly read_rgba's RGB.  Odd widths: the same
+ *             formula WITHOUT the reference's running-index shear and 255 fill -- the tensor is the picture, not the canvas;
+ *   crop      (crop_x, crop_y, crop_width, crop_height), display pixels, inside the picture (0, 0, 0, 0: all of it); no filter
+ *             tap reaches outside it;
+ *   resize    to width x height: torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=antialias)
+ *             of the crop's float RGB (0 .. 255) -- torch's tap tables, horizontal pass, then vertical;
+ *   value     F16 / BF16 / F32: (v / 255 - mean[c]) / std[c], c in the tensor's channel order (round to nearest even);
+ *             U8: rint(v) clamped to 0 .. 255 (mean / std unused);
+ *   layout    NCHW: [count][3][height][width]; NHWC: [count][height][width][3]; contiguous; RGB or BGR.
+ * Anything else -- a crop outside the picture, a side of 0 or above 4096, an unknown enum value, std 0, a picture or stream
+ * index out of range, a batch picture that was not decoded (picture_info.decoded 0) -- is an error and nothing is launched.
+ * Stream order: hip_stream first waits (an event, no host wait) for the stream that last wrote the pool; after the kernel an
+ * event is recorded on hip_stream, and the next decode, enqueue or tick of the handle waits for it on its own stream before it
+ * writes the pool.  The calls return after the launch (the host waits only when it is four renders of the handle ahead of the
+ * device: the slot tables in flight).  count 0: returns 0, launches nothing.  f16 / bf16: the f32 value rounded, within one
+ * ulp of torch's value cast -- except where normalisation cancels to within 5e-5 of 0, where the narrow type's ulp is finer
+ * than the f32 rounding of the resize and the value is within that f32 tolerance instead. */
+enum { JSMPEG_HIP_TENSOR_U8 = 0, JSMPEG_HIP_TENSOR_F16 = 1, JSMPEG_HIP_TENSOR_BF16 = 2, JSMPEG_HIP_TENSOR_F32 = 3 };
+enum { JSMPEG_HIP_TENSOR_NCHW = 0, JSMPEG_HIP_TENSOR_NHWC = 1 };
+enum { JSMPEG_HIP_TENSOR_RGB = 0, JSMPEG_HIP_TENSOR_BGR = 1 };
+typedef struct jsmpeg_hip_tensor_desc_t {
+	uint32_t width, height;                   /* of each picture in the tensor, 1..4096 */
+	uint32_t crop_x, crop_y, crop_width, crop_height;   /* display pixels; crop_width = crop_height = 0: whole picture */
+	uint32_t dtype, layout, order, antialias;
+	float mean[3], std[3];                    /* float dtypes only, in the tensor's channel order */
+} jsmpeg_hip_tensor_desc_t;
+
+/* pictures[k] (host array; NULL = 0 .. count-1) of the last decode -> tensor row k in dev_out, enqueued on hip_stream.  Settles an
+ * enqueued pass first, as jsmpeg_hip_batch_render_rgba does. */
+int jsmpeg_hip_batch_render_tensor(jsmpeg_hip_batch_t *b, const uint32_t *pictures, uint32_t count,
+                                   const jsmpeg_hip_tensor_desc_t *desc, void *dev_out, void *hip_stream);
+/* the same over the last tick's pictures (jsmpeg_hip_live_picture's index) */
+int jsmpeg_hip_live_render_tensor(jsmpeg_hip_live_t *l, const uint32_t *pictures, uint32_t count,
+                                  const jsmpeg_hip_tensor_desc_t *desc, void *dev_out, void *hip_stream);
+/* the newest decoded frame of each listed stream, from whichever tick decoded it; a stream with none yet:
+ * its row is all-zero bytes and have[k] = 0 (have may be NULL) */
+int jsmpeg_hip_live_render_tensor_latest(jsmpeg_hip_live_t *l, const uint32_t *streams, uint32_t count,
+                                         const jsmpeg_hip_tensor_desc_t *desc, void *dev_out, void *hip_stream,
+                                         uint8_t *have);
+
 /* Last error of the calling thread ("" if none). */
 const char *jsmpeg_hip_last_error(void);
 /* Number of visible HIP devices (0 if none / runtime unusable). */

@@ -7,6 +7,7 @@ import os
 import numpy as np
 
 from . import build as _build
+from . import tensor as _tensor
 
 
 class BatchConfig(ctypes.Structure):
@@ -102,6 +103,7 @@ def lib():
         L.jsmpeg_hip_batch_counters.argtypes = [vp, ctypes.POINTER(u64)]
         L.jsmpeg_hip_last_error.restype = ctypes.c_char_p
         L.jsmpeg_hip_device_count.restype = ctypes.c_int
+        _tensor.bind(L)
         _lib = L
     return _lib
 
@@ -120,6 +122,7 @@ class Batch:
         self.h = self.L.jsmpeg_hip_batch_create(ctypes.byref(cfg))
         if not self.h:
             raise RuntimeError("jsmpeg_hip_batch_create: " + last_error())
+        self.device = device if device >= 0 else _tensor.current_device()     # where tensor() puts its output
         cw, ch, lu, chb, fs = (ctypes.c_int32(), ctypes.c_int32(), ctypes.c_uint32(), ctypes.c_uint32(),
                                ctypes.c_uint64())
         self._ok(self.L.jsmpeg_hip_batch_geometry(self.h, cw, ch, lu, chb, fs))
@@ -260,6 +263,21 @@ class Batch:
         """Renderer stage on the device: pictures [first, first + count) -> RGBA (width * height * 4 bytes each,
         display size) into the device buffer `dev_ptr`, enqueued on `stream`."""
         self._ok(self.L.jsmpeg_hip_batch_render_rgba(self.h, first, count, dev_ptr, stream))
+
+    def tensor(self, pictures=None, size=None, crop=None, dtype=None, layout="nchw", order="rgb", antialias=True, mean=None,
+               std=None, out=None):
+        """Pictures of the last decode as ONE resized RGB torch.Tensor on the batch's device (C ABI part 7): row k is picture
+        pictures[k] (None: all of them; repeats and any order allowed), resized from the crop (x, y, width, height) -- default
+        the whole picture -- to size (height, width) -- default the crop's -- as F.interpolate(mode="bilinear",
+        antialias=antialias) would; dtype torch.uint8 / float16 / bfloat16 / float32 (default), float ones normalised as
+        (v / 255 - mean) / std; layout "nchw" / "nhwc", order "rgb" / "bgr".  Produced on torch's current stream of that
+        device, after the decode's work and with no host wait; the next decode waits for it.  out: a contiguous tensor of
+        exactly that shape, dtype and device to write into (ValueError otherwise)."""
+        idx, count = _tensor.indices(pictures, self.picture_count if pictures is None else 0)
+        ptr = idx.ctypes.data if idx is not None else None
+        return _tensor.render(lambda d, o, st: self._ok(self.L.jsmpeg_hip_batch_render_tensor(self.h, ptr, count, d, o, st)),
+                              self.device, self.width, self.height, count, size, crop, dtype, layout, order, antialias, mean,
+                              std, out)
 
     def read_rgba(self, p):
         """Picture p as RGBA uint8[height, width, 4]: device conversion, then a copy to the host."""

@@ -71,6 +71,15 @@ void batch_free(jsmpeg_hip_batch_t *b) {
 	for (auto &e : b->ev) if (e) hipEventDestroy(e);
 	for (auto &e : b->ev_level) if (e) hipEventDestroy(e);
 	if (b->own_stream) hipStreamDestroy(b->own_stream);
+	for (auto &t : b->tstage) {
+		if (t.done) { hipEventSynchronize(t.done); hipEventDestroy(t.done); }
+		if (t.h) hipHostFree(t.h);
+		hipFree(t.d);
+	}
+	for (uint32_t *h : b->tretired_h) hipHostFree(h);
+	for (uint32_t *d : b->tretired_d) hipFree(d);
+	if (b->ev_pool) hipEventDestroy(b->ev_pool);
+	if (b->ev_tensor) hipEventDestroy(b->ev_tensor);
 	delete b;
 }
 
@@ -746,6 +755,7 @@ extern "C" int jsmpeg_hip_batch_decode(jsmpeg_hip_batch_t *b, void *hip_stream) 
 	HIP_TRY(hipSetDevice(b->device));
 	hipStream_t st = (hipStream_t)hip_stream;
 	b->stream = st;
+	if (batch_wait_tensor(b, st) < 0) return -1;
 	b->timed = false;
 	b->n_sc = b->n_pics = b->n_levels = b->n_decoded = b->n_slices = b->n_slice_codes = 0;
 	if (b->n_streams == 0) return 0;
@@ -798,6 +808,7 @@ extern "C" int jsmpeg_hip_batch_enqueue(jsmpeg_hip_batch_t *b, void *hip_stream)
 	HIP_TRY(hipSetDevice(b->device));
 	hipStream_t st = (hipStream_t)hip_stream;
 	b->stream = st;
+	if (batch_wait_tensor(b, st) < 0) return -1;
 	b->timed = false; b->enqueued = true;
 	b->n_sc = b->n_pics = b->n_levels = b->n_decoded = b->n_slices = b->n_slice_codes = 0;
 	b->n_level_ev = 0; b->ordered = false; b->stats_pending = false; b->last_group = 0; b->ordered_status = 0; b->ordered_waits = 0;
@@ -1110,6 +1121,66 @@ extern "C" int jsmpeg_hip_batch_render_rgba(jsmpeg_hip_batch_t *b, uint32_t firs
 	r.rgba = (uint8_t *)dev_rgba; r.rgba_stride = (uint64_t)b->cfg.width * b->cfg.height * 4;
 	HIP_TRY(jm_launch_rgba(r, (hipStream_t)hip_stream));
 	return 0;
+}
+
+/* ---- part 7: pictures as resized RGB tensors (tensor_plan.h, k_tensor) ---- */
+
+int batch_render_tensor(jsmpeg_hip_batch_t *b, const uint32_t *slots, uint32_t count, const jsmpeg_hip_tensor_desc_t *desc,
+                        void *dev_out, hipStream_t st) {
+	HIP_TRY(hipSetDevice(b->device));
+	if (!b->ev_pool) {
+		HIP_TRY(hipEventCreateWithFlags(&b->ev_pool, hipEventDisableTiming));
+		HIP_TRY(hipEventCreateWithFlags(&b->ev_tensor, hipEventDisableTiming));
+	}
+	/* the next stage in turn: free once the render that used it last has finished (a wait only JM_TENSOR_STAGES renders ahead) */
+	jsmpeg_hip_batch_t::TensorStage *s = &b->tstage[b->tstage_next];
+	b->tstage_next = (b->tstage_next + 1) % JM_TENSOR_STAGES;
+	if (!s->done) HIP_TRY(hipEventCreateWithFlags(&s->done, hipEventDisableTiming));
+	else if (hipEventQuery(s->done) != hipSuccess) HIP_TRY(hipEventSynchronize(s->done));
+	if (s->cap < count) {
+		uint64_t cap = 64;
+		while (cap < count || cap < b->cfg.max_pictures) cap *= 2;
+		if (s->h) { b->tretired_h.push_back(s->h); b->tretired_d.push_back(s->d); }
+		s->h = nullptr; s->d = nullptr; s->cap = 0;
+		HIP_TRY(hipHostMalloc(&s->h, sizeof(uint32_t) * cap, hipHostMallocDefault));
+		HIP_TRY(jm_malloc(&s->d, sizeof(uint32_t) * cap));
+		s->cap = (uint32_t)std::min<uint64_t>(cap, 0xffffffffu);
+	}
+	memcpy(s->h, slots, sizeof(uint32_t) * count);
+	/* in: the frames are written on the decode's stream; the renders since the last decode are one chain (ev_tensor covers all) */
+	HIP_TRY(hipEventRecord(b->ev_pool, b->stream));
+	HIP_TRY(hipStreamWaitEvent(st, b->ev_pool, 0));
+	if (b->tensor_pending) HIP_TRY(hipStreamWaitEvent(st, b->ev_tensor, 0));
+	HIP_TRY(hipMemcpyAsync(s->d, s->h, sizeof(uint32_t) * count, hipMemcpyHostToDevice, st));
+	JmTensorBufs tb;
+	tb.pool = b->d_pool; tb.frame_bytes = b->g.frame_bytes; tb.luma_bytes = b->g.luma_bytes; tb.chroma_bytes = b->g.chroma_bytes;
+	tb.coded_width = b->g.coded_width; tb.slots = s->d; tb.count = count; tb.out = dev_out;
+	HIP_TRY(jm_launch_tensor(tb, jm_tensor_plan(desc, (uint32_t)b->cfg.width, (uint32_t)b->cfg.height), st));
+	/* out: the next decode, enqueue or tick waits for this on its own stream */
+	HIP_TRY(hipEventRecord(s->done, st));
+	HIP_TRY(hipEventRecord(b->ev_tensor, st));
+	b->tensor_pending = true;
+	return 0;
+}
+
+extern "C" int jsmpeg_hip_batch_render_tensor(jsmpeg_hip_batch_t *b, const uint32_t *pictures, uint32_t count,
+                                              const jsmpeg_hip_tensor_desc_t *desc, void *dev_out, void *hip_stream) {
+	g_err[0] = 0;
+	if (!b) return fail("null batch");
+	if (count == 0) return 0;
+	if (!desc || !dev_out) return fail("null argument");
+	if (batch_settle_enqueued(b) < 0) return -1;
+	if (const char *m = jm_tensor_check(desc, (uint32_t)b->cfg.width, (uint32_t)b->cfg.height)) return fail("render_tensor: %s", m);
+	std::vector<uint32_t> slots(count);
+	for (uint32_t k = 0; k < count; k++) {
+		const uint32_t p = pictures ? pictures[k] : k;
+		if (p >= b->n_pics) return fail("render_tensor: picture %u outside the %u pictures of the last decode", p, b->n_pics);
+		if (!b->h_pics[p].decoded) return fail("render_tensor: picture %u was not decoded (picture_info.decoded 0)", p);
+		slots[k] = b->slot.empty() ? p : b->slot[p];
+	}
+	HIP_TRY(hipSetDevice(b->device));
+	if (batch_settle_pending(b) < 0) return -1;
+	return batch_render_tensor(b, slots.data(), count, desc, dev_out, (hipStream_t)hip_stream);
 }
 
 /* The same in the reference's WebGL renderer's arithmetic (src/webgl.js:259-281). */

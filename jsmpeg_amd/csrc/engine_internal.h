@@ -66,6 +66,7 @@ static inline void geom_init(JmGeom &g, int width, int height) { jm_geom_init(g,
 #ifndef JM_DECODE_AHEAD
 #define JM_DECODE_AHEAD 48u        /* ... at most, and no more than fit 160 MB of frames (1080p: 48, 2160p: 12): dec_sequence_header */
 #endif
+#define JM_TENSOR_STAGES 4u     /* slot tables of part-7 renders in flight at a time (jsmpeg_hip_batch_t::tstage) */
 #define POOL_GUARD 256 /* bytes before/after a frame pool: aligned 12-byte prediction loads may straddle */
 
 /* =========================================================================
@@ -157,7 +158,30 @@ struct jsmpeg_hip_batch_t {
 	bool enqueued;               /* the last pass was enqueued (timings: no host turn-around) */
 	bool enq_failed;             /* ... and settling it failed: sync reports enq_err once */
 	char enq_err[512];
+	/* TENSOR renders (part 7, batch_render_tensor): ev_pool is recorded on the decode's stream before a render and waited for on
+	 * the render's; ev_tensor is recorded on the render's stream after it, and the next decode, enqueue or tick waits for it
+	 * (tensor_pending) before it writes the pool.  A render's slot table goes to the device from pinned memory through one of
+	 * JM_TENSOR_STAGES stages taken in turn; a stage is used again once the render that used it last has finished (its event):
+	 * the host waits only when it is that many renders ahead of the device.  A stage that is too small for a call gets larger
+	 * buffers (a power of two, at least max_pictures); the outgrown ones are freed with the batch -- a free in between would
+	 * synchronise the device. */
+	hipEvent_t ev_pool, ev_tensor;
+	bool tensor_pending;
+	struct TensorStage { uint32_t *h, *d; uint32_t cap; hipEvent_t done; };
+	TensorStage tstage[JM_TENSOR_STAGES];
+	uint32_t tstage_next;
+	std::vector<uint32_t *> tretired_h, tretired_d;
 };
+/* part 7: rows of pool slots (JM_NONE: a row of zeros) -> a tensor on `st`; the descriptor has passed jm_tensor_check */
+int batch_render_tensor(jsmpeg_hip_batch_t *b, const uint32_t *slots, uint32_t count, const jsmpeg_hip_tensor_desc_t *desc,
+                        void *dev_out, hipStream_t st);
+/* ... and the wait of a stream that is about to write the pool for the renders since the last one */
+static inline int batch_wait_tensor(jsmpeg_hip_batch_t *b, hipStream_t st) {
+	if (!b->tensor_pending) return 0;
+	b->tensor_pending = false;
+	HIP_TRY(hipStreamWaitEvent(st, b->ev_tensor, 0));
+	return 0;
+}
 int live_assign_slots(struct jsmpeg_hip_live_t *l);    /* the live front end's turn inside a decode: once the picture table is on the host */
 static inline uint8_t *frame_of(const jsmpeg_hip_batch_t *b, uint32_t p) {
 	return b->d_pool + (uint64_t)(b->slot.empty() ? p : b->slot[p]) * b->g.frame_bytes;

@@ -6,6 +6,7 @@
 
 #include "enqueue_plan.h"
 #include "mpeg1_dev.h"
+#include "tensor_plan.h"
 #include "vlc_lut.h"
 
 /* the start-code scan takes the ES in pieces of 256 lanes x 64 bytes, 1 .. JM_SCAN_MAX_SUBS pieces per workgroup (chunk) */
@@ -196,6 +197,19 @@ struct JmRgbaBufs {
 hipError_t jm_launch_rgba(const JmRgbaBufs &b, hipStream_t st);
 /* the same frames in the reference's WebGL form (src/webgl.js:259-281: bilinear chroma, float BT.601 matrix) */
 hipError_t jm_launch_rgba_gl(const JmRgbaBufs &b, hipStream_t st);
+
+/* Part 7: pool frames -> one resized RGB tensor (tensor_plan.h), one launch for every row.  Row k reads pool slot slots[k];
+ * JM_NONE: a row of zero bytes.  The frames: 16-byte aligned, coded width a multiple of 16 (macroblocks). */
+struct JmTensorBufs {
+	const uint8_t *pool;
+	uint64_t frame_bytes;
+	uint32_t luma_bytes, chroma_bytes;
+	int32_t coded_width;
+	const uint32_t *slots;       /* device [count] */
+	uint32_t count;
+	void *out;                   /* [count] rows of 3 * out_w * out_h elements */
+};
+hipError_t jm_launch_tensor(const JmTensorBufs &b, const JmTensorPlan &p, hipStream_t st);
 
 /* ---- ingest side: MPEG-TS -> elementary streams (ts_kernels.hip; reference src/ts.js) ---- */
 struct JmTsRec {                 /* what one 188-byte packet says by itself, 16 bytes */

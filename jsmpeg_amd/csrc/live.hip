@@ -798,6 +798,46 @@ extern "C" int jsmpeg_hip_live_read_rgba(jsmpeg_hip_live_t *l, uint32_t i, void 
 	return 0;
 }
 
+/* Part 7 (engine.hip batch_render_tensor): the last tick's pictures, or the newest decoded frame of each listed stream. */
+extern "C" int jsmpeg_hip_live_render_tensor(jsmpeg_hip_live_t *l, const uint32_t *pictures, uint32_t count,
+                                             const jsmpeg_hip_tensor_desc_t *desc, void *dev_out, void *hip_stream) {
+	g_err[0] = 0;
+	if (!l) return fail("null live handle");
+	if (count == 0) return 0;
+	if (!desc || !dev_out) return fail("null argument");
+	if (live_settle(l) < 0) return -1;
+	if (const char *m = jm_tensor_check(desc, (uint32_t)l->cfg.width, (uint32_t)l->cfg.height)) return fail("render_tensor: %s", m);
+	std::vector<uint32_t> slots(count);
+	for (uint32_t k = 0; k < count; k++) {
+		const uint32_t i = pictures ? pictures[k] : k;
+		if (i >= l->out.size()) return fail("render_tensor: picture %u outside the %u pictures of the last tick", i, (unsigned)l->out.size());
+		slots[k] = l->out[i].slot;
+	}
+	return batch_render_tensor(l->b, slots.data(), count, desc, dev_out, (hipStream_t)hip_stream);
+}
+
+extern "C" int jsmpeg_hip_live_render_tensor_latest(jsmpeg_hip_live_t *l, const uint32_t *streams, uint32_t count,
+                                                    const jsmpeg_hip_tensor_desc_t *desc, void *dev_out, void *hip_stream,
+                                                    uint8_t *have) {
+	g_err[0] = 0;
+	if (!l) return fail("null live handle");
+	if (count == 0) return 0;
+	if (!streams || !desc || !dev_out) return fail("null argument");
+	if (live_settle(l) < 0) return -1;
+	if (const char *m = jm_tensor_check(desc, (uint32_t)l->cfg.width, (uint32_t)l->cfg.height)) return fail("render_tensor_latest: %s", m);
+	std::vector<uint32_t> slots(count);
+	for (uint32_t k = 0; k < count; k++) {
+		const uint32_t s = streams[k];
+		if (s >= l->streams.size() || !l->streams[s].open) return fail("render_tensor_latest: stream %u is not open", s);
+		const LiveStream &S = l->streams[s];
+		slots[k] = S.have ? s * l->ring + S.head : JM_NONE;      /* (the ring slot of the picture decoded last) */
+	}
+	if (batch_render_tensor(l->b, slots.data(), count, desc, dev_out, (hipStream_t)hip_stream) < 0) return -1;
+	if (have)
+		for (uint32_t k = 0; k < count; k++) have[k] = slots[k] != JM_NONE;
+	return 0;
+}
+
 extern "C" int jsmpeg_hip_live_frame_hashes(jsmpeg_hip_live_t *l, uint64_t *out) {
 	g_err[0] = 0;
 	if (!l || !out) return fail("null argument");

@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 
 from . import batch as _batch
+from . import tensor as _tensor
 
 FLUSH = 1
 
@@ -102,6 +103,7 @@ class Live:
         self.h = self.L.jsmpeg_hip_live_create(ctypes.byref(cfg))
         if not self.h:
             raise RuntimeError("jsmpeg_hip_live_create: " + _batch.last_error())
+        self.device = device if device >= 0 else _tensor.current_device()     # where tensor() / latest_tensor() put their output
         cw, ch, lu, chb = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_uint32(), ctypes.c_uint32()
         self._ok(self.L.jsmpeg_hip_live_geometry(self.h, cw, ch, lu, chb))
         self.coded_width, self.coded_height, self.luma_bytes, self.chroma_bytes = cw.value, ch.value, lu.value, chb.value
@@ -227,6 +229,29 @@ class Live:
         out = np.empty((self.height, self.width, 4), dtype=np.uint8)
         self._ok(self.L.jsmpeg_hip_live_read_rgba(self.h, i, out.ctypes.data))
         return out
+
+    def tensor(self, pictures=None, size=None, crop=None, dtype=None, layout="nchw", order="rgb", antialias=True, mean=None,
+               std=None, out=None):
+        """The last tick's pictures (pictures() indices; None: all) as ONE resized RGB torch.Tensor on the handle's device:
+        Batch.tensor's arguments and contract (C ABI part 7).  The next tick waits for it on the device."""
+        idx, count = _tensor.indices(pictures, self.picture_count if pictures is None else 0)
+        ptr = idx.ctypes.data if idx is not None else None
+        return _tensor.render(lambda d, o, st: self._ok(self.L.jsmpeg_hip_live_render_tensor(self.h, ptr, count, d, o, st)),
+                              self.device, self.width, self.height, count, size, crop, dtype, layout, order, antialias, mean,
+                              std, out)
+
+    def latest_tensor(self, streams, size=None, crop=None, dtype=None, layout="nchw", order="rgb", antialias=True, mean=None,
+                      std=None, out=None):
+        """The NEWEST decoded frame of each listed stream, from whichever tick decoded it, as one tensor (Batch.tensor's
+        arguments): returns (tensor, have) -- have[k] False: stream streams[k] has no frame yet and its row is all zeros."""
+        idx, count = _tensor.indices(streams, 0)
+        have = np.zeros(max(1, count), dtype=np.uint8)
+        ptr = idx.ctypes.data if count else None
+        t = _tensor.render(lambda d, o, st: self._ok(self.L.jsmpeg_hip_live_render_tensor_latest(self.h, ptr, count, d, o, st,
+                                                                                                have.ctypes.data)),
+                           self.device, self.width, self.height, count, size, crop, dtype, layout, order, antialias, mean, std,
+                           out)
+        return t, have[:count].astype(bool)
 
     def frame_hashes(self):
         n = self.picture_count
