@@ -308,6 +308,33 @@ int jsmpeg_hip_batch_seed_stream(jsmpeg_hip_batch_t *b, uint32_t stream, const v
 /* out[p] = 1 where picture p of the last decode was decoded and left macroblocks unwritten (they show the stream's
  * decoded picture before last); at most `cap` entries; waits for the decode.  Returns the entries written or < 0. */
 int jsmpeg_hip_batch_uncovered(jsmpeg_hip_batch_t *b, uint8_t *out, uint32_t cap);
+/* SELECTED FRAMES ONLY: a few frames per stream (one per second for an indexing job, one for a thumbnail, the frame at a
+ * time for a seek) without decoding the rest.  Request k asks for frame frame[k] of stream stream[k]; frames are counted
+ * as a user of the reference counts them: the n-th picture the whole decode would decode (picture_info.decoded == 1), in
+ * stream order, from 0.  Repeats and any order are allowed; count == 0 or NULL arrays clear the selection.  Like links
+ * and seeds, every upload* / attach_device clears it: set it after the upload; it then holds for every decode / enqueue of
+ * that upload.  The passes parse and reconstruct the selection's CLOSURE over forward references only -- the pictures from
+ * each selected picture's intra picture (or the stream's first decoded picture) up to it --, worked out on the device
+ * behind the index (enqueue stays a pure enqueue).  After such a pass
+ *   - a picture that was not needed reads decoded == 0 in picture_info, its frame in the pool is not written, and
+ *     render_tensor / render_rgba* refuse it as they refuse every picture that was not decoded;
+ *   - picture_count, the picture indices, es_offset, type and the pool slots are exactly the whole decode's;
+ *   - counters [2] and [4] count the needed pictures and their slices.
+ * Exact, never approximate: a needed picture that leaves macroblocks UNWRITTEN shows its stream's decoded picture before
+ * last there, which for a GOP's first two pictures lies in the GOP in front -- maybe outside the closure.  Once the parse's
+ * counts are in, a stream with such a picture has its selection WIDENED to every frame from its beginning up to its last
+ * needed one, and the pass is run once more before jsmpeg_hip_batch_sync (or any reader) returns -- the contract of
+ * recon_info's status 4; the widening stays for the following passes of that upload (select_info says so).
+ * Fails for a stream index >= the uploaded streams, for a live handle's batch, and -- with the uploads' message -- while
+ * an enqueued pass is unsettled.  A pass (decode / enqueue) of a batch that has both a selection and linked or seeded
+ * streams is refused. */
+int jsmpeg_hip_batch_select(jsmpeg_hip_batch_t *b, const uint32_t *stream, const uint32_t *frame, uint32_t count);
+/* picture[k] = the picture index of request k in the last pass, 0xffffffff where the stream has no such frame; at most
+ * `cap` entries; settles the pass first, like every reader.  Returns the entries written (0: no selection) or < 0. */
+int jsmpeg_hip_batch_selected(jsmpeg_hip_batch_t *b, uint32_t *picture, uint32_t cap);
+/* The last selected pass: [0] selected pictures (distinct), [1] needed pictures (the closure: what was parsed and
+ * reconstructed), [2] streams whose selection has been widened, [3] 1 if this pass was done over because of that. */
+int jsmpeg_hip_batch_select_info(jsmpeg_hip_batch_t *b, uint64_t out[4]);
 
 /* ------------------------------------------------------------------ part 3
  * MP2 audio (MPEG-1 Audio Layer II) -- the sibling decoder of the reference's

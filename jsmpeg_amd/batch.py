@@ -29,6 +29,7 @@ BATCH_SYMBOLS = ("jsmpeg_hip_batch_create", "jsmpeg_hip_batch_destroy", "jsmpeg_
                  "jsmpeg_hip_batch_timings", "jsmpeg_hip_batch_level_timings", "jsmpeg_hip_batch_counters", "jsmpeg_hip_batch_recon_info", "jsmpeg_hip_batch_link_streams", "jsmpeg_hip_batch_seed_stream", "jsmpeg_hip_batch_uncovered", "jsmpeg_hip_batch_render_rgba",
                  "jsmpeg_hip_batch_read_rgba", "jsmpeg_hip_batch_render_rgba_gl", "jsmpeg_hip_batch_read_rgba_gl", "jsmpeg_hip_batch_upload_ts", "jsmpeg_hip_batch_upload_ts_writes", "jsmpeg_hip_batch_ts_writes",
                  "jsmpeg_hip_batch_read_es", "jsmpeg_hip_batch_stream_info",
+                 "jsmpeg_hip_batch_select", "jsmpeg_hip_batch_selected", "jsmpeg_hip_batch_select_info",
                  "jsmpeg_hip_decoder_render_rgba", "jsmpeg_hip_last_error",
                  "jsmpeg_hip_device_count", "jsmpeg_hip_decoder_get_device_frame", "jsmpeg_hip_decoder_ahead_stats")
 
@@ -101,11 +102,34 @@ def lib():
         L.jsmpeg_hip_batch_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         L.jsmpeg_hip_batch_counters.restype = ctypes.c_int
         L.jsmpeg_hip_batch_counters.argtypes = [vp, ctypes.POINTER(u64)]
+        L.jsmpeg_hip_batch_select.restype = ctypes.c_int
+        L.jsmpeg_hip_batch_select.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), u32]
+        L.jsmpeg_hip_batch_selected.restype = ctypes.c_int
+        L.jsmpeg_hip_batch_selected.argtypes = [vp, ctypes.POINTER(u32), u32]
+        L.jsmpeg_hip_batch_select_info.restype = ctypes.c_int
+        L.jsmpeg_hip_batch_select_info.argtypes = [vp, ctypes.POINTER(u64)]
         L.jsmpeg_hip_last_error.restype = ctypes.c_char_p
         L.jsmpeg_hip_device_count.restype = ctypes.c_int
         _tensor.bind(L)
         _lib = L
     return _lib
+
+
+def select_arrays(requests):
+    """[(stream, frame)] -> two ctypes uint32 arrays and their length; ValueError for anything else (host code only)"""
+    try:
+        reqs = [tuple(r) for r in requests]
+    except TypeError:
+        raise ValueError("select: requests must be a list of (stream, frame) pairs")
+    for r in reqs:
+        if len(r) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in r):
+            raise ValueError("select: a request is a (stream, frame) pair of integers, got %r" % (r,))
+        if not (0 <= r[0] <= 0xffffffff and 0 <= r[1] <= 0xffffffff):
+            raise ValueError("select: stream and frame numbers are unsigned 32-bit, got %r" % (r,))
+    n = len(reqs)
+    streams = (ctypes.c_uint32 * max(1, n))(*[int(r[0]) for r in reqs])
+    frames = (ctypes.c_uint32 * max(1, n))(*[int(r[1]) for r in reqs])
+    return streams, frames, n
 
 
 def last_error():
@@ -331,6 +355,30 @@ class Batch:
         fn.restype = ctypes.c_int
         fn.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
         self._ok(fn(self.h, stream, frame_last, frame_before_last))
+
+    def select(self, requests):
+        """Decode selected frames only from now on: requests = [(stream, frame)], frame n = the n-th picture of the stream
+        the whole decode would decode, from 0 (repeats, any order); None clears.  After upload / attach -- which clear it --
+        and for every decode / enqueue of that upload: upload(...), select(reqs), enqueue(), tensor(pictures=selected())."""
+        if requests is None:
+            self._ok(self.L.jsmpeg_hip_batch_select(self.h, None, None, 0))
+            return
+        streams, frames, n = select_arrays(requests)
+        self._ok(self.L.jsmpeg_hip_batch_select(self.h, streams, frames, n))
+        self._n_requests = n
+
+    def selected(self):
+        """the picture index of every request in the last pass, None where the stream has no such frame"""
+        n = getattr(self, "_n_requests", 0)
+        out = (ctypes.c_uint32 * max(1, n))()
+        k = self._ok(self.L.jsmpeg_hip_batch_selected(self.h, out, n))
+        return [None if out[i] == 0xffffffff else int(out[i]) for i in range(k)]
+
+    def select_info(self):
+        """the last selected pass: selected (distinct) and needed pictures, streams widened, whether the pass was done over"""
+        c = (ctypes.c_uint64 * 4)()
+        self._ok(self.L.jsmpeg_hip_batch_select_info(self.h, c))
+        return dict(selected=int(c[0]), needed=int(c[1]), widened_streams=int(c[2]), redone=int(c[3]))
 
     def uncovered(self):
         """per picture of the last decode: decoded and left macroblocks unwritten"""

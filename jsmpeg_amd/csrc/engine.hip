@@ -28,6 +28,8 @@ extern "C" int jsmpeg_hip_device_count(void) {
 }
 
 /* uploads, decode and enqueue on a batch whose enqueued pass is not settled fail with this (include/jsmpeg_hip.h) */
+static const char *const k_select_and_links = "the batch has a selection (jsmpeg_hip_batch_select) and linked or seeded streams "
+                                               "(jsmpeg_hip_batch_link_streams / _seed_stream): a pass takes one or the other";
 static const char *const k_in_flight = "a pass of this batch is in flight (jsmpeg_hip_batch_enqueue): call jsmpeg_hip_batch_sync first";
 
 /* ------------------------------------------------------------ shared state */
@@ -58,7 +60,7 @@ void batch_free(jsmpeg_hip_batch_t *b) {
 	hipFree(b->d_es); hipFree(b->d_streams); hipFree(b->d_scan_state); hipFree(b->d_sc_pos);
 	hipFree(b->d_sc_code); hipFree(b->d_sc_owner); hipFree(b->d_pic_sc); hipFree(b->d_slice_sc); hipFree(b->d_slice_order); hipFree(b->d_order_hist); hipFree(b->d_counters);
 	hipFree(b->d_pics); hipFree(b->d_desc); hipFree(b->d_covered); hipFree(b->d_mb); hipFree(b->d_tokens);
-	hipFree(b->d_done); hipFree(b->d_rstatus); hipFree(b->d_plan); hipFree(b->d_plan_u32);
+	hipFree(b->d_done); hipFree(b->d_rstatus); hipFree(b->d_plan); hipFree(b->d_plan_u32); hipFree(b->d_sel); hipFree(b->d_before_last);
 	if (b->h_rstatus) hipHostFree(b->h_rstatus);
 	hipFree(b->d_pool_alloc); hipFree(b->d_hashes); hipFree(b->d_dbg); hipFree(b->d_rgba);
 	hipFree(b->d_ts); hipFree(b->d_ts_rec); hipFree(b->d_ts_es_off); hipFree(b->d_ts_cand); hipFree(b->d_ts_writes); hipFree(b->d_ts_begin); hipFree(b->d_ts_len); hipFree(b->d_ts_small);
@@ -178,6 +180,12 @@ extern "C" void jsmpeg_hip_batch_destroy(jsmpeg_hip_batch_t *b) {
 	if (b) { hipDeviceSynchronize(); batch_free(b); }
 }
 
+/* like links and seeds, a selection belongs to one upload */
+static void batch_select_clear(jsmpeg_hip_batch_t *b) {
+	b->sel_set = b->sel_pending = b->sel_redone = b->sel_have_map = false;
+	b->sel_stream.clear(); b->sel_frame.clear(); b->sel_widened.clear();
+}
+
 static int batch_layout(jsmpeg_hip_batch_t *b, uint32_t n_streams, const uint64_t *lens) {
 	if (n_streams > b->cfg.max_streams) return fail("%u streams > max_streams %u", n_streams, b->cfg.max_streams);
 	uint64_t total = 0;
@@ -199,7 +207,7 @@ static int batch_layout(jsmpeg_hip_batch_t *b, uint32_t n_streams, const uint64_
 	b->es_bytes = (uint32_t)off;
 	b->n_streams = n_streams;
 	b->es_view = b->d_es;
-	b->link_prev.clear(); b->seeded.clear(); b->seed_frames.clear(); b->slot.clear();
+	b->link_prev.clear(); b->seeded.clear(); b->seed_frames.clear(); b->slot.clear(); batch_select_clear(b);
 	return 0;
 }
 
@@ -480,7 +488,7 @@ extern "C" int jsmpeg_hip_batch_attach_device(jsmpeg_hip_batch_t *b, const void 
 	b->es_bytes = (uint32_t)total_bytes;
 	b->n_streams = n_streams;
 	b->es_view = (const uint8_t *)dev_es;
-	b->link_prev.clear(); b->seeded.clear(); b->seed_frames.clear(); b->slot.clear();
+	b->link_prev.clear(); b->seeded.clear(); b->seed_frames.clear(); b->slot.clear(); batch_select_clear(b);
 	/* (pageable source: the runtime has taken its copy when the call returns) */
 	if (n_streams) HIP_TRY(hipMemcpyAsync(b->d_streams, b->h_streams.data(), sizeof(JmStream) * n_streams, hipMemcpyHostToDevice, st));
 	return 0;
@@ -621,6 +629,16 @@ static int enqueue_index(jsmpeg_hip_batch_t *b, hipStream_t st) {
 	ib.counters_rw = b->d_counters; ib.n_streams = b->n_streams; ib.sc_cap = b->sc_cap; ib.pic_cap = b->cfg.max_pictures;
 	ib.width = b->cfg.width; ib.height = b->cfg.height;
 	HIP_TRY(jm_launch_index(ib, st));
+	if (b->sel_set) {
+		/* selected frames only: the pictures outside the selection's closure leave the table here, before anything reads it */
+		JmSelectBufs sl;
+		sl.pics = b->d_pics; sl.streams = b->d_streams; sl.sc_owner = b->d_sc_owner; sl.counters = b->d_counters;
+		const size_t total = b->sel_off[b->n_streams];
+		sl.layout.bits = b->d_sel; sl.layout.off = b->d_sel + total / 32; sl.layout.nbits = sl.layout.off + b->n_streams + 1;
+		sl.frame_pic = b->d_sel + total / 32 + 2 * (size_t)b->n_streams + 1;
+		sl.before_last = b->d_before_last; sl.n_streams = b->n_streams; sl.pic_cap = b->cfg.max_pictures;
+		HIP_TRY(jm_launch_select(sl, st));
+	}
 	HIP_TRY(hipEventRecord(b->ev[1], st));
 	/* written by a kernel into the pinned tables, not copied by a DMA engine: a DMA job waits for the engines' other jobs -- a
 	 * host that uploads the NEXT pass's streams meanwhile (0.5 GB over PCIe on its own stream) held this turn-around for
@@ -641,11 +659,12 @@ static int enqueue_index(jsmpeg_hip_batch_t *b, hipStream_t st) {
 /* The walk over the picture table (enqueue_plan.h jm_walk_picture: one source with the device planner): decoded pictures,
  * their slices, and what the parse's launch wants to know of them (ps: the estimate of long slices, bytes per macroblock). */
 static void batch_walk(jsmpeg_hip_batch_t *b, JmParseSizing &ps) {
-	JmWalkSums w = { 0, 0, 0, 0, 0, 0, 0 };
+	JmWalkSums w = { 0, 0, 0, 0, 0, 0, 0, 0 };
 	const uint32_t lanes = std::min(b->h_counters[4], b->sc_cap);
 	for (uint32_t p = 0; p < b->n_pics; p++) jm_walk_picture(b->h_pics, b->n_pics, p, b->h_streams.data(), b->n_streams, lanes, b->es_bytes, w);
 	b->n_decoded = (uint32_t)w.n_decoded; b->n_slices = (uint32_t)w.n_slices;
-	jm_parse_sizing_from_walk(w, lanes, b->es_bytes, b->g.mb_size, ps, &b->roots_x16);
+	if (b->sel_set) jm_parse_sizing_from_walk(w, jm_selected_lanes(w, lanes), jm_selected_bytes(w, b->es_bytes), b->g.mb_size, ps, &b->roots_x16);
+	else jm_parse_sizing_from_walk(w, lanes, b->es_bytes, b->g.mb_size, ps, &b->roots_x16);
 }
 
 /* The decode's one host wait: the index's counters and picture table, and ONE walk over the table for everything the parse's
@@ -655,7 +674,7 @@ static int collect_index(jsmpeg_hip_batch_t *b, hipStream_t st, JmParseSizing &p
 	tr.mark("index-done");
 	if (b->h_counters[2]) return fail("start-code / picture table overflow: %u start codes, %u pictures (max_pictures %u)",
 	                                  b->h_counters[0], b->h_counters[1], b->cfg.max_pictures);
-	b->n_sc = b->h_counters[0]; b->n_pics = b->h_counters[1]; b->n_levels = b->h_counters[3];
+	b->n_sc = b->h_counters[0]; b->n_pics = b->h_counters[1]; b->n_levels = b->h_counters[b->sel_set ? 5 : 3];
 	b->n_slice_codes = std::min(b->h_counters[4], b->sc_cap);
 	/* (the picture table came over with the counters: one copy of the whole table, one turn-around -- but for a pass over
 	 * live streams that saw more picture start codes than such a pass usually does) */
@@ -688,7 +707,7 @@ static int enqueue_parse(jsmpeg_hip_batch_t *b, hipStream_t st, const JmParseSiz
 	pb.ticket = b->d_order_hist + 2 * JM_ORDER_BINS;
 	pb.cu_order = b->d_order_hist + 2 * JM_ORDER_BINS + 16;
 	pb.slice_sc = b->d_slice_order;             /* (ordered by step 2, beside the host's turn-around) */
-	pb.n_lanes = std::min(b->h_counters[4], b->sc_cap);   /* a lane per slice code (not per start code) */
+	pb.n_lanes = b->sel_set ? ps.n_lanes : std::min(b->h_counters[4], b->sc_cap);   /* a lane per slice code (not per start code); selected frames: per owned one, they come first */
 	/* + 1/8 on the estimate of long slices: it is by picture, the order by slice.  The compressed bytes per macroblock of the
 	 * decoded pictures set the parse's header-step threshold -- unless the pass has pictures whose slices are several times the
 	 * mean (coded video: an intra picture is 10-30 x a predicted one): the pass then lasts as long as THEIR slices' walk, and the
@@ -750,7 +769,10 @@ extern "C" int jsmpeg_hip_batch_decode(jsmpeg_hip_batch_t *b, void *hip_stream) 
 	g_err[0] = 0;
 	if (!b) return fail("null batch");
 	if (b->enq_pending) return fail("decode: %s", k_in_flight);
+	if (b->sel_set && (!b->link_prev.empty() || !b->seeded.empty())) return fail("decode: %s", k_select_and_links);
 	b->enqueued = false; b->enq_failed = false;
+	b->sel_pending = b->sel_set; b->sel_have_map = false;
+	if (!b->sel_in_redo) b->sel_redone = false;
 	HostTrace tr(b->trace);
 	HIP_TRY(hipSetDevice(b->device));
 	hipStream_t st = (hipStream_t)hip_stream;
@@ -799,6 +821,7 @@ extern "C" int jsmpeg_hip_batch_enqueue(jsmpeg_hip_batch_t *b, void *hip_stream)
 	g_err[0] = 0;
 	if (!b) return fail("null batch");
 	if (b->enq_pending) return fail("enqueue: %s", k_in_flight);
+	if (b->sel_set && (!b->link_prev.empty() || !b->seeded.empty())) return fail("enqueue: %s", k_select_and_links);
 	b->enq_failed = false;
 	/* what the device does not plan: live handles, linked / seeded streams, batches set to go level by level -- the blocking decode */
 	if (b->live || !b->link_prev.empty() || !b->seeded.empty() || b->recon.levels || b->recon.demoted || b->recon.order == 0) {
@@ -810,6 +833,7 @@ extern "C" int jsmpeg_hip_batch_enqueue(jsmpeg_hip_batch_t *b, void *hip_stream)
 	b->stream = st;
 	if (batch_wait_tensor(b, st) < 0) return -1;
 	b->timed = false; b->enqueued = true;
+	b->sel_pending = b->sel_set; b->sel_have_map = false; b->sel_redone = false;
 	b->n_sc = b->n_pics = b->n_levels = b->n_decoded = b->n_slices = b->n_slice_codes = 0;
 	b->n_level_ev = 0; b->ordered = false; b->stats_pending = false; b->last_group = 0; b->ordered_status = 0; b->ordered_waits = 0;
 	b->chain_heads.clear();
@@ -830,6 +854,7 @@ extern "C" int jsmpeg_hip_batch_enqueue(jsmpeg_hip_batch_t *b, void *hip_stream)
 	a.try_streams = !b->recon.chains; a.try_chains = own || b->recon.chains;
 	a.streams_forced = !own; a.chains_forced = b->recon.chains;
 	a.brk = b->recon.brk;
+	a.selected = b->sel_set ? 1u : 0u;
 	a.rows_cap = b->rows_cap;
 	uint32_t *u = b->d_plan_u32;
 	a.dec = u; a.chain_id = u + mp; a.stale = (int32_t *)(u + 2 * (size_t)mp); a.cstart = u + 3 * (size_t)mp; a.cend = u + 4 * (size_t)mp;
@@ -895,7 +920,7 @@ static int settle_enqueued_pass(jsmpeg_hip_batch_t *b) {
 		HIP_TRY(hipMemcpy(&b->h_plan, b->d_plan, sizeof(JmDevPlan), hipMemcpyDeviceToHost));
 		if (b->h_counters[2]) { rc = fail("start-code / picture table overflow: %u start codes, %u pictures (max_pictures %u)",
 		                                  b->h_counters[0], b->h_counters[1], b->cfg.max_pictures); break; }
-		b->n_sc = b->h_counters[0]; b->n_pics = b->h_counters[1]; b->n_levels = b->h_counters[3];
+		b->n_sc = b->h_counters[0]; b->n_pics = b->h_counters[1]; b->n_levels = b->h_counters[b->sel_set ? 5 : 3];
 		b->n_slice_codes = std::min(b->h_counters[4], b->sc_cap);
 		JmParseSizing ps;
 		batch_walk(b, ps);
@@ -931,14 +956,16 @@ static int settle_enqueued_pass(jsmpeg_hip_batch_t *b) {
 	} while (0);
 	return rc;
 }
+static int batch_settle_selected(jsmpeg_hip_batch_t *b);
 static int batch_settle_enqueued(jsmpeg_hip_batch_t *b) {
-	if (!b->enq_pending) return 0;
+	if (!b->enq_pending) return b->sel_pending ? batch_settle_selected(b) : 0;
 	b->enq_pending = false;
-	const int rc = settle_enqueued_pass(b);      /* (every failure in there -- HIP_TRY's included -- lands here) */
+	int rc = settle_enqueued_pass(b);      /* (every failure in there -- HIP_TRY's included -- lands here) */
+	if (rc >= 0 && b->sel_pending && batch_settle_selected(b) < 0) rc = -1;
 	if (rc < 0) {
 		b->enq_failed = true;
 		snprintf(b->enq_err, sizeof b->enq_err, "%s", g_err);
-		b->n_pics = 0;
+		b->n_pics = 0; b->sel_pending = false;
 	}
 	return rc;
 }
@@ -998,6 +1025,125 @@ static int batch_settle_pending(jsmpeg_hip_batch_t *b) {
 	return batch_settle(b);
 }
 
+/* ---- selected frames only (select_plan.h) ---- */
+
+/* the requests' layout on the device: bits | off | nbits | frame_pic (the stream that may still read the old one has drained) */
+static int batch_select_upload(jsmpeg_hip_batch_t *b) {
+	const uint32_t n = b->n_streams;
+	const size_t total = b->sel_off[n], words = total / 32 + 2 * (size_t)n + 1 + total;
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream));
+	if (words > b->sel_cap_words) {
+		hipFree(b->d_sel); b->d_sel = nullptr; b->sel_cap_words = 0;
+		HIP_TRY(jm_malloc(&b->d_sel, sizeof(uint32_t) * words));
+		b->sel_cap_words = words;
+	}
+	if (!b->d_before_last) HIP_TRY(jm_malloc(&b->d_before_last, sizeof(int32_t) * std::max(1u, b->cfg.max_pictures)));
+	if (total) HIP_TRY(hipMemcpy(b->d_sel, b->sel_bits.data(), sizeof(uint32_t) * (total / 32), hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(b->d_sel + total / 32, b->sel_off.data(), sizeof(uint32_t) * (n + 1), hipMemcpyHostToDevice));
+	if (n) HIP_TRY(hipMemcpy(b->d_sel + total / 32 + n + 1, b->sel_nbits.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+	return 0;
+}
+
+extern "C" int jsmpeg_hip_batch_select(jsmpeg_hip_batch_t *b, const uint32_t *stream, const uint32_t *frame, uint32_t count) {
+	g_err[0] = 0;
+	if (!b) return fail("null batch");
+	if (b->live) return fail("select: a live handle's batch decodes what arrives, it takes no selection");
+	if (b->enq_pending) return fail("select: %s", k_in_flight);
+	if (!count || !stream || !frame) { batch_select_clear(b); return 0; }
+	for (uint32_t k = 0; k < count; k++)
+		if (stream[k] >= b->n_streams) return fail("select: request %u names stream %u of %u uploaded streams", k, stream[k], b->n_streams);
+	batch_select_clear(b);
+	b->sel_stream.assign(stream, stream + count); b->sel_frame.assign(frame, frame + count);
+	/* a bitmap over frame numbers per stream; frame n needs n + 1 pictures, so one at or beyond max_pictures exists in no pass */
+	const uint32_t n = b->n_streams;
+	b->sel_nbits.assign(n, 0); b->sel_off.assign(n + 1, 0); b->sel_widened.assign(n, 0);
+	for (uint32_t k = 0; k < count; k++)
+		if (frame[k] < b->cfg.max_pictures) b->sel_nbits[stream[k]] = std::max(b->sel_nbits[stream[k]], frame[k] + 1);
+	for (uint32_t s = 0; s < n; s++) b->sel_off[s + 1] = b->sel_off[s] + ((b->sel_nbits[s] + 31u) & ~31u);
+	b->sel_bits.assign(b->sel_off[n] / 32, 0);
+	for (uint32_t k = 0; k < count; k++)
+		if (frame[k] < b->cfg.max_pictures) { const uint32_t i = b->sel_off[stream[k]] + frame[k]; b->sel_bits[i >> 5] |= 1u << (i & 31); }
+	if (batch_select_upload(b) < 0) return -1;
+	b->sel_set = true;
+	return 0;
+}
+
+/* What is left of a SELECTED pass once its stream has drained and batch_settle has had its turn: the parse's counts tell which
+ * pictures left macroblocks unwritten, and the pass is exact unless one of them showed another frame there than the whole decode
+ * does (select_plan.h jm_select_widen).  Such a stream's selection becomes a prefix from its beginning and the pass is run once
+ * more, here -- the contract of the flagged ordered launch and of the GOP chains' status 4: final when sync returns. */
+static int batch_settle_selected(jsmpeg_hip_batch_t *b) {
+	if (!b->sel_pending) return 0;
+	b->sel_pending = false;
+	HIP_TRY(hipSetDevice(b->device));
+	HIP_TRY(hipStreamSynchronize(b->stream));
+	if (batch_settle(b) < 0) return -1;
+	if (b->n_pics) {
+		HIP_TRY(hipEventSynchronize(b->ev_cov));
+		std::vector<int32_t> before_last(b->n_pics), stale;
+		HIP_TRY(hipMemcpy(before_last.data(), b->d_before_last, sizeof(int32_t) * b->n_pics, hipMemcpyDeviceToHost));
+		batch_plan_stale(b, stale);
+		std::vector<uint32_t> widen(b->n_streams);
+		if (jm_select_widen(b->h_pics, b->n_pics, b->n_streams, stale.data(), before_last.data(), b->h_covered, (uint32_t)b->g.mb_size, widen.data())) {
+			if (b->sel_in_redo) return fail("internal: a selection widened to a prefix of its streams still is not the whole decode's");
+			for (uint32_t s = 0; s < b->n_streams; s++) {
+				if (!widen[s]) continue;
+				if (widen[s] > b->sel_nbits[s]) return fail("internal: stream %u's needed pictures outrun its selection", s);
+				b->sel_widened[s] = 1;
+				for (uint32_t f = 0; f < widen[s]; f++) { const uint32_t i = b->sel_off[s] + f; b->sel_bits[i >> 5] |= 1u << (i & 31); }
+			}
+			if (batch_select_upload(b) < 0) return -1;
+			b->sel_in_redo = true;
+			int rc = jsmpeg_hip_batch_decode(b, b->stream);
+			if (rc >= 0) rc = hipStreamSynchronize(b->stream) == hipSuccess ? 0 : fail("hipStreamSynchronize failed behind a widened selection's pass");
+			if (rc >= 0) rc = batch_settle(b);
+			if (rc >= 0) rc = batch_settle_selected(b);
+			b->sel_in_redo = false;
+			b->sel_redone = true;
+			return rc < 0 ? -1 : 0;
+		}
+	}
+	const size_t total = b->sel_off[b->n_streams];
+	b->sel_frame_pic.assign(total, JM_NONE);
+	if (total && b->n_pics) HIP_TRY(hipMemcpy(b->sel_frame_pic.data(), b->d_sel + total / 32 + 2 * (size_t)b->n_streams + 1, sizeof(uint32_t) * total, hipMemcpyDeviceToHost));
+	b->sel_have_map = true;
+	return 0;
+}
+
+/* the picture of request k in the last pass; JM_NONE: the stream has no such frame */
+static uint32_t batch_selected_picture(const jsmpeg_hip_batch_t *b, size_t k) {
+	const uint32_t s = b->sel_stream[k], f = b->sel_frame[k];
+	return f < b->sel_nbits[s] ? b->sel_frame_pic[b->sel_off[s] + f] : JM_NONE;
+}
+
+extern "C" int jsmpeg_hip_batch_selected(jsmpeg_hip_batch_t *b, uint32_t *picture, uint32_t cap) {
+	g_err[0] = 0;
+	if (!b || (cap && !picture)) return fail("null argument");
+	if (batch_settle_enqueued(b) < 0) return -1;
+	if (!b->sel_set) return 0;
+	if (!b->sel_have_map) return fail("selected: no pass has run since the selection was set");
+	const uint32_t n = (uint32_t)std::min<size_t>(cap, b->sel_stream.size());
+	for (uint32_t k = 0; k < n; k++) picture[k] = batch_selected_picture(b, k);
+	return (int)n;
+}
+
+extern "C" int jsmpeg_hip_batch_select_info(jsmpeg_hip_batch_t *b, uint64_t out[4]) {
+	g_err[0] = 0;
+	if (!b || !out) return fail("null argument");
+	if (batch_settle_enqueued(b) < 0) return -1;
+	out[0] = out[1] = out[2] = out[3] = 0;
+	if (!b->sel_set || !b->sel_have_map) return 0;
+	std::vector<uint32_t> pics;
+	for (size_t k = 0; k < b->sel_stream.size(); k++) { const uint32_t p = batch_selected_picture(b, k); if (p != JM_NONE) pics.push_back(p); }
+	std::sort(pics.begin(), pics.end());
+	out[0] = (uint64_t)(std::unique(pics.begin(), pics.end()) - pics.begin());
+	out[1] = b->n_decoded;
+	for (uint8_t w : b->sel_widened) out[2] += w;
+	out[3] = b->sel_redone ? 1 : 0;
+	return 0;
+}
+
 extern "C" int jsmpeg_hip_batch_sync(jsmpeg_hip_batch_t *b) {
 	g_err[0] = 0;
 	if (!b) return fail("null batch");
@@ -1009,7 +1155,8 @@ extern "C" int jsmpeg_hip_batch_sync(jsmpeg_hip_batch_t *b) {
 	}
 	HIP_TRY(hipSetDevice(b->device));
 	HIP_TRY(hipStreamSynchronize(b->stream));
-	return batch_settle(b);
+	if (batch_settle(b) < 0) return -1;
+	return batch_settle_selected(b);
 }
 
 extern "C" uint32_t jsmpeg_hip_batch_picture_count(jsmpeg_hip_batch_t *b) {

@@ -165,6 +165,15 @@ struct jsmpeg_hip_batch_t {
 	 * the host waits only when it is that many renders ahead of the device.  A stage that is too small for a call gets larger
 	 * buffers (a power of two, at least max_pictures); the outgrown ones are freed with the batch -- a free in between would
 	 * synchronise the device. */
+	/* SELECTED frames (jsmpeg_hip_batch_select; select_plan.h): the requests as given, their layout on the host and -- bits | off |
+	 * nbits | frame_pic in ONE allocation -- on the device, where k_select reads it behind the index of every pass until the next
+	 * upload / attach clears it.  sel_pending: a selected pass's check of its unwritten macroblocks is outstanding (batch_settle_selected:
+	 * every reader and sync; a stream that fails it is widened -- sel_widened, sel_bits -- and the pass run once more, sel_redone) */
+	std::vector<uint32_t> sel_stream, sel_frame, sel_off, sel_nbits, sel_bits, sel_frame_pic;
+	std::vector<uint8_t> sel_widened;
+	uint32_t *d_sel; size_t sel_cap_words;
+	int32_t *d_before_last;      /* [max_pictures] the whole decode's decoded picture before last of every picture (k_select) */
+	bool sel_set, sel_pending, sel_redone, sel_in_redo, sel_have_map;
 	hipEvent_t ev_pool, ev_tensor;
 	bool tensor_pending;
 	struct TensorStage { uint32_t *h, *d; uint32_t cap; hipEvent_t done; };

@@ -129,7 +129,8 @@ JM_HD uint32_t jm_plan_parse_rules(JmParseSizing &b, const JmParseOverrides &o, 
 /* The walk over the picture table (engine.hip collect_index): decoded pictures and their slices, how many slices are much
  * longer than the mean, the bytes of the pictures whose slices are several times it (coded video's intra pictures) and of
  * the pictures without a forward reference.  `lanes`: the pass's slice codes. */
-struct JmWalkSums { uint64_t n_decoded, n_slices, long_slices, crit_bytes, crit_pics, root_bytes, roots; };
+struct JmWalkSums { uint64_t n_decoded, n_slices, long_slices, crit_bytes, crit_pics, root_bytes, roots,
+                    bytes; };       /* bytes: of the decoded pictures -- what a pass over SELECTED frames (select_plan.h) parses, where es_bytes is all there is */
 JM_HD void jm_walk_picture(const JmPic *pics, uint32_t n_pics, uint32_t p, const JmStream *streams, uint32_t n_streams,
                            uint64_t lanes, uint32_t es_bytes, JmWalkSums &s) {
 	const JmPic &pic = pics[p];
@@ -138,11 +139,17 @@ JM_HD void jm_walk_picture(const JmPic *pics, uint32_t n_pics, uint32_t p, const
 	if (pic.stream >= n_streams) return;
 	const uint32_t end = p + 1 < n_pics && pics[p + 1].stream == pic.stream ? pics[p + 1].pos : streams[pic.stream].es_end;
 	const uint64_t bytes = end > pic.pos ? end - pic.pos : 0;
+	s.bytes += bytes;
 	if (pic.fwd < 0) { s.root_bytes += bytes; s.roots++; }
 	if (!pic.n_slices) return;
 	if (bytes * 2 * lanes >= (uint64_t)3 * es_bytes * pic.n_slices) s.long_slices += pic.n_slices;   /* >= 1.5 x the mean slice */
 	if (bytes * lanes >= (uint64_t)4 * es_bytes * pic.n_slices) { s.crit_bytes += bytes; s.crit_pics++; }   /* >= 4 x: coded video's intra pictures */
 }
+
+/* A pass over selected frames: the slice order puts the slice codes nobody owns last, so the parse takes the owned ones only,
+ * and the bytes per macroblock are those of the pictures it parses (jm_parse_sizing_from_walk's n_lanes and es_bytes) */
+JM_HD uint32_t jm_selected_lanes(const JmWalkSums &w, uint32_t lanes) { return (uint32_t)jm_umin64(w.n_slices, lanes); }
+JM_HD uint32_t jm_selected_bytes(const JmWalkSums &w, uint32_t es_bytes) { return (uint32_t)jm_umin64(w.bytes, es_bytes); }
 
 /* ... and what the parse's launch takes from it (engine.hip enqueue_parse): the estimate of long slices (+ 1/8: the estimate
  * is by picture, the order by slice), the compressed bytes per macroblock x 16 -- the critical pictures' when there are any --
@@ -192,6 +199,7 @@ struct JmPlanArgs {
 	uint32_t tiles_per_picture, group;
 	uint32_t try_streams, try_chains, streams_forced, chains_forced;   /* jm_choose_recon: the kinds it tries; forced = no distance rule */
 	int32_t brk;                 /* JSMPEG_HIP_RECON_BREAK */
+	uint32_t selected;           /* the pass has a selection (k_select ran): the parse is sized by the needed pictures */
 	/* scratch, device memory: dec, chain_id, cstart, cend [pic_cap]; ustart, uend [n_streams]; seq [8 rows_cap] */
 	uint32_t *dec, *chain_id, *ustart, *uend, *cstart, *cend, *seq;
 	int32_t *stale;              /* out [pic_cap]: recon_plan.h jm_plan_stale */
@@ -336,13 +344,13 @@ JM_HD void jm_plan_run(X &x, const JmPlanArgs &a, JmPlanShared &s) {
 		s.overflow = a.counters[2] != 0;
 		s.n_pics = s.overflow ? 0u : jm_umin(a.counters[1], a.pic_cap);
 		s.n_lanes = s.overflow ? 0u : jm_umin(a.counters[4], a.sc_cap);
-		s.sums = JmWalkSums{ 0, 0, 0, 0, 0, 0, 0 };
+		s.sums = JmWalkSums{ 0, 0, 0, 0, 0, 0, 0, 0 };
 		s.kind = JM_PLAN_HOST; s.rows = 0; s.lockstep = 0; s.n_chains = 0; s.n_dec = 0;
 		for (uint32_t c = 0; c < 8; c++) s.load[c] = 0;
 	});
 	/* the walk; what the pass's launches start from: covered counts, done words, status words, `stale` */
 	x.par([&](uint32_t t, uint32_t nt) {
-		JmWalkSums w = { 0, 0, 0, 0, 0, 0, 0 };
+		JmWalkSums w = { 0, 0, 0, 0, 0, 0, 0, 0 };
 		for (uint32_t p = t; p < s.n_pics; p += nt) {
 			jm_walk_picture(a.pics, s.n_pics, p, a.streams, a.n_streams, s.n_lanes, a.es_bytes, w);
 			a.covered[p] = 0; a.done[(size_t)JM_DONE_STRIDE * p] = 0; a.stale[p] = JM_STALE_NONE;
@@ -352,7 +360,7 @@ JM_HD void jm_plan_run(X &x, const JmPlanArgs &a, JmPlanShared &s) {
 		if (w.n_decoded) {
 			x.add64(&s.sums.n_decoded, w.n_decoded); x.add64(&s.sums.n_slices, w.n_slices); x.add64(&s.sums.long_slices, w.long_slices);
 			x.add64(&s.sums.crit_bytes, w.crit_bytes); x.add64(&s.sums.crit_pics, w.crit_pics); x.add64(&s.sums.root_bytes, w.root_bytes);
-			x.add64(&s.sums.roots, w.roots);
+			x.add64(&s.sums.roots, w.roots); x.add64(&s.sums.bytes, w.bytes);
 		}
 	});
 	/* the parse's sizing (one lane); the decoded pictures of the streams, compacted in table order (each thread a run of the table) */
@@ -361,9 +369,10 @@ JM_HD void jm_plan_run(X &x, const JmPlanArgs &a, JmPlanShared &s) {
 			JmDevPlan &P = *a.plan;
 			P.n_sc = s.overflow ? 0u : a.counters[0];
 			P.overflow = s.overflow; P.n_pics = s.n_pics;
-			jm_parse_sizing_from_walk(s.sums, s.n_lanes, a.es_bytes, a.mb_size, P.parse, nullptr);
+			if (a.selected) jm_parse_sizing_from_walk(s.sums, jm_selected_lanes(s.sums, s.n_lanes), jm_selected_bytes(s.sums, a.es_bytes), a.mb_size, P.parse, nullptr);
+			else jm_parse_sizing_from_walk(s.sums, s.n_lanes, a.es_bytes, a.mb_size, P.parse, nullptr);
 			P.parse.debug_flags = a.debug_flags;
-			if (s.n_lanes) { bool tk = false; jm_plan_parse_rules(P.parse, a.ov, true, &tk); }
+			if (P.parse.n_lanes) { bool tk = false; jm_plan_parse_rules(P.parse, a.ov, true, &tk); }
 			else { P.parse.n_batches = 0; P.parse.lanes_per_wave = 64; P.parse.split_service = 0; P.parse.prio_batches = 0; }
 		}
 		const uint32_t chunk = (s.n_pics + nt - 1) / nt;

@@ -6,6 +6,7 @@
 
 #include "enqueue_plan.h"
 #include "mpeg1_dev.h"
+#include "select_plan.h"
 #include "tensor_plan.h"
 #include "vlc_lut.h"
 
@@ -60,6 +61,20 @@ struct JmIndexBufs {
 	int width, height;
 };
 hipError_t jm_launch_index(const JmIndexBufs &b, hipStream_t st);
+
+/* A pass over selected frames only (select_plan.h): behind jm_launch_index, before anything reads the picture table.  One
+ * workgroup per stream; nothing is launched for a batch without a selection. */
+struct JmSelectBufs {
+	JmPic *pics;                 /* the table as k_index wrote it: thinned in place */
+	const JmStream *streams;
+	uint32_t *sc_owner;          /* the slice codes of dropped pictures go back to JM_NONE */
+	uint32_t *counters;          /* [2] read; [5] deepest needed level + 1, [6] needed pictures, [7] their slices (zeroed with the rest) */
+	JmSelectLayout layout;       /* the requests, device memory */
+	uint32_t *frame_pic;         /* out [layout.off[n_streams]] */
+	int32_t *before_last;        /* out [pic_cap] */
+	uint32_t n_streams, pic_cap;
+};
+hipError_t jm_launch_select(const JmSelectBufs &b, hipStream_t st);
 
 /* The order in which the slice parse takes the slices: longest first (by bytes up to the next start code), so that
  * the 64 slices of a wavefront and the 8 wavefronts of a workgroup have about the same way to go. */

@@ -422,6 +422,98 @@ hipError_t jm_launch_index(const JmIndexBufs &b, hipStream_t st) {
 }
 
 /* ------------------------------------------------------------------------
+ * A pass over selected frames only (select_plan.h): right behind k_index, one
+ * workgroup per stream, only when a selection is set.  Forward over the stream's
+ * pictures, 256 at a time: the frame numbers (the decoded pictures' count, as
+ * k_index scans it), the selected pictures, the whole decode's decoded picture
+ * before last of each.  Then backwards: the closure over forward references as
+ * two min-scans (the first selected picture at or behind p, the first anchor
+ * behind p) with a carry from chunk to chunk -- and every decoded picture outside
+ * it leaves the pass: everything downstream keys off JmPic::decoded and the
+ * slice codes' owners.
+ * ---------------------------------------------------------------------- */
+__global__ __launch_bounds__(JM_WG) void k_select(JmSelectBufs b) {
+	__shared__ int scan[JM_WG];
+	__shared__ int byrank[JM_WG];
+	__shared__ int carry[5];          /* decoded pictures so far | the last decoded picture | the one before | -(the first selected picture behind) | -(the first anchor behind) */
+	const uint32_t s = blockIdx.x;
+	if (b.counters[2]) return;       /* the tables overflowed: the host fails the pass */
+	const uint32_t lo = b.streams[s].pic_lo, hi = min(b.streams[s].pic_hi, b.pic_cap);
+	const JmSelectLayout l = b.layout;
+	const uint32_t nbits = l.nbits[s], off = l.off[s];
+	for (uint32_t f = threadIdx.x; f < nbits; f += JM_WG) b.frame_pic[off + f] = JM_NONE;
+	if (threadIdx.x == 0) { carry[0] = 0; carry[1] = -1; carry[2] = -1; carry[3] = INT_MIN; carry[4] = INT_MIN; }
+	__syncthreads();
+	for (uint32_t base = lo; base < hi; base += JM_WG) {
+		const uint32_t p = base + threadIdx.x;
+		const bool in = p < hi;
+		const bool dec = in && b.pics[p].decoded;
+		const int c0 = carry[0], last1 = carry[1], last2 = carry[2];
+		__syncthreads();
+		const int incl = jm_wg_scan_add(scan, dec ? 1 : 0);
+		const int n = scan[JM_WG - 1];
+		if (dec) byrank[incl - 1] = (int)p;
+		__syncthreads();
+		if (in) {
+			b.before_last[p] = dec ? jm_select_before_last(byrank, (uint32_t)(incl - 1), last1, last2) : -1;
+			if (dec) {
+				const uint32_t frame = (uint32_t)(c0 + incl - 1);
+				if (frame < nbits) b.frame_pic[off + frame] = p;
+				if (jm_select_bit(l, s, frame)) b.pics[p].pad_ = JM_PIC_SEL_SELECTED;
+			}
+		}
+		__syncthreads();
+		if (threadIdx.x == 0) { jm_select_carry_last(byrank, (uint32_t)n, carry[1], carry[2]); carry[0] = c0 + n; }
+		__syncthreads();
+	}
+	int needed = 0, slices = 0, levels = 0;
+	for (uint32_t c = (hi - lo + JM_WG - 1) / JM_WG; c-- > 0;) {
+		const uint32_t p = lo + c * JM_WG + (JM_WG - 1 - threadIdx.x);      /* the chunk's last picture in lane 0 */
+		const bool in = p < hi;
+		JmPic pic;
+		pic.decoded = 0; pic.pad_ = 0; pic.level = 0;
+		if (in) pic = b.pics[p];
+		const bool dec = in && pic.decoded;
+		const int cs = carry[3], ca = carry[4];
+		__syncthreads();
+		const int ns = max(cs, jm_wg_scan_max(scan, dec && (pic.pad_ & JM_PIC_SEL_SELECTED) ? -(int)p : INT_MIN));
+		__syncthreads();
+		const int na_incl = max(ca, jm_wg_scan_max(scan, dec && jm_select_anchor(pic) ? -(int)p : INT_MIN));
+		__syncthreads();
+		scan[threadIdx.x] = na_incl;
+		__syncthreads();
+		const int na = threadIdx.x ? scan[threadIdx.x - 1] : ca;        /* strictly behind p: one lane down */
+		if (dec) {
+			if (jm_select_needed(true, ns == INT_MIN ? JM_NONE : (uint32_t)-ns, na == INT_MIN ? JM_NONE : (uint32_t)-na)) {
+				needed++; slices += (int)pic.n_slices; levels = max(levels, pic.level + 1);
+			} else {
+				jm_select_drop(pic, b.sc_owner);
+				b.pics[p] = pic;
+			}
+		}
+		if (threadIdx.x == JM_WG - 1) { carry[3] = ns; carry[4] = na_incl; }
+		__syncthreads();
+	}
+	/* what the pass is left with: [5] the needed pictures' deepest level + 1, [6] the needed pictures, [7] their slices
+	 * ([3] stays the whole decode's depth; the parse and the plans size themselves from the picture table) */
+	needed = jm_wg_scan_add(scan, needed);
+	__syncthreads();
+	slices = jm_wg_scan_add(scan, slices);
+	__syncthreads();
+	levels = jm_wg_scan_max(scan, levels);
+	if (threadIdx.x == JM_WG - 1 && needed) {
+		atomicMax(&b.counters[5], (uint32_t)levels);
+		atomicAdd(&b.counters[6], (uint32_t)needed);
+		atomicAdd(&b.counters[7], (uint32_t)slices);
+	}
+}
+
+hipError_t jm_launch_select(const JmSelectBufs &b, hipStream_t st) {
+	if (b.n_streams) hipLaunchKernelGGL(k_select, dim3(b.n_streams), dim3(JM_WG), 0, st, b);
+	return hipGetLastError();
+}
+
+/* ------------------------------------------------------------------------
  * Slice order: a counting sort of the slices by length, longest first.  The
  * slice parse is one lane per slice and a lane's way is as long as its slice:
  * in stream order every 12th picture of cfg2 is an intra picture whose slices

@@ -570,6 +570,56 @@ static napi_value fn_batch_set_reconstruct(napi_env env, napi_callback_info info
 	return NULL;
 }
 
+/* batchSelect(handle, Uint32Array streams, Uint32Array frames): jsmpeg_hip_batch_select -- the following passes of this upload
+ * decode these frames (and what they need) only; batchSelect(handle) / (handle, null): clears */
+static napi_value fn_batch_select(napi_env env, napi_callback_info info) {
+	size_t argc = 3;
+	napi_value argv[3];
+	NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+	jsmpeg_hip_batch_t *b = argc ? batch_arg(env, argv[0]) : NULL;
+	if (!b) return NULL;
+	void *st = NULL, *fr = NULL; size_t n_st = 0, n_fr = 0; napi_typedarray_type t_st, t_fr; napi_value ab; size_t off;
+	napi_valuetype vt = napi_undefined;
+	if (argc > 1) NAPI_OK(napi_typeof(env, argv[1], &vt));
+	if (vt != napi_undefined && vt != napi_null) {
+		if (argc < 3 || napi_get_typedarray_info(env, argv[1], &t_st, &n_st, &st, &ab, &off) != napi_ok || t_st != napi_uint32_array ||
+		    napi_get_typedarray_info(env, argv[2], &t_fr, &n_fr, &fr, &ab, &off) != napi_ok || t_fr != napi_uint32_array || n_st != n_fr || n_st > 0xffffffffu) {
+			napi_throw_type_error(env, NULL, "jsmpeg_hip: batchSelect(handle, Uint32Array streams, Uint32Array frames) of one length"); return NULL;
+		}
+	}
+	if (jsmpeg_hip_batch_select(b, (const uint32_t *)st, (const uint32_t *)fr, (uint32_t)n_st) < 0) { napi_throw_error(env, NULL, jsmpeg_hip_last_error()); return NULL; }
+	return NULL;
+}
+/* batchSelected(handle, Uint32Array out) -> entries written: the picture of every request in the last pass, 0xffffffff = no such frame */
+static napi_value fn_batch_selected(napi_env env, napi_callback_info info) {
+	size_t argc = 2;
+	napi_value argv[2], out;
+	NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+	jsmpeg_hip_batch_t *b = argc ? batch_arg(env, argv[0]) : NULL;
+	if (!b) return NULL;
+	void *data = NULL; size_t len = 0; napi_typedarray_type t; napi_value ab; size_t off;
+	if (argc < 2 || napi_get_typedarray_info(env, argv[1], &t, &len, &data, &ab, &off) != napi_ok || t != napi_uint32_array || len > 0xffffffffu) {
+		napi_throw_type_error(env, NULL, "jsmpeg_hip: batchSelected(handle, Uint32Array)"); return NULL;
+	}
+	const int n = jsmpeg_hip_batch_selected(b, (uint32_t *)data, (uint32_t)len);
+	if (n < 0) { napi_throw_error(env, NULL, jsmpeg_hip_last_error()); return NULL; }
+	NAPI_OK(napi_create_int32(env, n, &out));
+	return out;
+}
+static napi_value fn_batch_select_info(napi_env env, napi_callback_info info) {
+	size_t argc = 1;
+	napi_value argv[1], out;
+	NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+	jsmpeg_hip_batch_t *b = argc ? batch_arg(env, argv[0]) : NULL;
+	if (!b) return NULL;
+	uint64_t v[4];
+	if (jsmpeg_hip_batch_select_info(b, v) < 0) { napi_throw_error(env, NULL, jsmpeg_hip_last_error()); return NULL; }
+	NAPI_OK(napi_create_object(env, &out));
+	if (!set_u32(env, out, "selected", (double)v[0]) || !set_u32(env, out, "needed", (double)v[1]) || !set_u32(env, out, "widenedStreams", (double)v[2]) ||
+	    !set_u32(env, out, "redone", (double)v[3])) { napi_throw_error(env, NULL, "jsmpeg_hip: cannot build the selection info"); return NULL; }
+	return out;
+}
+
 static napi_value fn_batch_picture_info(napi_env env, napi_callback_info info) {
 	size_t argc = 2;
 	napi_value argv[2], out;
@@ -1092,7 +1142,7 @@ static napi_value init(napi_env env, napi_value exports) {
 		{ "decode", fn_decode }, { "getPlanes", fn_get_planes }, { "renderRGBA", fn_render_rgba },
 		{ "deviceCount", fn_device_count }, { "lastError", fn_last_error }, { "liveDecoders", fn_live_decoders },
 		{ "batchCreate", fn_batch_create }, { "batchDestroy", fn_batch_destroy }, { "batchUpload", fn_batch_upload },
-		{ "batchUploadTS", fn_batch_upload_ts }, { "batchDecode", fn_batch_decode }, { "batchDecodeAsync", fn_batch_decode_async }, { "batchEnqueue", fn_batch_enqueue }, { "batchQuery", fn_batch_query }, { "batchSync", fn_batch_sync }, { "batchSetReconstruct", fn_batch_set_reconstruct }, { "batchPictureInfo", fn_batch_picture_info },
+		{ "batchUploadTS", fn_batch_upload_ts }, { "batchDecode", fn_batch_decode }, { "batchDecodeAsync", fn_batch_decode_async }, { "batchEnqueue", fn_batch_enqueue }, { "batchQuery", fn_batch_query }, { "batchSync", fn_batch_sync }, { "batchSetReconstruct", fn_batch_set_reconstruct }, { "batchSelect", fn_batch_select }, { "batchSelected", fn_batch_selected }, { "batchSelectInfo", fn_batch_select_info }, { "batchPictureInfo", fn_batch_picture_info },
 		{ "batchTsWrites", fn_batch_ts_writes }, { "batchReadPlanes", fn_batch_read_planes }, { "batchReadFrames", fn_batch_read_frames }, { "batchReadRGBA", fn_batch_read_rgba },
 		{ "batchGeometry", fn_batch_geometry }, { "batchStreamInfo", fn_batch_stream_info }, { "batchTimings", fn_batch_timings }, { "batchFrameHashes", fn_batch_frame_hashes },
 		{ "mp2Create", fn_mp2_create }, { "mp2Destroy", fn_mp2_destroy }, { "mp2BufferWrite", fn_mp2_buffer_write },

@@ -116,6 +116,7 @@ function install(JSMpeg, options) {
   HIPBatch.prototype.uploadTS = function (buffers, streamId) {
     this._idle('uploadTS');
     this.native.batchUploadTS(this.handle, buffers, streamId || 0xE0);
+    this.requests = null;
     this.writes = buffers.map((_, s) => this.native.batchTsWrites(this.handle, s));
     return this;
   };
@@ -123,6 +124,7 @@ function install(JSMpeg, options) {
   HIPBatch.prototype.upload = function (buffers) {
     this._idle('upload');
     this.native.batchUpload(this.handle, buffers);
+    this.requests = null;
     this.writes = null;
     return this;
   };
@@ -177,6 +179,41 @@ function install(JSMpeg, options) {
       poll();
     });
   };
+  // SELECTED FRAMES ONLY (jsmpeg_hip_batch_select): requests = [[stream, frame] | {stream, frame}], frame n = the n-th picture of
+  // the stream the whole decode would decode, from 0 -- a few frames per stream (one per second for an index, one for a
+  // thumbnail) without decoding the rest: the following decode() / decodeAsync() / enqueue() of THIS upload parse and
+  // reconstruct only what those frames need (worked out on the device).  null clears; so does every upload.  After the pass
+  // selected() gives the picture of every request (null: the stream has no such frame), forEachFrame hands out the selected
+  // pictures only (index = the frame number asked for), and selectInfo() says what it cost.
+  HIPBatch.prototype.select = function (requests) {
+    this._idle('select');
+    if (requests === null || requests === undefined) { this.native.batchSelect(this.handle, null); this.requests = null; return this; }
+    if (!Array.isArray(requests)) throw new TypeError('HIPBatch.select: an array of [stream, frame] requests, or null');
+    const streams = new Uint32Array(requests.length), frames = new Uint32Array(requests.length);
+    requests.forEach((r, k) => {
+      const s = Array.isArray(r) ? r[0] : r && r.stream, f = Array.isArray(r) ? r[1] : r && r.frame;
+      if (!Number.isInteger(s) || !Number.isInteger(f) || s < 0 || f < 0 || s > 0xffffffff || f > 0xffffffff || (Array.isArray(r) && r.length !== 2))
+        throw new TypeError('HIPBatch.select: request ' + k + ' is not a [stream, frame] pair of unsigned integers');
+      streams[k] = s; frames[k] = f;
+    });
+    if (!requests.length) { this.native.batchSelect(this.handle, null); this.requests = null; return this; }
+    this.native.batchSelect(this.handle, streams, frames);
+    this.requests = { streams, frames };
+    return this;
+  };
+  HIPBatch.prototype.selected = function () {
+    this._idle('selected');
+    if (!this.requests) return [];
+    const out = new Uint32Array(this.requests.streams.length);
+    const n = this.native.batchSelected(this.handle, out);
+    return Array.from(out.subarray(0, n), (p) => (p === 0xffffffff ? null : p));
+  };
+  // { selected, needed, widenedStreams, redone }: distinct selected pictures, pictures parsed and reconstructed, streams whose
+  // selection had to be widened to a prefix (a chain's first pictures left macroblocks unwritten), whether the pass was done over
+  HIPBatch.prototype.selectInfo = function () {
+    this._idle('selectInfo');
+    return this.native.batchSelectInfo(this.handle);
+  };
   HIPBatch.prototype._idle = function (what) {
     if (this.decoding) throw new Error('JSMpeg.HIPBatch.' + what + ': a decodeAsync() / enqueue() of this batch is in flight');
   };
@@ -219,7 +256,13 @@ function install(JSMpeg, options) {
     this._idle('forEachFrame');
     if (typeof opts === 'function') { cb = opts; opts = {}; }
     const perStream = new Map();
+    const frameOf = this.requests ? new Map() : null;      // a selected pass: the selected pictures only, at the frame numbers asked for
+    if (frameOf) {
+      const sel = this.selected();
+      sel.forEach((p, k) => { if (p !== null) frameOf.set(p, this.requests.frames[k]); });
+    }
     for (let p = 0; p < this.pictures; p++) {
+      if (frameOf && !frameOf.has(p)) continue;
       const info = this.pictureInfo(p);
       if (!info.decoded) continue;
       if (!perStream.has(info.stream)) perStream.set(info.stream, []);
@@ -241,14 +284,15 @@ function install(JSMpeg, options) {
       // without time stamps (elementary streams) the clock is the decoder's own: 1 / frameRate of the stream's sequence header
       // per picture (reference src/mpeg1.js:57, decoder.js:73-104) -- the rate the index kernel read, not an assumed one
       const rate = this.writes && this.writes[stream] ? 0 : this.native.batchStreamInfo(this.handle, stream).frameRate;
-      list.forEach((p, index) => {
+      list.forEach((p, place) => {
+        const index = frameOf ? frameOf.get(p) : place;
         const w = this.writes && this.writes[stream] && this.writes[stream][index];
         const frame = { stream, index, picture: p, pts: w ? w.pts : index / (rate || 30), width: this.width, height: this.height,
                         codedWidth: this.codedWidth, codedHeight: this.codedHeight };
         if (rgba) frame.rgba = this.readRGBA(p, rgba);
         else {
           if (p < have.first || p >= have.first + have.count) {            // the next chunk: from this picture to the stream's last, at most `chunk`
-            have = { first: p, count: Math.min(chunk, list[list.length - 1] - p + 1) };
+            have = { first: p, count: frameOf ? 1 : Math.min(chunk, list[list.length - 1] - p + 1) };
             this.native.batchReadFrames(this.handle, have.first, have.count, this.out, bytes);
           }
           const at = (p - have.first) * bytes;
@@ -266,6 +310,7 @@ function install(JSMpeg, options) {
   HIPBatch.prototype.decodeTS = function (buffers, opts) {
     opts = opts || {};
     this.uploadTS(buffers, opts.streamId);
+    if (opts.select) this.select(opts.select);
     this.decode();
     if (this.audio) {
       this.uploadAudioTS(buffers, opts.audioStreamId);
@@ -353,17 +398,55 @@ function install(JSMpeg, options) {
     }
     return n;
   };
+  // Selected frames only, for buffers of any mix of sizes: requests name streams by their index into the buffers of the
+  // FOLLOWING decodeTS / decode calls (null clears); each size's batch gets the requests of its streams.  selected(): per
+  // request { size: 'WxH', picture } (picture null: no such frame; the whole entry null: the stream was skipped);
+  // selectInfo(): { 'WxH': HIPBatch.selectInfo() }.
+  HIPBatchRouter.prototype.select = function (requests) {
+    this.requests = requests && requests.length ? requests.map((r) => (Array.isArray(r) ? { stream: r[0], frame: r[1] } : r)) : null;
+    this.placed = null;
+    return this;
+  };
+  HIPBatchRouter.prototype.requestsFor = function (batch, index) {
+    if (!this.requests) return null;
+    const key = batch.width + 'x' + batch.height, mine = [];
+    if (!this.placed) this.placed = this.requests.map(() => null);
+    this.requests.forEach((r, k) => {
+      const s = index.indexOf(r.stream);
+      if (s < 0) return;
+      this.placed[k] = { size: key, at: mine.length };
+      mine.push([s, r.frame]);
+    });
+    return mine.length ? mine : null;
+  };
+  HIPBatchRouter.prototype.selected = function () {
+    if (!this.requests || !this.placed) return [];
+    const per = new Map();
+    return this.placed.map((pl) => {
+      if (!pl) return null;
+      if (!per.has(pl.size)) per.set(pl.size, this.batches.get(pl.size).selected());
+      return { size: pl.size, picture: per.get(pl.size)[pl.at] };
+    });
+  };
+  HIPBatchRouter.prototype.selectInfo = function () {
+    const out = {};
+    for (const [key, b] of this.batches.entries()) if (b.requests) out[key] = b.selectInfo();
+    return out;
+  };
   HIPBatchRouter.prototype.decodeTS = function (buffers, opts) {
     opts = opts || {};
+    this.placed = null;
     return this.route(buffers, (b) => HIPBatchRouter.probeTS(b, opts.streamId), (batch, bufs, index) => batch.decodeTS(bufs, Object.assign({}, opts, {
+      select: this.requestsFor(batch, index),
       onFrame: opts.onFrame && ((f) => { f.batchStream = f.stream; f.stream = index[f.stream]; opts.onFrame(f); }),
       onAudio: opts.onAudio && ((a) => { a.stream = index[a.stream]; opts.onAudio(a); }),
     })));
   };
   HIPBatchRouter.prototype.decode = function (buffers, opts) {      // elementary streams
     opts = opts || {};
+    this.placed = null;
     return this.route(buffers, (b) => HIPBatchRouter.probeES(b, 1 << 16), (batch, bufs, index) => {
-      batch.upload(bufs).decode();
+      batch.upload(bufs).select(this.requestsFor(batch, index)).decode();
       return opts.onFrame ? batch.forEachFrame(opts, (f) => { f.batchStream = f.stream; f.stream = index[f.stream]; opts.onFrame(f); }) : batch.pictures;
     });
   };
