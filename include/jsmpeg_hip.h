@@ -780,6 +780,62 @@ int jsmpeg_hip_live_render_tensor_latest(jsmpeg_hip_live_t *l, const uint32_t *s
                                          const jsmpeg_hip_tensor_desc_t *desc, void *dev_out, void *hip_stream,
                                          uint8_t *have);
 
+/* ------------------------------------------------------------------ part 8
+ * The way back: an MPEG-1 INTRA ENCODER on the device.  Frames in HBM (a pool slot, a live picture's device_frame, the caller's
+ * own planes) or RGB tensors -> elementary streams that a jsmpeg player, the reference decoder and parts 2 and 5 of this header
+ * read.  I pictures only, one quantiser scale per picture, the default intra matrix, one slice per macroblock row; the integer
+ * transform, the quantiser and the colour conversion are stated exactly in jsmpeg_amd/csrc/enc_block.h.  EVERY picture carries
+ * its own sequence and GOP header in front (20 bytes): every picture is a joining point for a viewer and a unit for
+ * jsmpeg_hip_split_gops.  Streams lie in the output from 16-byte aligned begins with 0xff in front of the first, between them
+ * and 256 bytes behind the last: the buffer can be handed to jsmpeg_hip_batch_attach_device as it is.
+ * OUT OF SCOPE: P pictures (they need a closed loop), rate control, custom matrices, a Node binding, resizing of YCbCr (resize
+ * the RGB tensor).
+ * A pass is a PURE ENQUEUE on hip_stream, like jsmpeg_hip_batch_enqueue: every size and offset is worked out on the device; the
+ * host waits in jsmpeg_hip_encoder_sync and the readers only (they settle the pass first).  One pass at a time per handle: a
+ * second encode before the first is settled is refused.  ORDERING AGAINST THE PRODUCER OF THE FRAMES IS THE CALLER'S: pass the
+ * stream the decode or render ran on, after jsmpeg_hip_batch_sync, exactly as jsmpeg_hip_batch_frame_pool demands of consumers.
+ * A bad argument -- a size of zero or out of range, a quantiser scale of 0 or above 31, streams that do not ascend or reach
+ * max_streams, count above max_pictures, a NULL or misaligned (16 bytes) frame -- returns < 0 with jsmpeg_hip_last_error, and
+ * nothing is launched.  Without a device jsmpeg_hip_encoder_create returns NULL ("no CPU fallback"). */
+typedef struct jsmpeg_hip_encoder_t jsmpeg_hip_encoder_t;
+typedef struct jsmpeg_hip_encoder_config_t {
+	int32_t width, height;        /* display size, 1..4095; coded size = next multiples of 16; at most 175 macroblock rows */
+	uint32_t max_pictures;        /* per call */
+	uint32_t max_streams;         /* per call */
+	uint64_t max_es_bytes;        /* output capacity per call (the leading gap and the gaps between streams included) */
+	uint32_t frame_rate_code;     /* 1..8 as in the sequence header; 0: 5 (30 / s) */
+	int32_t device;               /* -1: current */
+} jsmpeg_hip_encoder_config_t;
+#define JSMPEG_HIP_ENC_END 1u     /* close every stream of the call with a sequence end code */
+
+jsmpeg_hip_encoder_t *jsmpeg_hip_encoder_create(const jsmpeg_hip_encoder_config_t *config);
+void jsmpeg_hip_encoder_destroy(jsmpeg_hip_encoder_t *enc);
+/* frames[k]: DEVICE pointer to picture k's planes, Y | Cr | Cb of the coded size (jsmpeg_hip_batch_geometry's layout: a
+ * pool slot, a live picture's device_frame, the caller's own); stream[k]: ascending, < max_streams (NULL: all stream 0);
+ * qscale[k]: 1..31 (NULL: `quantiser_scale` for all).  Pure enqueue on hip_stream; returns 0 or < 0. */
+int jsmpeg_hip_encoder_encode(jsmpeg_hip_encoder_t *enc, const void *const *frames, const uint32_t *stream, const uint8_t *qscale,
+                              uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream);
+/* the same from `count` RGB pictures in ONE device tensor: uint8, layout / order as in part 7's enums, display size; converted
+ * into a frame store of the handle's own (max_pictures frames, allocated by the first call) */
+int jsmpeg_hip_encoder_encode_rgb(jsmpeg_hip_encoder_t *enc, const void *dev_rgb, uint32_t layout, uint32_t order, const uint32_t *stream,
+                                  const uint8_t *qscale, uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream);
+int jsmpeg_hip_encoder_sync(jsmpeg_hip_encoder_t *enc);             /* settles; < 0 with a message on overflow: nothing of the call is valid */
+int jsmpeg_hip_encoder_query(jsmpeg_hip_encoder_t *enc);            /* 1 finished, 0 not; never blocks */
+void *jsmpeg_hip_encoder_es(jsmpeg_hip_encoder_t *enc, uint64_t *total_bytes);   /* device buffer of the last call; NULL after an overflow */
+int jsmpeg_hip_encoder_stream_range(jsmpeg_hip_encoder_t *enc, uint32_t stream, uint64_t *begin, uint64_t *end);
+int jsmpeg_hip_encoder_picture_range(jsmpeg_hip_encoder_t *enc, uint32_t k, uint64_t *offset, uint32_t *bytes);   /* from its sequence header on */
+/* the stream's bytes to the host (at most cap; host NULL: none); returns the stream's length or < 0 */
+int64_t jsmpeg_hip_encoder_read_es(jsmpeg_hip_encoder_t *enc, uint32_t stream, void *host, uint64_t cap);
+int jsmpeg_hip_encoder_timings(jsmpeg_hip_encoder_t *enc, float out_ms[4]);      /* convert, measure + scan, write, total */
+
+/* Host-side TS mux (plain C, no device; a jsmpeg player takes TS): one PES per unit (a picture's range in `es`) with its PTS,
+ * the payload in 184-byte pieces, the unit's last packet padded by adaptation-field stuffing -- what the reference's demuxer
+ * (ts.js:127-147, jsmpeg_hip_ts_demux_host) ends a video PES by.  *continuity (in / out, may be NULL: 0) is the PID's counter,
+ * carried across calls.  Returns the bytes written, a multiple of 188, or < 0; ts == NULL: the bytes needed. */
+int64_t jsmpeg_hip_ts_mux_host(const uint8_t *es, const uint64_t *offset, const uint32_t *bytes, const uint64_t *pts_90k,
+                               uint32_t n_units, uint32_t stream_id, uint32_t pid, uint8_t *continuity /* in/out */,
+                               uint8_t *ts, uint64_t ts_cap);
+
 /* Last error of the calling thread ("" if none). */
 const char *jsmpeg_hip_last_error(void);
 /* Number of visible HIP devices (0 if none / runtime unusable). */

@@ -1,0 +1,457 @@
+/*
+ * MPEG-1 intra encoder on the device (include/jsmpeg_hip.h part 8): frames in HBM, or RGB tensors, to elementary streams
+ * that a jsmpeg player, the reference decoder and this library's own batch / live front ends read.  The per-macroblock work
+ * is enc_block.h's (shared with tests/sim/sim_encode.cpp); here are the kernels, the pass as a pure enqueue, and the host-side
+ * TS mux.
+ *
+ * A pass on the caller's stream, every size and offset worked out on the device:
+ *   k_enc_rgb            tensor input only: RGB -> Y | Cr | Cb of the coded size in the encoder's frame store
+ *   k_enc_measure        a macroblock per lane: transform, quantise, count bits; 12 bytes per macroblock out
+ *   k_enc_scan_slices    a slice per lane: the macroblocks' bit offsets (their DC codes depend on the predecessor), the slice's bytes
+ *   k_enc_scan_pictures  a picture per lane: the slices' offsets, the picture's bytes
+ *   k_enc_place          one workgroup: the pictures' and streams' offsets in the output, the total, the overflow flag
+ *   k_enc_clear          zeroes the total (the write ORs into it), 0xff behind it
+ *   k_enc_write          a macroblock per lane again: transform, quantise, write bits; the headers by the lanes that begin them
+ * The host waits in jsmpeg_hip_encoder_sync and the readers only.
+ */
+#include "engine_internal.h"
+#include "enc_block.h"
+
+#define JM_ENC_LANES 64
+
+struct JmEncPic {
+	const uint8_t *frame;    /* Y | Cr | Cb of the coded size */
+	uint32_t stream, ordinal, q;
+	uint32_t last;           /* the last picture of its stream in this call */
+};
+
+struct JmEncArgs {
+	uint32_t width, height, cw, ch, mbw, mbh, count, frame_rate_code, end;
+	uint64_t cap;
+	const JmEncPic *pics;
+	const JmEncTables *tables;
+	JmEncMb *mb;             /* [count][mbh][mbw] */
+	uint32_t *slice;         /* [count][mbh]: bytes, then offset in the picture */
+	uint64_t *result;        /* total | status | stream_begin[max_streams] | stream_end[max_streams] | pic_off[max_pictures] | pic_bytes (u32) */
+	uint32_t max_streams, max_pictures;
+	uint32_t *words;         /* the output */
+};
+JM_HD uint64_t *enc_stream_begin(const JmEncArgs &a) { return a.result + 2; }
+JM_HD uint64_t *enc_stream_end(const JmEncArgs &a) { return a.result + 2 + a.max_streams; }
+JM_HD uint64_t *enc_pic_off(const JmEncArgs &a) { return a.result + 2 + 2 * (size_t)a.max_streams; }
+JM_HD uint32_t *enc_pic_bytes(const JmEncArgs &a) { return (uint32_t *)(a.result + 2 + 2 * (size_t)a.max_streams + a.max_pictures); }
+static size_t enc_result_bytes(uint32_t max_streams, uint32_t max_pictures) {
+	return 8 * (2 + 2 * (size_t)max_streams + max_pictures) + 4 * (size_t)max_pictures;
+}
+
+/* ------------------------------------------------------------------ kernels */
+
+__global__ void __launch_bounds__(256) k_enc_rgb(JmEncArgs a, const uint8_t *rgb, uint32_t layout, uint32_t order) {
+	const uint32_t qw = a.cw >> 1, qh = a.ch >> 1;
+	const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= (uint64_t)a.count * qw * qh) return;
+	const uint32_t k = (uint32_t)(g / ((uint64_t)qw * qh)), r = (uint32_t)(g % ((uint64_t)qw * qh));
+	jm_enc_rgb_quad(rgb + (size_t)k * a.width * a.height * 3, layout, order, a.width, a.height, r % qw, r / qw,
+	                const_cast<uint8_t *>(a.pics[k].frame), a.cw, a.ch);
+}
+
+/* the macroblock of lane g: picture, row, column and the three plane pointers */
+struct EncLane { uint32_t k, row, col; const uint8_t *y, *cr, *cb; };
+static __device__ __forceinline__ EncLane enc_lane(const JmEncArgs &a, uint64_t g) {
+	EncLane l;
+	const uint32_t mbs = a.mbw * a.mbh, m = (uint32_t)(g % mbs);
+	l.k = (uint32_t)(g / mbs); l.row = m / a.mbw; l.col = m % a.mbw;
+	const uint8_t *f = a.pics[l.k].frame;
+	const size_t luma = (size_t)a.cw * a.ch, coff = (size_t)l.row * 8u * (a.cw >> 1) + (size_t)l.col * 8u;
+	l.y = f + (size_t)l.row * 16u * a.cw + (size_t)l.col * 16u;
+	l.cr = f + luma + coff;
+	l.cb = f + luma + (luma >> 2) + coff;
+	return l;
+}
+
+__global__ void __launch_bounds__(JM_ENC_LANES) k_enc_measure(JmEncArgs a) {
+	__shared__ int16_t zz[64 * JM_ENC_LANES];
+	const uint64_t g = (uint64_t)blockIdx.x * JM_ENC_LANES + threadIdx.x;
+	if (g >= (uint64_t)a.count * a.mbw * a.mbh) return;
+	const EncLane l = enc_lane(a, g);
+	JmEncMb rec;
+	uint64_t dcs;
+	rec.bits = jm_enc_measure(l.y, l.cr, l.cb, a.cw, a.pics[l.k].q, a.tables, zz + threadIdx.x, JM_ENC_LANES, &dcs);
+	rec.dc[0] = (uint32_t)dcs; rec.dc[1] = (uint32_t)(dcs >> 32);
+	a.mb[g] = rec;
+}
+
+__global__ void __launch_bounds__(64) k_enc_scan_slices(JmEncArgs a) {
+	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+	if (s >= a.count * a.mbh) return;
+	a.slice[s] = jm_enc_scan_slice(a.mb + (size_t)s * a.mbw, a.mbw, a.tables);
+}
+
+__global__ void __launch_bounds__(64) k_enc_scan_pictures(JmEncArgs a) {
+	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= a.count) return;
+	enc_pic_bytes(a)[k] = jm_enc_scan_picture(a.slice + (size_t)k * a.mbh, a.mbh);
+}
+
+/* one workgroup: 256 pictures at a time through LDS, lane 0 walks them */
+__global__ void __launch_bounds__(256) k_enc_place(JmEncArgs a) {
+	__shared__ uint32_t s_bytes[256], s_stream[256];
+	__shared__ uint64_t s_off[256];
+	__shared__ JmEncPlace place;
+	uint64_t *sb = enc_stream_begin(a), *se = enc_stream_end(a);
+	for (uint32_t i = threadIdx.x; i < a.max_streams; i += 256) { sb[i] = 0; se[i] = 0; }
+	if (threadIdx.x == 0) place = jm_enc_place_begin();
+	__syncthreads();
+	for (uint32_t base = 0; base < a.count; base += 256) {
+		const uint32_t k = base + threadIdx.x, n = min(256u, a.count - base);
+		if (k < a.count) { s_bytes[threadIdx.x] = enc_pic_bytes(a)[k]; s_stream[threadIdx.x] = a.pics[k].stream; }
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			JmEncPlace p = place;
+			for (uint32_t i = 0; i < n; i++) s_off[i] = jm_enc_place_picture(p, s_stream[i], s_bytes[i], a.end != 0, sb, se);
+			place = p;
+		}
+		__syncthreads();
+		if (k < a.count) enc_pic_off(a)[k] = s_off[threadIdx.x];
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) {
+		JmEncPlace p = place;
+		jm_enc_place_close(p, a.end != 0, se);
+		a.result[0] = p.at;
+		a.result[1] = p.at > a.cap ? 1u : 0u;
+	}
+}
+
+__global__ void __launch_bounds__(256) k_enc_clear(JmEncArgs a) {
+	if (a.result[1]) return;
+	const uint64_t total16 = a.result[0] >> 4, n = total16 + (JM_ENC_TAIL >> 4);
+	uint4 *out = reinterpret_cast<uint4 *>(a.words);
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+		const uint32_t v = i < total16 ? 0u : 0xffffffffu;
+		out[i] = make_uint4(v, v, v, v);
+	}
+}
+
+__global__ void __launch_bounds__(JM_ENC_LANES) k_enc_write(JmEncArgs a) {
+	__shared__ int16_t zz[64 * JM_ENC_LANES];
+	if (a.result[1]) return;
+	const uint64_t g = (uint64_t)blockIdx.x * JM_ENC_LANES + threadIdx.x;
+	if (g >= (uint64_t)a.count * a.mbw * a.mbh) return;
+	const EncLane l = enc_lane(a, g);
+	const JmEncPic pic = a.pics[l.k];
+	const uint64_t pic_at = enc_pic_off(a)[l.k], slice_at = pic_at + a.slice[(size_t)l.k * a.mbh + l.row];
+	if (l.col == 0) {
+		jm_enc_put_slice_header(a.words, slice_at, l.row, pic.q);
+		if (l.row == 0) {
+			jm_enc_put_picture_headers(a.words, pic_at, a.width, a.height, a.frame_rate_code, pic.ordinal);
+			if (pic.last) jm_enc_put_stream_tail(a.words, pic_at + enc_pic_bytes(a)[l.k], a.end != 0);
+			if (l.k == 0)
+				for (uint32_t i = 0; i < JM_ENC_LEAD_GAP / 4; i++) jm_enc_or(a.words + i, 0xffffffffu);
+		}
+	}
+	const uint32_t pred = l.col ? jm_enc_pred_of(jm_enc_mb_dcs(a.mb[g - 1])) : JM_ENC_PRED0;
+	JmEncBits bw = jm_enc_bits_at(a.words, slice_at * 8u + a.mb[g].bits);
+	jm_enc_write(l.y, l.cr, l.cb, a.cw, pic.q, a.tables, zz + threadIdx.x, JM_ENC_LANES, pred, bw);
+	jm_enc_flush(bw);
+}
+
+/* ------------------------------------------------------------------ the handle */
+
+struct jsmpeg_hip_encoder_t {
+	jsmpeg_hip_encoder_config_t cfg;
+	int device;
+	uint32_t cw, ch, mbw, mbh;
+	uint64_t frame_bytes;
+	JmEncTables *d_tables;
+	JmEncPic *d_pics, *h_pics;       /* h_pics: pinned */
+	JmEncMb *d_mb;
+	uint32_t *d_slice;
+	uint64_t *d_result, *h_result;   /* h_result: pinned */
+	uint8_t *d_es;
+	uint8_t *d_store;                /* frames of the tensor input, allocated by the first jsmpeg_hip_encoder_encode_rgb */
+	hipStream_t stream;
+	hipEvent_t ev[4], ev_done;
+	bool pending, valid, have_pass;
+	uint32_t count;
+};
+
+static void enc_free(jsmpeg_hip_encoder_t *e) {
+	if (!e) return;
+	hipSetDevice(e->device);
+	if (e->pending) hipEventSynchronize(e->ev_done);
+	hipFree(e->d_tables); hipFree(e->d_pics); hipFree(e->d_mb); hipFree(e->d_slice); hipFree(e->d_result); hipFree(e->d_es); hipFree(e->d_store);
+	if (e->h_pics) hipHostFree(e->h_pics);
+	if (e->h_result) hipHostFree(e->h_result);
+	for (hipEvent_t &v : e->ev) if (v) hipEventDestroy(v);
+	if (e->ev_done) hipEventDestroy(e->ev_done);
+	delete e;
+}
+
+static int enc_alloc(jsmpeg_hip_encoder_t *e) {
+	static const JmEncTables tables = jm_enc_make_tables();
+	const size_t mbs = (size_t)e->mbw * e->mbh, np = e->cfg.max_pictures;
+	const size_t rb = enc_result_bytes(e->cfg.max_streams, e->cfg.max_pictures);
+	HIP_TRY(jm_malloc(&e->d_tables, sizeof(JmEncTables)));
+	HIP_TRY(hipMemcpy(e->d_tables, &tables, sizeof(JmEncTables), hipMemcpyHostToDevice));
+	HIP_TRY(jm_malloc(&e->d_pics, sizeof(JmEncPic) * np));
+	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_pics), sizeof(JmEncPic) * np, hipHostMallocDefault));
+	HIP_TRY(jm_malloc(&e->d_mb, sizeof(JmEncMb) * mbs * np));
+	HIP_TRY(jm_malloc(&e->d_slice, sizeof(uint32_t) * e->mbh * np));
+	HIP_TRY(jm_malloc(&e->d_result, rb));
+	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_result), rb, hipHostMallocDefault));
+	memset(e->h_result, 0, rb);
+	HIP_TRY(jm_malloc(&e->d_es, jm_enc_align16(e->cfg.max_es_bytes) + JM_ENC_TAIL + 16));
+	for (hipEvent_t &v : e->ev) HIP_TRY(hipEventCreate(&v));
+	HIP_TRY(hipEventCreateWithFlags(&e->ev_done, hipEventDisableTiming));
+	return 0;
+}
+
+extern "C" jsmpeg_hip_encoder_t *jsmpeg_hip_encoder_create(const jsmpeg_hip_encoder_config_t *config) {
+	g_err[0] = 0;
+	if (!config) { fail("jsmpeg_hip_encoder_create: NULL config"); return nullptr; }
+	if (jsmpeg_hip_device_count() <= 0) {
+		fail("no HIP device available: the MPEG-1 encode path has no CPU fallback");
+		return nullptr;
+	}
+	if (config->width < 1 || config->width > 4095 || config->height < 1 || config->height > 4095) {
+		fail("encoder: size %d x %d, each side must be 1 .. 4095", config->width, config->height); return nullptr;
+	}
+	if ((config->height + 15) / 16 > 175) { fail("encoder: height %d has more than 175 macroblock rows (slice start codes 01 .. AF)", config->height); return nullptr; }
+	if (config->max_pictures < 1 || config->max_streams < 1 || config->max_es_bytes < 64) {
+		fail("encoder: max_pictures, max_streams must be >= 1 and max_es_bytes >= 64"); return nullptr;
+	}
+	if (config->max_es_bytes > 0xffffffffull * 4) { fail("encoder: max_es_bytes above 16 GiB"); return nullptr; }
+	if (config->frame_rate_code > 8) { fail("encoder: frame_rate_code %u, must be 1 .. 8 (0: 30 / s)", config->frame_rate_code); return nullptr; }
+	jsmpeg_hip_encoder_t *e = new jsmpeg_hip_encoder_t();
+	e->cfg = *config;
+	if (e->cfg.frame_rate_code == 0) e->cfg.frame_rate_code = 5;
+	if (config->device >= 0 && hipSetDevice(config->device) != hipSuccess) { fail("hipSetDevice(%d) failed", config->device); delete e; return nullptr; }
+	if (hipGetDevice(&e->device) != hipSuccess) { fail("hipGetDevice failed"); delete e; return nullptr; }
+	e->mbw = (uint32_t)(config->width + 15) >> 4; e->mbh = (uint32_t)(config->height + 15) >> 4;
+	e->cw = e->mbw * 16; e->ch = e->mbh * 16;
+	e->frame_bytes = (uint64_t)e->cw * e->ch * 3 / 2;
+	if (enc_alloc(e) != 0) { enc_free(e); return nullptr; }
+	return e;
+}
+
+extern "C" void jsmpeg_hip_encoder_destroy(jsmpeg_hip_encoder_t *e) { enc_free(e); }
+
+/* waits for the pass in flight, reads its verdict */
+static int enc_settle(jsmpeg_hip_encoder_t *e) {
+	if (!e->pending) return 0;
+	HIP_TRY(hipSetDevice(e->device));
+	e->pending = false;
+	HIP_TRY(hipEventSynchronize(e->ev_done));
+	if (e->h_result[1]) {
+		e->valid = false;
+		return fail("encoder: the call's streams need %llu bytes, max_es_bytes is %llu: nothing of the call is valid",
+		            (unsigned long long)e->h_result[0], (unsigned long long)e->cfg.max_es_bytes);
+	}
+	e->valid = true;
+	return 0;
+}
+
+static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const void *dev_rgb, uint32_t layout, uint32_t order,
+                   const uint32_t *stream, const uint8_t *qscale, uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream) {
+	g_err[0] = 0;
+	if (!e) return fail("encoder: NULL handle");
+	if (e->pending) return fail("encoder: an encode is in flight: jsmpeg_hip_encoder_sync (or a reader) settles it first");
+	if (count > e->cfg.max_pictures) return fail("encoder: %u pictures > max_pictures %u", count, e->cfg.max_pictures);
+	if (flags & ~JSMPEG_HIP_ENC_END) return fail("encoder: unknown flags 0x%x", flags);
+	if (count && !frames && !dev_rgb) return fail("encoder: NULL frames");
+	if (dev_rgb && (layout > JSMPEG_HIP_TENSOR_NHWC || order > JSMPEG_HIP_TENSOR_BGR)) return fail("encoder: layout %u / order %u unknown", layout, order);
+	if (!qscale && (quantiser_scale < 1 || quantiser_scale > 31)) return fail("encoder: quantiser_scale %u, must be 1 .. 31", quantiser_scale);
+	for (uint32_t k = 0; k < count; k++) {
+		if (frames && !frames[k]) return fail("encoder: frames[%u] is NULL", k);
+		if (frames && ((uintptr_t)frames[k] & 15u)) return fail("encoder: frames[%u] is not 16-byte aligned", k);
+		if (qscale && (qscale[k] < 1 || qscale[k] > 31)) return fail("encoder: qscale[%u] = %u, must be 1 .. 31", k, qscale[k]);
+		if (stream && stream[k] >= e->cfg.max_streams) return fail("encoder: stream[%u] = %u >= max_streams %u", k, stream[k], e->cfg.max_streams);
+		if (stream && k && stream[k] < stream[k - 1]) return fail("encoder: stream[] must ascend (stream[%u] = %u after %u)", k, stream[k], stream[k - 1]);
+	}
+	HIP_TRY(hipSetDevice(e->device));
+	hipStream_t st = (hipStream_t)hip_stream;
+	e->count = count;
+	e->have_pass = true;
+	if (count == 0) { e->valid = true; e->h_result[0] = 0; e->h_result[1] = 0; return 0; }
+	if (dev_rgb && !e->d_store) HIP_TRY(jm_malloc(&e->d_store, (size_t)e->frame_bytes * e->cfg.max_pictures));
+	for (uint32_t k = 0, ordinal = 0; k < count; k++) {
+		const uint32_t s = stream ? stream[k] : 0;
+		ordinal = (k && s == e->h_pics[k - 1].stream) ? ordinal + 1 : 0;
+		JmEncPic &p = e->h_pics[k];
+		p.frame = frames ? (const uint8_t *)frames[k] : e->d_store + (size_t)k * e->frame_bytes;
+		p.stream = s; p.ordinal = ordinal; p.q = qscale ? qscale[k] : quantiser_scale;
+		p.last = (k + 1 == count || (stream && stream[k + 1] != s)) ? 1u : 0u;
+	}
+	JmEncArgs a;
+	a.width = (uint32_t)e->cfg.width; a.height = (uint32_t)e->cfg.height; a.cw = e->cw; a.ch = e->ch; a.mbw = e->mbw; a.mbh = e->mbh;
+	a.count = count; a.frame_rate_code = e->cfg.frame_rate_code; a.end = (flags & JSMPEG_HIP_ENC_END) ? 1u : 0u;
+	a.cap = e->cfg.max_es_bytes;
+	a.pics = e->d_pics; a.tables = e->d_tables; a.mb = e->d_mb; a.slice = e->d_slice; a.result = e->d_result;
+	a.max_streams = e->cfg.max_streams; a.max_pictures = e->cfg.max_pictures;
+	a.words = reinterpret_cast<uint32_t *>(e->d_es);
+	const uint64_t lanes = (uint64_t)count * e->mbw * e->mbh;
+	const uint32_t mb_grid = (uint32_t)((lanes + JM_ENC_LANES - 1) / JM_ENC_LANES);
+	e->stream = st;
+	e->valid = false;
+	HIP_TRY(hipMemcpyAsync(e->d_pics, e->h_pics, sizeof(JmEncPic) * count, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipEventRecord(e->ev[0], st));
+	if (dev_rgb) {
+		const uint64_t quads = (uint64_t)count * (e->cw >> 1) * (e->ch >> 1);
+		k_enc_rgb<<<dim3((uint32_t)((quads + 255) / 256)), dim3(256), 0, st>>>(a, (const uint8_t *)dev_rgb, layout, order);
+	}
+	HIP_TRY(hipEventRecord(e->ev[1], st));
+	k_enc_measure<<<dim3(mb_grid), dim3(JM_ENC_LANES), 0, st>>>(a);
+	k_enc_scan_slices<<<dim3((count * e->mbh + 63) / 64), dim3(64), 0, st>>>(a);
+	k_enc_scan_pictures<<<dim3((count + 63) / 64), dim3(64), 0, st>>>(a);
+	k_enc_place<<<dim3(1), dim3(256), 0, st>>>(a);
+	HIP_TRY(hipEventRecord(e->ev[2], st));
+	k_enc_clear<<<dim3(1024), dim3(256), 0, st>>>(a);
+	k_enc_write<<<dim3(mb_grid), dim3(JM_ENC_LANES), 0, st>>>(a);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(e->ev[3], st));
+	HIP_TRY(hipMemcpyAsync(e->h_result, e->d_result, enc_result_bytes(e->cfg.max_streams, e->cfg.max_pictures), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipEventRecord(e->ev_done, st));
+	e->pending = true;
+	return 0;
+}
+
+extern "C" int jsmpeg_hip_encoder_encode(jsmpeg_hip_encoder_t *e, const void *const *frames, const uint32_t *stream, const uint8_t *qscale,
+                                         uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream) {
+	if (count && !frames) { g_err[0] = 0; return fail("encoder: NULL frames"); }
+	return enc_run(e, frames, nullptr, 0, 0, stream, qscale, count, quantiser_scale, flags, hip_stream);
+}
+
+extern "C" int jsmpeg_hip_encoder_encode_rgb(jsmpeg_hip_encoder_t *e, const void *dev_rgb, uint32_t layout, uint32_t order, const uint32_t *stream,
+                                             const uint8_t *qscale, uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream) {
+	if (count && !dev_rgb) { g_err[0] = 0; return fail("encoder: NULL tensor"); }
+	return enc_run(e, nullptr, dev_rgb, layout, order, stream, qscale, count, quantiser_scale, flags, hip_stream);
+}
+
+extern "C" int jsmpeg_hip_encoder_sync(jsmpeg_hip_encoder_t *e) {
+	g_err[0] = 0;
+	if (!e) return fail("encoder: NULL handle");
+	return enc_settle(e);
+}
+
+extern "C" int jsmpeg_hip_encoder_query(jsmpeg_hip_encoder_t *e) {
+	g_err[0] = 0;
+	if (!e) return fail("encoder: NULL handle");
+	if (!e->pending) return 1;
+	HIP_TRY(hipSetDevice(e->device));
+	const hipError_t r = hipEventQuery(e->ev_done);
+	if (r == hipSuccess) return 1;
+	if (r == hipErrorNotReady) return 0;
+	return fail("hipEventQuery: %s", hipGetErrorString(r));
+}
+
+/* the readers: settle, then refuse a handle without a valid pass */
+static int enc_ready(jsmpeg_hip_encoder_t *e) {
+	g_err[0] = 0;
+	if (!e) return fail("encoder: NULL handle");
+	if (enc_settle(e) < 0) return -1;
+	if (!e->have_pass) return fail("encoder: nothing was encoded yet");
+	if (!e->valid) return fail("encoder: the last call overflowed max_es_bytes (%llu): nothing of it is valid", (unsigned long long)e->cfg.max_es_bytes);
+	return 0;
+}
+
+extern "C" void *jsmpeg_hip_encoder_es(jsmpeg_hip_encoder_t *e, uint64_t *total_bytes) {
+	if (enc_ready(e) < 0) return nullptr;
+	if (total_bytes) *total_bytes = e->h_result[0];
+	return e->d_es;
+}
+
+extern "C" int jsmpeg_hip_encoder_stream_range(jsmpeg_hip_encoder_t *e, uint32_t stream, uint64_t *begin, uint64_t *end) {
+	if (enc_ready(e) < 0) return -1;
+	if (stream >= e->cfg.max_streams) return fail("encoder: stream %u >= max_streams %u", stream, e->cfg.max_streams);
+	const bool any = e->count != 0;
+	if (begin) *begin = any ? e->h_result[2 + stream] : 0;
+	if (end) *end = any ? e->h_result[2 + e->cfg.max_streams + stream] : 0;
+	return 0;
+}
+
+extern "C" int jsmpeg_hip_encoder_picture_range(jsmpeg_hip_encoder_t *e, uint32_t k, uint64_t *offset, uint32_t *bytes) {
+	if (enc_ready(e) < 0) return -1;
+	if (k >= e->count) return fail("encoder: picture %u of %u", k, e->count);
+	const uint64_t *off = e->h_result + 2 + 2 * (size_t)e->cfg.max_streams;
+	if (offset) *offset = off[k];
+	if (bytes) *bytes = reinterpret_cast<const uint32_t *>(off + e->cfg.max_pictures)[k];
+	return 0;
+}
+
+extern "C" int64_t jsmpeg_hip_encoder_read_es(jsmpeg_hip_encoder_t *e, uint32_t stream, void *host, uint64_t cap) {
+	uint64_t b = 0, n = 0;
+	if (jsmpeg_hip_encoder_stream_range(e, stream, &b, &n) < 0) return -1;
+	n -= b;
+	const uint64_t k = std::min(n, cap);
+	if (k && host) {
+		HIP_TRY(hipSetDevice(e->device));
+		HIP_TRY(hipMemcpy(host, e->d_es + b, k, hipMemcpyDeviceToHost));
+	}
+	return (int64_t)n;
+}
+
+extern "C" int jsmpeg_hip_encoder_timings(jsmpeg_hip_encoder_t *e, float out_ms[4]) {
+	if (enc_ready(e) < 0) return -1;
+	if (!out_ms) return fail("encoder: NULL out_ms");
+	for (int i = 0; i < 4; i++) out_ms[i] = 0.0f;
+	if (!e->count) return 0;
+	HIP_TRY(hipSetDevice(e->device));
+	for (int i = 0; i < 3; i++) HIP_TRY(hipEventElapsedTime(&out_ms[i], e->ev[i], e->ev[i + 1]));
+	HIP_TRY(hipEventElapsedTime(&out_ms[3], e->ev[0], e->ev[3]));
+	return 0;
+}
+
+/* ------------------------------------------------------------------ TS mux (host, no device)
+ * One PES per unit: 00 00 01 stream_id, PES_packet_length (0 when the unit does not fit 16 bits), '10' flags, PTS only, the
+ * payload in 184-byte pieces.  The reference's demuxer (ts.js:127-147) ends a PES by its length or -- length 0 -- by a
+ * LATER packet of it that carries an adaptation field, so: the unit's last packet is stuffed to its size by an adaptation
+ * field, no packet between the first and the last has one, and a unit of unknown length whose last packet would come out full
+ * gets one stuffing byte in its FIRST packet (an adaptation field there ends nothing: ts.js:143). */
+extern "C" int64_t jsmpeg_hip_ts_mux_host(const uint8_t *es, const uint64_t *offset, const uint32_t *bytes, const uint64_t *pts_90k,
+                                          uint32_t n_units, uint32_t stream_id, uint32_t pid, uint8_t *continuity, uint8_t *ts, uint64_t ts_cap) {
+	g_err[0] = 0;
+	if (n_units && (!offset || !bytes || !pts_90k || (ts && !es))) return fail("ts_mux: NULL argument");
+	if (pid > 0x1fff || stream_id > 0xff) return fail("ts_mux: pid %u / stream id %u out of range", pid, stream_id);
+	uint8_t cc = continuity ? (uint8_t)(*continuity & 15u) : 0;
+	uint64_t at = 0;
+	for (uint32_t u = 0; u < n_units; u++) {
+		const uint64_t total = 14 + (uint64_t)bytes[u];               /* PES header + payload */
+		const bool sized = (uint64_t)bytes[u] + 8 <= 0xffff;
+		uint64_t lead = (!sized && total % 184 == 0) ? 1 : 0;          /* stuffing bytes (adaptation field) in the first packet */
+		const uint64_t packets = (total + lead + 183) / 184;
+		if (!ts) { at += packets * 188; continue; }
+		if (at + packets * 188 > ts_cap) return fail("ts_mux: %llu bytes do not fit ts_cap %llu", (unsigned long long)(at + packets * 188), (unsigned long long)ts_cap);
+		uint8_t head[14];
+		const uint32_t plen = sized ? bytes[u] + 8 : 0;
+		const uint64_t p = pts_90k[u] & 0x1ffffffffull;
+		head[0] = 0; head[1] = 0; head[2] = 1; head[3] = (uint8_t)stream_id;
+		head[4] = (uint8_t)(plen >> 8); head[5] = (uint8_t)plen;
+		head[6] = 0x80; head[7] = 0x80; head[8] = 5;
+		head[9] = (uint8_t)(0x21 | ((p >> 29) & 0x0e));
+		head[10] = (uint8_t)(p >> 22); head[11] = (uint8_t)(0x01 | ((p >> 14) & 0xfe));
+		head[12] = (uint8_t)(p >> 7); head[13] = (uint8_t)(0x01 | ((p << 1) & 0xfe));
+		uint64_t done = 0;                                             /* bytes of header + payload emitted */
+		for (uint64_t k = 0; k < packets; k++) {
+			uint8_t *pk = ts + at;
+			const uint64_t left = total - done;
+			uint64_t stuff = k == 0 ? lead : 0;                        /* bytes of adaptation field, its length byte included */
+			if (left + stuff < 184) stuff = 184 - left;                /* the last packet: padded to size */
+			const uint64_t n = 184 - stuff;
+			pk[0] = 0x47;
+			pk[1] = (uint8_t)((k == 0 ? 0x40 : 0) | (pid >> 8));
+			pk[2] = (uint8_t)pid;
+			pk[3] = (uint8_t)((stuff ? 0x30 : 0x10) | cc);
+			cc = (cc + 1) & 15u;
+			uint8_t *w = pk + 4;
+			if (stuff) {
+				*w++ = (uint8_t)(stuff - 1);
+				if (stuff > 1) { *w++ = 0; memset(w, 0xff, stuff - 2); w += stuff - 2; }
+			}
+			for (uint64_t i = 0; i < n; i++, done++) w[i] = done < 14 ? head[done] : es[offset[u] + done - 14];
+			at += 188;
+		}
+	}
+	if (ts && continuity) *continuity = cc;
+	return (int64_t)at;
+}

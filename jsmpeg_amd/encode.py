@@ -1,0 +1,235 @@
+"""The MPEG-1 intra encoder on the device: the Python side of C ABI part 8 (include/jsmpeg_hip.h, jsmpeg_hip_encoder_*) and
+the host-side TS mux.  Frames in HBM (a Batch's pool, a Live tick's pictures, any device pointers) or uint8 RGB torch tensors
+-> elementary streams in a device buffer that Batch.attach_device takes as it is.  I pictures only, one quantiser scale per
+picture.  torch is imported only when a tensor is handed in."""
+import ctypes
+
+import numpy as np
+
+from . import batch as _batch
+
+END = 1
+
+SYMBOLS = ("jsmpeg_hip_encoder_create", "jsmpeg_hip_encoder_destroy", "jsmpeg_hip_encoder_encode", "jsmpeg_hip_encoder_encode_rgb",
+           "jsmpeg_hip_encoder_sync", "jsmpeg_hip_encoder_query", "jsmpeg_hip_encoder_es", "jsmpeg_hip_encoder_stream_range",
+           "jsmpeg_hip_encoder_picture_range", "jsmpeg_hip_encoder_read_es", "jsmpeg_hip_encoder_timings", "jsmpeg_hip_ts_mux_host")
+
+
+class EncoderConfig(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("max_pictures", ctypes.c_uint32),
+                ("max_streams", ctypes.c_uint32), ("max_es_bytes", ctypes.c_uint64), ("frame_rate_code", ctypes.c_uint32),
+                ("device", ctypes.c_int32)]
+
+
+_bound = None
+
+
+def lib():
+    """libjsmpeg_hip with the part-8 argtypes set"""
+    global _bound
+    if _bound is None:
+        L = _batch.lib()
+        vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
+        L.jsmpeg_hip_encoder_create.restype = vp
+        L.jsmpeg_hip_encoder_create.argtypes = [ctypes.POINTER(EncoderConfig)]
+        L.jsmpeg_hip_encoder_destroy.restype = None
+        L.jsmpeg_hip_encoder_destroy.argtypes = [vp]
+        L.jsmpeg_hip_encoder_encode.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_encode.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp]
+        L.jsmpeg_hip_encoder_encode_rgb.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_encode_rgb.argtypes = [vp, vp, u32, u32, vp, vp, u32, u32, u32, vp]
+        for name in ("jsmpeg_hip_encoder_sync", "jsmpeg_hip_encoder_query"):
+            getattr(L, name).restype = ctypes.c_int
+            getattr(L, name).argtypes = [vp]
+        L.jsmpeg_hip_encoder_es.restype = vp
+        L.jsmpeg_hip_encoder_es.argtypes = [vp, ctypes.POINTER(u64)]
+        L.jsmpeg_hip_encoder_stream_range.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_stream_range.argtypes = [vp, u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+        L.jsmpeg_hip_encoder_picture_range.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_picture_range.argtypes = [vp, u32, ctypes.POINTER(u64), ctypes.POINTER(u32)]
+        L.jsmpeg_hip_encoder_read_es.restype = ctypes.c_int64
+        L.jsmpeg_hip_encoder_read_es.argtypes = [vp, u32, vp, u64]
+        L.jsmpeg_hip_encoder_timings.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.jsmpeg_hip_ts_mux_host.restype = ctypes.c_int64
+        L.jsmpeg_hip_ts_mux_host.argtypes = [vp, vp, vp, vp, u32, u32, u32, ctypes.POINTER(ctypes.c_uint8), vp, u64]
+        _bound = L
+    return _bound
+
+
+def ts_mux(es, ranges, pts, stream_id=0xE0, pid=0x100, continuity=0):
+    """Host-side TS mux (no device): `es` bytes, ranges = [(offset, bytes)] -- one PES per range -- and pts = seconds per
+    range -> (MPEG-TS bytes as a uint8 array, the continuity counter to hand to the next call)."""
+    L = lib()
+    es = np.ascontiguousarray(np.frombuffer(es, dtype=np.uint8) if isinstance(es, (bytes, bytearray)) else es, dtype=np.uint8)
+    n = len(ranges)
+    if len(pts) != n:
+        raise ValueError("ts_mux: one pts per range")
+    off = np.ascontiguousarray([r[0] for r in ranges], dtype=np.uint64)
+    ln = np.ascontiguousarray([r[1] for r in ranges], dtype=np.uint32)
+    if n and int((off + ln).max()) > es.size:
+        raise ValueError("ts_mux: a range ends behind the bytes")
+    p90 = np.ascontiguousarray([int(round(float(t) * 90000.0)) for t in pts], dtype=np.uint64)
+    cc = ctypes.c_uint8(continuity & 15)
+    need = L.jsmpeg_hip_ts_mux_host(es.ctypes.data, off.ctypes.data, ln.ctypes.data, p90.ctypes.data, n, stream_id, pid, ctypes.byref(cc), None, 0)
+    if need < 0:
+        raise RuntimeError(_batch.last_error())
+    out = np.empty(max(1, need), dtype=np.uint8)
+    got = L.jsmpeg_hip_ts_mux_host(es.ctypes.data, off.ctypes.data, ln.ctypes.data, p90.ctypes.data, n, stream_id, pid, ctypes.byref(cc), out.ctypes.data, need)
+    if got != need:
+        raise RuntimeError(_batch.last_error() or "jsmpeg_hip_ts_mux_host: %d bytes, %d expected" % (got, need))
+    return out[:need], int(cc.value)
+
+
+class Encoder:
+    """Pictures on the device -> MPEG-1 elementary streams (all I pictures) on the device.  A call is a pure enqueue; sync()
+    or any reader settles it."""
+
+    def __init__(self, width, height, max_pictures, max_streams, max_es_bytes, frame_rate_code=0, device=-1):
+        self.L = lib()
+        cfg = EncoderConfig(width, height, max_pictures, max_streams, max_es_bytes, frame_rate_code, device)
+        self.width, self.height = width, height
+        self.coded_width, self.coded_height = (width + 15) & ~15, (height + 15) & ~15
+        self.frame_bytes = self.coded_width * self.coded_height * 3 // 2
+        self.max_pictures, self.max_streams = max_pictures, max_streams
+        self.h = self.L.jsmpeg_hip_encoder_create(ctypes.byref(cfg))
+        if not self.h:
+            raise RuntimeError("jsmpeg_hip_encoder_create: " + _batch.last_error())
+        self.device = device
+        self.count = 0
+        self._continuity = 0
+
+    def _ok(self, rc):
+        if rc < 0:
+            raise RuntimeError(_batch.last_error())
+        return rc
+
+    def close(self):
+        if self.h:
+            self.L.jsmpeg_hip_encoder_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _lists(self, count, streams, qscale):
+        s = None if streams is None else np.ascontiguousarray(streams, dtype=np.uint32)
+        if s is not None and s.shape != (count,):
+            raise ValueError("streams: one stream number per picture")
+        if isinstance(qscale, (int, np.integer)):
+            return s, None, int(qscale)
+        q = np.asarray(qscale)
+        if q.shape != (count,) or (count and (q.min() < 0 or q.max() > 255)):
+            raise ValueError("qscale: an integer or one per picture")
+        return s, np.ascontiguousarray(q, dtype=np.uint8), 0
+
+    def encode(self, frame_ptrs, streams=None, qscale=8, end=True, stream=None):
+        """frame_ptrs: device addresses of Y | Cr | Cb planes of the coded size, one per picture; streams: ascending stream
+        numbers (None: all stream 0); qscale: 1 .. 31, or one per picture; end: close every stream with a sequence end
+        code; stream: the HIP stream to enqueue on -- the one the frames were produced on (ordering is the caller's)."""
+        ptrs = [int(p) if p else 0 for p in frame_ptrs]
+        n = len(ptrs)
+        arr = (ctypes.c_void_p * max(1, n))(*ptrs)
+        s, q, qs = self._lists(n, streams, qscale)
+        self._ok(self.L.jsmpeg_hip_encoder_encode(self.h, arr, None if s is None else s.ctypes.data, None if q is None else q.ctypes.data,
+                                                  n, qs, END if end else 0, stream))
+        self.count = n
+
+    def encode_batch(self, batch, pictures, streams=None, qscale=8, end=True, stream=None):
+        """pictures of a Batch's last decode, straight from its frame pool (the batch is synchronised first; a picture that was
+        not decoded is refused).  streams None: each picture's own stream number, which must then ascend."""
+        batch.sync()
+        infos = [batch.picture_info(int(p)) for p in pictures]
+        for p, info in zip(pictures, infos):
+            if not info.decoded:
+                raise ValueError("encode_batch: picture %d was not decoded" % int(p))
+        if streams is None:
+            streams = [info.stream for info in infos]
+        base = batch.frame_pool_ptr
+        self.encode([base + int(p) * batch.frame_stride for p in pictures], streams, qscale, end, stream)
+
+    def encode_live(self, live, pictures=None, streams=None, qscale=8, end=True, stream=None):
+        """pictures of a Live's last tick (None: all of them, in tick order), from their device_frame pointers.  streams
+        None: the pictures are sorted by their live stream id (stable) and numbered 0, 1, .. in that order"""
+        pics = live.pictures()
+        if pictures is not None:
+            pics = [pics[int(i)] for i in pictures]
+        if streams is None:
+            order = sorted(range(len(pics)), key=lambda i: pics[i].stream)
+            pics = [pics[i] for i in order]
+            ids = sorted({p.stream for p in pics})
+            streams = [ids.index(p.stream) for p in pics]
+        self.encode([p.device_frame for p in pics], streams, qscale, end, stream)
+        return pics
+
+    def encode_tensor(self, x, streams=None, qscale=8, end=True, order="rgb"):
+        """x: a contiguous torch uint8 CUDA tensor [N, 3, H, W] or [N, H, W, 3] of the display size; runs on torch's current
+        stream of the tensor's device"""
+        import torch
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or not x.is_cuda or x.dim() != 4 or not x.is_contiguous():
+            raise ValueError("encode_tensor: a contiguous uint8 CUDA tensor [N, 3, H, W] or [N, H, W, 3] is needed")
+        if tuple(x.shape[1:]) == (3, self.height, self.width):
+            layout = 0
+        elif tuple(x.shape[1:]) == (self.height, self.width, 3):
+            layout = 1
+        else:
+            raise ValueError("encode_tensor: shape %r is neither [N, 3, %d, %d] nor [N, %d, %d, 3]" % (tuple(x.shape), self.height, self.width, self.height, self.width))
+        if str(order).lower() not in ("rgb", "bgr"):
+            raise ValueError("order %r: one of rgb, bgr" % (order,))
+        n = int(x.shape[0])
+        s, q, qs = self._lists(n, streams, qscale)
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        self._ok(self.L.jsmpeg_hip_encoder_encode_rgb(self.h, x.data_ptr() if n else None, layout, 1 if str(order).lower() == "bgr" else 0,
+                                                      None if s is None else s.ctypes.data, None if q is None else q.ctypes.data,
+                                                      n, qs, END if end else 0, st))
+        self.count = n
+        self._keep = x          # the tensor stays alive until the next call
+
+    def sync(self):
+        self._ok(self.L.jsmpeg_hip_encoder_sync(self.h))
+
+    def query(self):
+        """True once the pass in flight has finished on the device; never waits"""
+        return bool(self._ok(self.L.jsmpeg_hip_encoder_query(self.h)))
+
+    def device_es(self):
+        """(device address, total bytes) of the last call's buffer: 16-byte aligned stream begins, 0xff around them"""
+        total = ctypes.c_uint64()
+        p = self.L.jsmpeg_hip_encoder_es(self.h, ctypes.byref(total))
+        if not p:
+            raise RuntimeError(_batch.last_error())
+        return p, int(total.value)
+
+    def stream_range(self, stream):
+        b, e = ctypes.c_uint64(), ctypes.c_uint64()
+        self._ok(self.L.jsmpeg_hip_encoder_stream_range(self.h, stream, ctypes.byref(b), ctypes.byref(e)))
+        return int(b.value), int(e.value)
+
+    def es(self, stream=0):
+        """the stream's bytes, copied to the host"""
+        n = self._ok(self.L.jsmpeg_hip_encoder_read_es(self.h, stream, None, 0))
+        out = np.empty(max(1, n), dtype=np.uint8)
+        self._ok(self.L.jsmpeg_hip_encoder_read_es(self.h, stream, out.ctypes.data, n))
+        return out[:n].tobytes()
+
+    def picture_ranges(self):
+        """[(offset in the device buffer, bytes)] per picture of the last call, from its sequence header on"""
+        out = []
+        for k in range(self.count):
+            o, b = ctypes.c_uint64(), ctypes.c_uint32()
+            self._ok(self.L.jsmpeg_hip_encoder_picture_range(self.h, k, ctypes.byref(o), ctypes.byref(b)))
+            out.append((int(o.value), int(b.value)))
+        return out
+
+    def timings(self):
+        ms = (ctypes.c_float * 4)()
+        self._ok(self.L.jsmpeg_hip_encoder_timings(self.h, ms))
+        return dict(convert_ms=ms[0], measure_ms=ms[1], write_ms=ms[2], total_ms=ms[3])
+
+    def ts_mux(self, es, ranges, pts, stream_id=0xE0, pid=0x100):
+        """ts_mux() with the continuity counter carried from call to call on this object"""
+        out, self._continuity = ts_mux(es, ranges, pts, stream_id, pid, self._continuity)
+        return out

@@ -1,0 +1,189 @@
+"""What the intra encoder (C ABI part 8) costs: ms per call, MEASURED (the tests assert bytes, never times).  Pool frames of a
+decoded batch (bench.py's generator, cfg2: 64 streams x 120 pictures of 1080p) to streams at q = 8, for 64 pictures (the first of
+every stream) and for all 7680: the call's span split by jsmpeg_hip_encoder_timings, the output bytes, the bytes the two passes
+read and write per picture against a plain device copy's rate measured in the same process, and the whole pass of decode alone
+against decode + encode (what a transcode costs).  A third step: Batch.tensor(uint8) -> encode_tensor -> decode, the luma PSNR
+against the first decode.
+
+Every GPU step is a child process of this tool under its own `timeout`; the steps are chained and the tool stops at the first
+one that fails.  The figures go into the bench section of profiles/enc_notes.md (nothing is written for a step that did not
+run).
+    python tools/encode_bench.py [--steps pool64,pool7680,tensor] [--reps 8]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+W, H = 1920, 1080
+STEPS = {"pool64": 300, "pool7680": 420, "tensor": 120}          # seconds each step may take
+
+
+def median(v):
+    return round(float(np.median(v)), 3)
+
+
+def copy_rate(L, nbytes, reps):
+    """GB/s (read + written) of a plain device-to-device copy of nbytes"""
+    import ctypes
+    L.jsmpeg_hip_device_alloc.restype = ctypes.c_void_p
+    L.jsmpeg_hip_device_alloc.argtypes = [ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32]
+    L.jsmpeg_hip_device_copy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+    L.jsmpeg_hip_device_free.argtypes = [ctypes.c_void_p]
+    a, b = L.jsmpeg_hip_device_alloc(nbytes, 0, 1), L.jsmpeg_hip_device_alloc(nbytes, 0, 2)
+    if not a or not b:
+        raise RuntimeError("device_alloc failed")
+    ms = []
+    for r in range(reps + 2):
+        L.jsmpeg_hip_device_synchronize()
+        t0 = time.perf_counter()
+        L.jsmpeg_hip_device_copy(b, a, nbytes)
+        L.jsmpeg_hip_device_synchronize()
+        if r >= 2:
+            ms.append((time.perf_counter() - t0) * 1e3)
+    L.jsmpeg_hip_device_free(a)
+    L.jsmpeg_hip_device_free(b)
+    return 2 * nbytes / (float(np.median(ms)) * 1e-3) / 1e9
+
+
+def step_pool(all_pictures, reps):
+    import bench
+    from jsmpeg_amd import batch as jb
+    from jsmpeg_amd import encode
+    streams = [g[0] for g in bench.generate_streams(0, 64, 120)]
+    total = sum(len(s) for s in streams)
+    with jb.Batch(W, H, 64, 7680 + 8, total + 64 * 64 + 4096, device=0) as b:
+        b.upload(streams)
+        assert b.decode() == 7680
+        infos = b.pictures()
+        if all_pictures:
+            pics = [p for p, i in enumerate(infos) if i.decoded]
+        else:
+            seen, pics = set(), []
+            for p, i in enumerate(infos):
+                if i.decoded and i.stream not in seen:
+                    seen.add(i.stream)
+                    pics.append(p)
+        sn = [infos[p].stream for p in pics]
+        # size the output from a call over the first pictures
+        with encode.Encoder(W, H, 64, 64, 64 << 20, device=0) as probe:
+            probe.encode_batch(b, pics[:64], [0] * 64 if all_pictures else sn[:64], 8)
+            probe.sync()
+            per_picture = probe.device_es()[1] / 64.0
+        cap = int(per_picture * len(pics) * 1.5) + (1 << 20)
+        with encode.Encoder(W, H, len(pics), 64, cap, device=0) as enc:
+            ptrs = [b.frame_pool_ptr + p * b.frame_stride for p in pics]
+            wall, split = [], []
+            for r in range(reps + 2):
+                t0 = time.perf_counter()
+                enc.encode(ptrs, sn, 8)
+                enc.sync()
+                if r >= 2:
+                    wall.append((time.perf_counter() - t0) * 1e3)
+                    split.append(enc.timings())
+            out_bytes = enc.device_es()[1]
+            dec, both = [], []
+            for r in range(reps + 2):
+                t0 = time.perf_counter()
+                b.decode()
+                t1 = time.perf_counter()
+                enc.encode(ptrs, sn, 8)
+                enc.sync()
+                t2 = time.perf_counter()
+                if r >= 2:
+                    dec.append((t1 - t0) * 1e3)
+                    both.append((t2 - t0) * 1e3)
+            rate = copy_rate(b.L, 1 << 30, reps)
+            frame = b.frame_stride
+            mbs = (W + 15) // 16 * ((H + 15) // 16)
+            moved = 2 * frame + 2 * 12 * mbs + 2 * out_bytes / len(pics)       # both passes read the frame; records out and in; clear + write
+            total_ms = median([s["total_ms"] for s in split])
+            return dict(step="pool7680" if all_pictures else "pool64", pictures=len(pics), streams=len(set(sn)), q=8,
+                        wall_ms=median(wall), convert_ms=median([s["convert_ms"] for s in split]), measure_scan_ms=median([s["measure_ms"] for s in split]),
+                        write_ms=median([s["write_ms"] for s in split]), total_ms=total_ms, output_bytes=int(out_bytes),
+                        output_bytes_per_picture=round(out_bytes / len(pics)), moved_bytes_per_picture=round(moved),
+                        copy_GBps=round(rate, 1), copy_bound_ms=round(moved * len(pics) / (rate * 1e9) * 1e3, 3),
+                        ratio_to_copy_bound=round(total_ms / (moved * len(pics) / (rate * 1e9) * 1e3), 2),
+                        decode_alone_wall_ms=median(dec), decode_then_encode_wall_ms=median(both))
+
+
+def step_tensor():
+    import torch
+    import enc_inputs as ei
+    from jsmpeg_amd import batch as jb
+    from jsmpeg_amd import build, cabi, encode
+    es = np.fromfile(os.path.join(ROOT, "tests", "golden", "enc_pan_176x144.m1v"), dtype=np.uint8)
+    oracle = build.build_oracle()
+    first, _, _ = cabi.decode_stream(oracle, es, keep="planes")
+    frames = [ei.frame_of(*f) for f in first]
+    out = dict(step="tensor", content="enc_pan_176x144", pictures=len(frames))
+    with jb.Batch(176, 144, 1, 16, 1 << 20, device=0) as b, encode.Encoder(176, 144, 16, 1, 4 << 20, device=0) as enc:
+        b.upload([es])
+        b.decode()
+        x = b.tensor(dtype=torch.uint8)
+        for q in (2, 8, 31):
+            enc.encode_tensor(x, qscale=q)
+            dec, _, _ = cabi.decode_stream(oracle, np.frombuffer(enc.es(0), dtype=np.uint8), keep="planes")
+            out["psnr_q%d" % q] = round(ei.psnr(*ei.luma_sse(dec, frames, 176, 144)), 2)
+    return out
+
+
+def notes(results):
+    lines = ["## Cost on the MI355X (measured by tools/encode_bench.py)", ""]
+    for r in results:
+        if r["step"].startswith("pool"):
+            lines += ["**%d pictures of 1080p into %d streams, q = %d, frames from a batch's pool** (cfg2 content)." % (r["pictures"], r["streams"], r["q"]), "",
+                      "| | ms |", "|---|---|",
+                      "| call + sync, host clock | %.3f |" % r["wall_ms"],
+                      "| timings: convert | %.3f |" % r["convert_ms"],
+                      "| timings: measure + scan | %.3f |" % r["measure_scan_ms"],
+                      "| timings: write | %.3f |" % r["write_ms"],
+                      "| timings: total | %.3f |" % r["total_ms"],
+                      "| decode alone (whole pass, host clock) | %.3f |" % r["decode_alone_wall_ms"],
+                      "| decode, then encode | %.3f |" % r["decode_then_encode_wall_ms"], "",
+                      "Output %d bytes (%d per picture).  The two passes move %d bytes per picture (the frame read twice, 12 bytes per macroblock"
+                      % (r["output_bytes"], r["output_bytes_per_picture"], r["moved_bytes_per_picture"]),
+                      "out and in, the output cleared and written); a plain device copy ran at %.1f GB/s in the same process, which would move"
+                      % r["copy_GBps"],
+                      "them in %.3f ms: the call takes %.2f times that." % (r["copy_bound_ms"], r["ratio_to_copy_bound"]), ""]
+        else:
+            lines += ["**Tensor round trip** (`Batch.tensor(uint8)` -> `encode_tensor` -> decode, %s, %d pictures): luma PSNR against the first decode "
+                      % (r["content"], r["pictures"]) + ", ".join("%.2f dB at q = %s" % (v, k[6:]) for k, v in r.items() if k.startswith("psnr_q")) + ".", ""]
+    return "\n".join(lines)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", default="pool64,pool7680,tensor")
+    ap.add_argument("--reps", type=int, default=8)
+    ap.add_argument("--child")
+    a = ap.parse_args()
+    if a.child:
+        r = step_tensor() if a.child == "tensor" else step_pool(a.child == "pool7680", a.reps)
+        print("RESULT " + json.dumps(r), flush=True)
+        return 0
+    results = []
+    for step in a.steps.split(","):
+        cmd = ["timeout", "-k", "10", str(STEPS[step]), sys.executable, os.path.abspath(__file__), "--child", step, "--reps", str(a.reps)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+        if p.returncode != 0 or not line:
+            print("step %s failed (exit status %d); stopping here\n%s" % (step, p.returncode, p.stdout[-3000:]), flush=True)
+            break
+        results.append(json.loads(line[-1][7:]))
+        print(line[-1][7:], flush=True)
+    if results:
+        from enc_quality import NOTES, replace_section
+        replace_section(NOTES, "bench", notes(results))
+    return 0 if len(results) == len(a.steps.split(",")) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
