@@ -781,15 +781,19 @@ int jsmpeg_hip_live_render_tensor_latest(jsmpeg_hip_live_t *l, const uint32_t *s
                                          uint8_t *have);
 
 /* ------------------------------------------------------------------ part 8
- * The way back: an MPEG-1 INTRA ENCODER on the device.  Frames in HBM (a pool slot, a live picture's device_frame, the caller's
+ * The way back: an MPEG-1 ENCODER on the device, I pictures and -- with a GOP, jsmpeg_hip_encoder_set_gop -- I + P.  Frames in HBM (a pool slot, a live picture's device_frame, the caller's
  * own planes) or RGB tensors -> elementary streams that a jsmpeg player, the reference decoder and parts 2 and 5 of this header
- * read.  I pictures only, one quantiser scale per picture, the default intra matrix, one slice per macroblock row; the integer
- * transform, the quantiser and the colour conversion are stated exactly in jsmpeg_amd/csrc/enc_block.h.  EVERY picture carries
- * its own sequence and GOP header in front (20 bytes): every picture is a joining point for a viewer and a unit for
+ * read.  One quantiser scale per picture, the default matrices, one slice per macroblock row; the integer transform, the
+ * quantiser and the colour conversion are stated exactly in jsmpeg_amd/csrc/enc_block.h, motion search, mode decision and the
+ * closed loop in jsmpeg_amd/csrc/enc_motion.h.  EVERY I picture carries its own sequence and GOP header in front (20 bytes):
+ * every I picture -- with gop 1, the default, every picture -- is a joining point for a viewer and a unit for
  * jsmpeg_hip_split_gops.  Streams lie in the output from 16-byte aligned begins with 0xff in front of the first, between them
  * and 256 bytes behind the last: the buffer can be handed to jsmpeg_hip_batch_attach_device as it is.
- * OUT OF SCOPE: P pictures (they need a closed loop), rate control, custom matrices, a Node binding, resizing of YCbCr (resize
- * the RGB tensor).
+ * P CHAINS DO NOT CROSS CALLS: every stream of a call begins with an I picture, whatever the call before ended with (a live
+ * stream that goes on pays one I picture per call).  Batch STREAMS, not pictures: a P picture waits for the picture before it,
+ * so a call with one stream runs one picture at a time on the device.
+ * OUT OF SCOPE: B pictures, rate control and quantiser changes inside a picture, custom matrices, P chains across calls, vectors
+ * beyond +-15 pels, a Node binding, resizing of YCbCr (resize the RGB tensor).
  * A pass is a PURE ENQUEUE on hip_stream, like jsmpeg_hip_batch_enqueue: every size and offset is worked out on the device; the
  * host waits in jsmpeg_hip_encoder_sync and the readers only (they settle the pass first).  One pass at a time per handle: a
  * second encode before the first is settled is refused.  ORDERING AGAINST THE PRODUCER OF THE FRAMES IS THE CALLER'S: pass the
@@ -826,7 +830,20 @@ int jsmpeg_hip_encoder_stream_range(jsmpeg_hip_encoder_t *enc, uint32_t stream, 
 int jsmpeg_hip_encoder_picture_range(jsmpeg_hip_encoder_t *enc, uint32_t k, uint64_t *offset, uint32_t *bytes);   /* from its sequence header on */
 /* the stream's bytes to the host (at most cap; host NULL: none); returns the stream's length or < 0 */
 int64_t jsmpeg_hip_encoder_read_es(jsmpeg_hip_encoder_t *enc, uint32_t stream, void *host, uint64_t cap);
-int jsmpeg_hip_encoder_timings(jsmpeg_hip_encoder_t *enc, float out_ms[4]);      /* convert, measure + scan, write, total */
+int jsmpeg_hip_encoder_timings(jsmpeg_hip_encoder_t *enc, float out_ms[4]);      /* convert, measure + scan (a GOP's level loop included), write, total */
+/* gop 1 (the default): today's streams, byte for byte.  gop N > 1: in every stream of a call the pictures whose ordinal in the
+ * stream is a multiple of N are I pictures with the sequence + GOP header in front, the others are P pictures (picture header
+ * only, full_pel_forward_vector 0, temporal reference = the ordinal in the GOP) predicted from the encoder's OWN reconstruction
+ * of the picture before -- exactly the frame a decoder holds.  jsmpeg_hip_encoder_picture_range of a P picture begins at its
+ * picture start code.  search_range: full-pel radius 0 .. 15; 0 = zero vectors only, no half-pel step (conditional
+ * replenishment); forward_f_code is 1 up to 7 and 2 above.  Refused while a pass is in flight, for gop 0, gop > 1024,
+ * search_range > 15.  The stores only a GOP needs -- a reconstructed frame per picture of a call, the macroblocks' motion
+ * records -- are allocated by the first call that asks for gop > 1. */
+int jsmpeg_hip_encoder_set_gop(jsmpeg_hip_encoder_t *enc, uint32_t gop, uint32_t search_range);
+/* device pointer of picture k's reconstruction in the last call (Y | Cr | Cb, coded size); NULL with a message when gop is 1 */
+const void *jsmpeg_hip_encoder_recon(jsmpeg_hip_encoder_t *enc, uint32_t k);
+/* macroblocks of picture k by kind: intra, predicted + coded, predicted not coded, skipped */
+int jsmpeg_hip_encoder_picture_stats(jsmpeg_hip_encoder_t *enc, uint32_t k, uint32_t out[4]);
 
 /* Host-side TS mux (plain C, no device; a jsmpeg player takes TS): one PES per unit (a picture's range in `es`) with its PTS,
  * the payload in 184-byte pieces, the unit's last packet padded by adaptation-field stuffing -- what the reference's demuxer

@@ -3,9 +3,10 @@
  * and the CPU simulator (tests/sim/sim_encode.cpp) share.  Host + device; on the CPU an atomic OR is a plain OR and a lane's
  * slot of LDS is a local array, nothing else differs.  tests/enc_ref.py restates every formula below in numpy.
  *
- * I pictures only, one quantiser scale per picture, the default intra matrix, one slice per macroblock row.  OUT OF SCOPE
- * (say so to whoever asks): P pictures (they need a closed loop: the encoder's reference must be the decoder's
- * reconstruction), rate control, custom matrices, a Node binding, resizing of YCbCr (resize the RGB tensor with torch).
+ * I pictures here, one quantiser scale per picture, the default intra matrix, one slice per macroblock row; P pictures and the
+ * closed loop they need (the encoder's reference must be the decoder's reconstruction) are enc_motion.h's, built on what is
+ * below.  OUT OF SCOPE (say so to whoever asks): B pictures, rate control, custom matrices, a Node binding, resizing of YCbCr
+ * (resize the RGB tensor with torch).
  *
  * FORWARD DCT, exactly:  with C[k][n] = round(2^14 * c_k * cos((2n + 1) k pi / 16)), c_0 = sqrt(1/8), c_k = 1/2
  * (jm_enc_make_const below, 16-bit signed), and the block's pixels x[y][n] in 0 .. 255 (MPEG-1 intra blocks are not level-shifted),
@@ -15,6 +16,8 @@
  * c8 is EIGHT TIMES the orthonormal DCT coefficient (2^28 / 8 = 2^25): three fractional bits go into the quantiser.
  * Bounds (tools/fdct_bounds.py adds up the table, as tools/idct_bounds.py does for the inverse): sum_n |C[k][n]| <= 46344,
  * so |t| <= 255 * 46344 = 11 817 720 < 2^24 and |a| <= 46344 * 11 817 720 < 2^39: int32 and int64 hold them with room.
+ * The same sums bound the residual of a predicted block, x in -255 .. 255 (enc_motion.h; tools/fdct_bounds.py --signed): there
+ * |t| reaches 11 817 720 itself, the high and low halves of t stay within +-2886 and 0 .. 4095, their sums below 2^28.
  *
  * QUANTISER, for the reference's dequantiser (mpeg1.c decode_block, oracle/mpeg1_oracle.c), W = the default intra matrix:
  *     DC level = clamp((c8[0][0] + 32) >> 6, 0, 255)             round(dc / 8)

@@ -13,11 +13,21 @@
  *   k_enc_clear          zeroes the total (the write ORs into it), 0xff behind it
  *   k_enc_write          a macroblock per lane again: transform, quantise, write bits; the headers by the lanes that begin them
  * The host waits in jsmpeg_hip_encoder_sync and the readers only.
+ *
+ * With a GOP (jsmpeg_hip_encoder_set_gop, gop > 1; the rules: enc_motion.h) the measure step becomes a loop over LEVELS,
+ * level = a picture's ordinal in its stream mod gop: all pictures of a level, of every stream, in one launch each of
+ *   k_enc_motion         P levels: a wavefront per macroblock searches the reconstruction of the picture before
+ *   k_enc_measure_p      a macroblock per lane: mode, residual, quantise, count, reconstruct into the per-picture store
+ * then k_enc_scan_slices_p / k_enc_scan_pictures_p (the neighbour-dependent codes, the kinds), place and clear as above, and
+ * ONE k_enc_write_p over every macroblock of the call: it recomputes a macroblock's levels from the source and the kept
+ * reconstruction of the picture before.  The host builds the level lists from the stream numbers; it never reads the device.
  */
 #include "engine_internal.h"
 #include "enc_block.h"
+#include "enc_motion.h"
 
 #define JM_ENC_LANES 64
+#define JM_ENC_MOTION_WAVES 4    /* macroblocks (one wavefront each) of a k_enc_motion workgroup */
 
 struct JmEncPic {
 	const uint8_t *frame;    /* Y | Cr | Cb of the coded size */
@@ -156,6 +166,159 @@ __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_write(JmEncArgs a) {
 	jm_enc_flush(bw);
 }
 
+/* ------------------------------------------------------------------ kernels of a GOP (gop > 1) */
+
+struct JmEncPArgs {
+	uint8_t *recon;              /* [count] reconstructed frames, Y | Cr | Cb of the coded size */
+	uint64_t frame_bytes;
+	JmEncPMb *pmb;               /* [count][mbh][mbw] */
+	const JmEncPTables *ptables;
+	const uint32_t *list;        /* the call's picture numbers, sorted by level */
+	uint32_t *slice_kinds;       /* [count][mbh][4] */
+	uint32_t *stats;             /* [count][4] */
+	uint32_t gop, search, r_size;
+};
+
+static __device__ __forceinline__ uint64_t enc_wave_min(uint64_t v) {
+#pragma unroll
+	for (int o = 32; o; o >>= 1) { const uint64_t t = __shfl_xor((unsigned long long)v, o); v = t < v ? t : v; }
+	return v;
+}
+static __device__ __forceinline__ uint32_t enc_wave_sum(uint32_t v) {
+#pragma unroll
+	for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+	return v;
+}
+
+/* A WAVEFRONT PER MACROBLOCK of the n pictures list[first ..]: the window and the macroblock staged in LDS, a lane per item
+ * (dy, four dx sharing their dwords: 64 packed SADs per candidate, the unaligned dwords by v_alignbyte with constant shifts),
+ * a wavefront min-reduction of the packed key; then the eight half-pel neighbours on eight lanes each, and the activity. */
+__global__ void __launch_bounds__(64 * JM_ENC_MOTION_WAVES) k_enc_motion(JmEncArgs a, JmEncPArgs p, uint32_t first, uint32_t n) {
+	__shared__ uint32_t s_win[JM_ENC_MOTION_WAVES][JM_ENCP_WIN_WORDS];
+	__shared__ uint32_t s_cur[JM_ENC_MOTION_WAVES][64];
+	const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, mbs = a.mbw * a.mbh;
+	const uint64_t total = (uint64_t)n * mbs;
+	uint64_t g = (uint64_t)blockIdx.x * JM_ENC_MOTION_WAVES + wave;
+	const bool live = g < total;
+	if (!live) g = total - 1;                  /* a wavefront without a macroblock repeats the last one and stores nothing */
+	const uint32_t k = p.list[first + (uint32_t)(g / mbs)], m = (uint32_t)(g % mbs), row = m / a.mbw, col = m % a.mbw;
+	JM_GLOBAL const uint8_t *cur = (JM_GLOBAL const uint8_t *)a.pics[k].frame + ((size_t)row * 16u * a.cw + (size_t)col * 16u);
+	JM_GLOBAL const uint8_t *ref = (JM_GLOBAL const uint8_t *)p.recon + (size_t)(k - 1) * p.frame_bytes;   /* a P picture is never a call's first */
+	uint32_t *win = s_win[wave], *mb = s_cur[wave];
+	const uint32_t R = p.search;
+	/* the rows a search of radius R and its half-pel step read: 15 - R .. 32 + R */
+	for (uint32_t i = (15u - R) * JM_ENCP_WIN_DW + lane; i < (33u + R) * JM_ENCP_WIN_DW; i += 64u) win[i] = jm_encp_window_dword(ref, a.cw, a.ch, col, row, i);
+	mb[lane] = *reinterpret_cast<JM_GLOBAL const uint32_t *>(cur + (size_t)(lane >> 2) * a.cw + (size_t)(lane & 3u) * 4u);
+	__syncthreads();
+
+	const JmEncSearch shape = jm_encp_search_shape(R);
+	uint64_t best = JM_ENCP_NO_KEY;
+	for (uint32_t it = lane; it < shape.items; it += 64u) {
+		const uint64_t key = jm_encp_search_item(win, mb, R, shape, it, a.cw, a.ch, col, row);
+		best = key < best ? key : best;
+	}
+	best = enc_wave_min(best);
+	uint32_t sad = jm_encp_key_sad(best);
+	int mvh = 2 * jm_encp_key_dx(best), mvv = 2 * jm_encp_key_dy(best);
+	if (R) {
+		int hh, hv;
+		jm_encp_half_step(lane >> 3, &hh, &hv);
+		const int mh = mvh + hh, mv = mvv + hv;
+		const bool ok = jm_encp_half_ok(a.cw, a.ch, col, row, mh, mv, p.r_size);
+		uint32_t part = ok ? jm_encp_halfpel_part(win, mb, mh, mv, lane & 7u) : 0u;
+		part += __shfl_xor(part, 1); part += __shfl_xor(part, 2); part += __shfl_xor(part, 4);
+		const uint64_t hk = enc_wave_min(ok ? ((uint64_t)part << 3) | (lane >> 3) : JM_ENCP_NO_KEY);
+		if (hk != JM_ENCP_NO_KEY && (uint32_t)(hk >> 3) < sad) {
+			jm_encp_half_step((uint32_t)(hk & 7u), &hh, &hv);
+			sad = (uint32_t)(hk >> 3); mvh += hh; mvv += hv;
+		}
+	}
+	const uint32_t mean = (enc_wave_sum(jm_encp_sad4(mb[lane], 0u, 0u)) + 128u) >> 8;
+	const uint32_t activity = enc_wave_sum(jm_encp_sad4(mb[lane], mean * 0x01010101u, 0u));
+	if (live && lane == 0) p.pmb[(size_t)k * mbs + m].info = jm_encp_decide(sad, activity, mvh, mvv);
+}
+
+/* the macroblock of lane g of the n pictures list[first ..] */
+struct EncPLane { uint32_t k, m, row, col; };
+static __device__ __forceinline__ EncPLane encp_lane(const JmEncArgs &a, const JmEncPArgs &p, uint32_t first, uint64_t g) {
+	EncPLane l;
+	const uint32_t mbs = a.mbw * a.mbh;
+	l.k = p.list[first + (uint32_t)(g / mbs)]; l.m = (uint32_t)(g % mbs); l.row = l.m / a.mbw; l.col = l.m % a.mbw;
+	return l;
+}
+
+__global__ void __launch_bounds__(JM_ENC_LANES) k_enc_measure_p(JmEncArgs a, JmEncPArgs p, uint32_t first, uint32_t n) {
+	__shared__ int16_t zz[64 * JM_ENC_LANES];
+	__shared__ uint32_t pp[16 * JM_ENC_LANES];
+	const uint64_t g = (uint64_t)blockIdx.x * JM_ENC_LANES + threadIdx.x;
+	if (g >= (uint64_t)n * a.mbw * a.mbh) return;
+	const EncPLane l = encp_lane(a, p, first, g);
+	const JmEncPic pic = a.pics[l.k];
+	JmEncPMb *rec = p.pmb + ((size_t)l.k * a.mbw * a.mbh + l.m);
+	JM_GLOBAL uint8_t *recon = (JM_GLOBAL uint8_t *)p.recon + (size_t)l.k * p.frame_bytes;
+	const uint32_t found = (pic.ordinal % p.gop) ? rec->info : 0u;
+	JmEncPMb out;
+	out.dc[0] = out.dc[1] = 0; out.inh = 0; out.pred = 0;
+	if (found & 1u) {
+		out.bits = jm_encp_measure_inter((JM_GLOBAL const uint8_t *)pic.frame, recon - p.frame_bytes, recon, a.cw, a.ch, a.mbw, l.col, l.row,
+		                                 jm_encp_mvh(found), jm_encp_mvv(found), pic.q, a.tables, p.ptables, zz + threadIdx.x, JM_ENC_LANES,
+		                                 pp + threadIdx.x, JM_ENC_LANES, &out.info);
+	} else {
+		uint64_t dcs;
+		out.bits = jm_encp_measure_intra((JM_GLOBAL const uint8_t *)pic.frame, recon, a.cw, a.ch, l.col, l.row, pic.q, a.tables, zz + threadIdx.x, JM_ENC_LANES, &dcs);
+		out.dc[0] = (uint32_t)dcs; out.dc[1] = (uint32_t)(dcs >> 32);
+		out.info = jm_encp_info(JM_ENCP_INTRA, false, 0, 0, 0);
+	}
+	*rec = out;
+}
+
+__global__ void __launch_bounds__(64) k_enc_scan_slices_p(JmEncArgs a, JmEncPArgs p) {
+	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+	if (s >= a.count * a.mbh) return;
+	uint32_t kinds[4] = { 0, 0, 0, 0 };
+	a.slice[s] = jm_encp_scan_slice(p.pmb + (size_t)s * a.mbw, a.mbw, (a.pics[s / a.mbh].ordinal % p.gop) != 0, p.r_size, a.tables, p.ptables, kinds);
+	for (int i = 0; i < 4; i++) p.slice_kinds[(size_t)s * 4 + i] = kinds[i];
+}
+
+__global__ void __launch_bounds__(64) k_enc_scan_pictures_p(JmEncArgs a, JmEncPArgs p) {
+	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= a.count) return;
+	enc_pic_bytes(a)[k] = jm_encp_scan_picture(a.slice + (size_t)k * a.mbh, a.mbh, (a.pics[k].ordinal % p.gop) ? JM_ENC_P_HEAD_BYTES : JM_ENC_PIC_HEAD_BYTES);
+	for (int i = 0; i < 4; i++) {
+		uint32_t sum = 0;
+		for (uint32_t r = 0; r < a.mbh; r++) sum += p.slice_kinds[((size_t)k * a.mbh + r) * 4 + i];
+		p.stats[(size_t)k * 4 + i] = sum;
+	}
+}
+
+__global__ void __launch_bounds__(JM_ENC_LANES) k_enc_write_p(JmEncArgs a, JmEncPArgs p) {
+	__shared__ int16_t zz[64 * JM_ENC_LANES];
+	__shared__ uint32_t pp[16 * JM_ENC_LANES];
+	if (a.result[1]) return;
+	const uint64_t g = (uint64_t)blockIdx.x * JM_ENC_LANES + threadIdx.x;
+	if (g >= (uint64_t)a.count * a.mbw * a.mbh) return;
+	const uint32_t mbs = a.mbw * a.mbh, k = (uint32_t)(g / mbs), m = (uint32_t)(g % mbs), row = m / a.mbw, col = m % a.mbw;
+	const JmEncPic pic = a.pics[k];
+	const bool p_picture = (pic.ordinal % p.gop) != 0;
+	const uint64_t pic_at = enc_pic_off(a)[k], slice_at = pic_at + a.slice[(size_t)k * a.mbh + row];
+	if (col == 0) {
+		jm_enc_put_slice_header(a.words, slice_at, row, pic.q);
+		if (row == 0) {
+			if (p_picture) jm_encp_put_picture_header(a.words, pic_at, pic.ordinal % p.gop, p.r_size);
+			else jm_enc_put_picture_headers(a.words, pic_at, a.width, a.height, a.frame_rate_code, pic.ordinal);
+			if (pic.last) jm_enc_put_stream_tail(a.words, pic_at + enc_pic_bytes(a)[k], a.end != 0);
+			if (k == 0)
+				for (uint32_t i = 0; i < JM_ENC_LEAD_GAP / 4; i++) jm_enc_or(a.words + i, 0xffffffffu);
+		}
+	}
+	const JmEncPMb rec = p.pmb[g];
+	JmEncBits bw = jm_enc_bits_at(a.words, slice_at * 8u + rec.bits);
+	JM_GLOBAL const uint8_t *ref = (JM_GLOBAL const uint8_t *)p.recon + (size_t)(p_picture ? k - 1 : k) * p.frame_bytes;
+	jm_encp_write(rec, (JM_GLOBAL const uint8_t *)pic.frame, ref, a.cw, a.ch, col, row, p_picture, p.r_size, pic.q, a.tables, p.ptables, zz + threadIdx.x, JM_ENC_LANES,
+	              pp + threadIdx.x, JM_ENC_LANES, bw);
+	jm_enc_flush(bw);
+}
+
 /* ------------------------------------------------------------------ the handle */
 
 struct jsmpeg_hip_encoder_t {
@@ -174,13 +337,24 @@ struct jsmpeg_hip_encoder_t {
 	hipEvent_t ev[4], ev_done;
 	bool pending, valid, have_pass;
 	uint32_t count;
+	/* a GOP (jsmpeg_hip_encoder_set_gop); the stores are allocated by the first call that asks for gop > 1 */
+	uint32_t gop, search;
+	uint8_t *d_recon;                /* a reconstructed frame per picture of a call */
+	JmEncPMb *d_pmb;
+	JmEncPTables *d_ptables;
+	uint32_t *d_list, *h_list;       /* the pictures by level; h_list: pinned */
+	uint32_t *d_slice_kinds, *d_stats, *h_stats;   /* h_stats: pinned */
+	bool gop_ready;                  /* all of the stores above are there */
+	bool pass_gop;                   /* the last call ran with gop > 1 */
 };
 
+static void enc_free_gop(jsmpeg_hip_encoder_t *e);
 static void enc_free(jsmpeg_hip_encoder_t *e) {
 	if (!e) return;
 	hipSetDevice(e->device);
 	if (e->pending) hipEventSynchronize(e->ev_done);
 	hipFree(e->d_tables); hipFree(e->d_pics); hipFree(e->d_mb); hipFree(e->d_slice); hipFree(e->d_result); hipFree(e->d_es); hipFree(e->d_store);
+	enc_free_gop(e);
 	if (e->h_pics) hipHostFree(e->h_pics);
 	if (e->h_result) hipHostFree(e->h_result);
 	for (hipEvent_t &v : e->ev) if (v) hipEventDestroy(v);
@@ -231,6 +405,7 @@ extern "C" jsmpeg_hip_encoder_t *jsmpeg_hip_encoder_create(const jsmpeg_hip_enco
 	e->mbw = (uint32_t)(config->width + 15) >> 4; e->mbh = (uint32_t)(config->height + 15) >> 4;
 	e->cw = e->mbw * 16; e->ch = e->mbh * 16;
 	e->frame_bytes = (uint64_t)e->cw * e->ch * 3 / 2;
+	e->gop = 1; e->search = 0;
 	if (enc_alloc(e) != 0) { enc_free(e); return nullptr; }
 	return e;
 }
@@ -249,6 +424,79 @@ static int enc_settle(jsmpeg_hip_encoder_t *e) {
 		            (unsigned long long)e->h_result[0], (unsigned long long)e->cfg.max_es_bytes);
 	}
 	e->valid = true;
+	return 0;
+}
+
+static void enc_free_gop(jsmpeg_hip_encoder_t *e) {
+	hipFree(e->d_recon); hipFree(e->d_pmb); hipFree(e->d_ptables); hipFree(e->d_list); hipFree(e->d_slice_kinds); hipFree(e->d_stats);
+	if (e->h_list) hipHostFree(e->h_list);
+	if (e->h_stats) hipHostFree(e->h_stats);
+	e->d_recon = nullptr; e->d_pmb = nullptr; e->d_ptables = nullptr; e->d_list = nullptr; e->d_slice_kinds = nullptr; e->d_stats = nullptr;
+	e->h_list = nullptr; e->h_stats = nullptr;
+	e->gop_ready = false;
+}
+
+/* the stores only a GOP needs; the caller frees what a failure leaves behind (enc_free_gop) */
+static int enc_alloc_gop(jsmpeg_hip_encoder_t *e) {
+	static const JmEncPTables ptables = jm_encp_make_tables();
+	const size_t mbs = (size_t)e->mbw * e->mbh, np = e->cfg.max_pictures;
+	HIP_TRY(hipSetDevice(e->device));
+	HIP_TRY(jm_malloc(&e->d_ptables, sizeof(JmEncPTables)));
+	HIP_TRY(hipMemcpy(e->d_ptables, &ptables, sizeof(JmEncPTables), hipMemcpyHostToDevice));
+	HIP_TRY(jm_malloc(&e->d_recon, (size_t)e->frame_bytes * np + 16));      /* + 16: jm_encp_predict8 reads whole dwords */
+	HIP_TRY(jm_malloc(&e->d_pmb, sizeof(JmEncPMb) * mbs * np));
+	HIP_TRY(jm_malloc(&e->d_list, sizeof(uint32_t) * np));
+	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_list), sizeof(uint32_t) * np, hipHostMallocDefault));
+	HIP_TRY(jm_malloc(&e->d_slice_kinds, sizeof(uint32_t) * 4 * e->mbh * np));
+	HIP_TRY(jm_malloc(&e->d_stats, sizeof(uint32_t) * 4 * np));
+	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_stats), sizeof(uint32_t) * 4 * np, hipHostMallocDefault));
+	e->gop_ready = true;
+	return 0;
+}
+
+extern "C" int jsmpeg_hip_encoder_set_gop(jsmpeg_hip_encoder_t *e, uint32_t gop, uint32_t search_range) {
+	g_err[0] = 0;
+	if (!e) return fail("encoder: NULL handle");
+	if (e->pending) return fail("encoder: an encode is in flight: jsmpeg_hip_encoder_sync (or a reader) settles it first");
+	if (gop < 1 || gop > 1024) return fail("encoder: gop %u, must be 1 .. 1024", gop);
+	if (search_range > JM_ENC_MAX_SEARCH) return fail("encoder: search_range %u, must be 0 .. %u", search_range, JM_ENC_MAX_SEARCH);
+	if (gop > 1 && !e->gop_ready && enc_alloc_gop(e) != 0) { enc_free_gop(e); return -1; }     /* gop and search_range stay as they were */
+	e->gop = gop; e->search = search_range;
+	return 0;
+}
+
+/* the gop > 1 pass between ev[1] and ev[3]; `a` is complete */
+static int enc_run_gop(jsmpeg_hip_encoder_t *e, const JmEncArgs &a, uint32_t count, hipStream_t st) {
+	JmEncPArgs p;
+	p.recon = e->d_recon; p.frame_bytes = e->frame_bytes; p.pmb = e->d_pmb; p.ptables = e->d_ptables; p.list = e->d_list;
+	p.slice_kinds = e->d_slice_kinds; p.stats = e->d_stats;
+	p.gop = e->gop; p.search = e->search; p.r_size = jm_encp_r_size(e->search);
+	/* the pictures by level = ordinal mod gop: a counting sort of what the host already has */
+	uint32_t levels = 0;
+	for (uint32_t k = 0; k < count; k++) levels = std::max(levels, e->h_pics[k].ordinal % e->gop + 1);
+	std::vector<uint32_t> begin(levels + 1, 0);
+	for (uint32_t k = 0; k < count; k++) begin[e->h_pics[k].ordinal % e->gop + 1]++;
+	for (uint32_t l = 0; l < levels; l++) begin[l + 1] += begin[l];
+	{
+		std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
+		for (uint32_t k = 0; k < count; k++) e->h_list[at[e->h_pics[k].ordinal % e->gop]++] = k;
+	}
+	HIP_TRY(hipMemcpyAsync(e->d_list, e->h_list, sizeof(uint32_t) * count, hipMemcpyHostToDevice, st));
+	const uint64_t mbs = (uint64_t)e->mbw * e->mbh;
+	for (uint32_t l = 0; l < levels; l++) {
+		const uint32_t first = begin[l], n = begin[l + 1] - begin[l];
+		if (!n) continue;
+		if (l) k_enc_motion<<<dim3((uint32_t)((n * mbs + JM_ENC_MOTION_WAVES - 1) / JM_ENC_MOTION_WAVES)), dim3(64 * JM_ENC_MOTION_WAVES), 0, st>>>(a, p, first, n);
+		k_enc_measure_p<<<dim3((uint32_t)((n * mbs + JM_ENC_LANES - 1) / JM_ENC_LANES)), dim3(JM_ENC_LANES), 0, st>>>(a, p, first, n);
+	}
+	k_enc_scan_slices_p<<<dim3((count * e->mbh + 63) / 64), dim3(64), 0, st>>>(a, p);
+	k_enc_scan_pictures_p<<<dim3((count + 63) / 64), dim3(64), 0, st>>>(a, p);
+	k_enc_place<<<dim3(1), dim3(256), 0, st>>>(a);
+	HIP_TRY(hipEventRecord(e->ev[2], st));
+	k_enc_clear<<<dim3(1024), dim3(256), 0, st>>>(a);
+	k_enc_write_p<<<dim3((uint32_t)((count * mbs + JM_ENC_LANES - 1) / JM_ENC_LANES)), dim3(JM_ENC_LANES), 0, st>>>(a, p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(e->h_stats, e->d_stats, sizeof(uint32_t) * 4 * count, hipMemcpyDeviceToHost, st));
 	return 0;
 }
 
@@ -301,14 +549,19 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 		k_enc_rgb<<<dim3((uint32_t)((quads + 255) / 256)), dim3(256), 0, st>>>(a, (const uint8_t *)dev_rgb, layout, order);
 	}
 	HIP_TRY(hipEventRecord(e->ev[1], st));
-	k_enc_measure<<<dim3(mb_grid), dim3(JM_ENC_LANES), 0, st>>>(a);
-	k_enc_scan_slices<<<dim3((count * e->mbh + 63) / 64), dim3(64), 0, st>>>(a);
-	k_enc_scan_pictures<<<dim3((count + 63) / 64), dim3(64), 0, st>>>(a);
-	k_enc_place<<<dim3(1), dim3(256), 0, st>>>(a);
-	HIP_TRY(hipEventRecord(e->ev[2], st));
-	k_enc_clear<<<dim3(1024), dim3(256), 0, st>>>(a);
-	k_enc_write<<<dim3(mb_grid), dim3(JM_ENC_LANES), 0, st>>>(a);
-	HIP_TRY(hipGetLastError());
+	e->pass_gop = e->gop > 1;
+	if (e->pass_gop) {
+		if (enc_run_gop(e, a, count, st) != 0) return -1;
+	} else {
+		k_enc_measure<<<dim3(mb_grid), dim3(JM_ENC_LANES), 0, st>>>(a);
+		k_enc_scan_slices<<<dim3((count * e->mbh + 63) / 64), dim3(64), 0, st>>>(a);
+		k_enc_scan_pictures<<<dim3((count + 63) / 64), dim3(64), 0, st>>>(a);
+		k_enc_place<<<dim3(1), dim3(256), 0, st>>>(a);
+		HIP_TRY(hipEventRecord(e->ev[2], st));
+		k_enc_clear<<<dim3(1024), dim3(256), 0, st>>>(a);
+		k_enc_write<<<dim3(mb_grid), dim3(JM_ENC_LANES), 0, st>>>(a);
+		HIP_TRY(hipGetLastError());
+	}
 	HIP_TRY(hipEventRecord(e->ev[3], st));
 	HIP_TRY(hipMemcpyAsync(e->h_result, e->d_result, enc_result_bytes(e->cfg.max_streams, e->cfg.max_pictures), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipEventRecord(e->ev_done, st));
@@ -376,6 +629,22 @@ extern "C" int jsmpeg_hip_encoder_picture_range(jsmpeg_hip_encoder_t *e, uint32_
 	const uint64_t *off = e->h_result + 2 + 2 * (size_t)e->cfg.max_streams;
 	if (offset) *offset = off[k];
 	if (bytes) *bytes = reinterpret_cast<const uint32_t *>(off + e->cfg.max_pictures)[k];
+	return 0;
+}
+
+extern "C" const void *jsmpeg_hip_encoder_recon(jsmpeg_hip_encoder_t *e, uint32_t k) {
+	if (enc_ready(e) < 0) return nullptr;
+	if (!e->pass_gop) { fail("encoder: the last call ran with gop 1: it keeps no reconstruction (jsmpeg_hip_encoder_set_gop)"); return nullptr; }
+	if (k >= e->count) { fail("encoder: picture %u of %u", k, e->count); return nullptr; }
+	return e->d_recon + (size_t)k * e->frame_bytes;
+}
+
+extern "C" int jsmpeg_hip_encoder_picture_stats(jsmpeg_hip_encoder_t *e, uint32_t k, uint32_t out[4]) {
+	if (enc_ready(e) < 0) return -1;
+	if (k >= e->count) return fail("encoder: picture %u of %u", k, e->count);
+	if (!out) return fail("encoder: NULL out");
+	const uint32_t mbs = e->mbw * e->mbh;
+	for (int i = 0; i < 4; i++) out[i] = e->pass_gop ? e->h_stats[(size_t)k * 4 + i] : (i == 0 ? mbs : 0u);
 	return 0;
 }
 

@@ -1,7 +1,8 @@
-"""The MPEG-1 intra encoder on the device: the Python side of C ABI part 8 (include/jsmpeg_hip.h, jsmpeg_hip_encoder_*) and
+"""The MPEG-1 encoder on the device (I pictures, or I + P with a GOP): the Python side of C ABI part 8 (include/jsmpeg_hip.h, jsmpeg_hip_encoder_*) and
 the host-side TS mux.  Frames in HBM (a Batch's pool, a Live tick's pictures, any device pointers) or uint8 RGB torch tensors
--> elementary streams in a device buffer that Batch.attach_device takes as it is.  I pictures only, one quantiser scale per
-picture.  torch is imported only when a tensor is handed in."""
+-> elementary streams in a device buffer that Batch.attach_device takes as it is.  I pictures, or -- Encoder.set_gop -- I + P
+with motion search on the device and a closed loop; one quantiser scale per picture.  torch is imported only when a tensor is
+handed in."""
 import ctypes
 
 import numpy as np
@@ -12,7 +13,8 @@ END = 1
 
 SYMBOLS = ("jsmpeg_hip_encoder_create", "jsmpeg_hip_encoder_destroy", "jsmpeg_hip_encoder_encode", "jsmpeg_hip_encoder_encode_rgb",
            "jsmpeg_hip_encoder_sync", "jsmpeg_hip_encoder_query", "jsmpeg_hip_encoder_es", "jsmpeg_hip_encoder_stream_range",
-           "jsmpeg_hip_encoder_picture_range", "jsmpeg_hip_encoder_read_es", "jsmpeg_hip_encoder_timings", "jsmpeg_hip_ts_mux_host")
+           "jsmpeg_hip_encoder_picture_range", "jsmpeg_hip_encoder_read_es", "jsmpeg_hip_encoder_timings", "jsmpeg_hip_ts_mux_host",
+           "jsmpeg_hip_encoder_set_gop", "jsmpeg_hip_encoder_recon", "jsmpeg_hip_encoder_picture_stats")
 
 
 class EncoderConfig(ctypes.Structure):
@@ -51,6 +53,12 @@ def lib():
         L.jsmpeg_hip_encoder_read_es.argtypes = [vp, u32, vp, u64]
         L.jsmpeg_hip_encoder_timings.restype = ctypes.c_int
         L.jsmpeg_hip_encoder_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+        L.jsmpeg_hip_encoder_set_gop.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_set_gop.argtypes = [vp, u32, u32]
+        L.jsmpeg_hip_encoder_recon.restype = vp
+        L.jsmpeg_hip_encoder_recon.argtypes = [vp, u32]
+        L.jsmpeg_hip_encoder_picture_stats.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_picture_stats.argtypes = [vp, u32, ctypes.POINTER(u32)]
         L.jsmpeg_hip_ts_mux_host.restype = ctypes.c_int64
         L.jsmpeg_hip_ts_mux_host.argtypes = [vp, vp, vp, vp, u32, u32, u32, ctypes.POINTER(ctypes.c_uint8), vp, u64]
         _bound = L
@@ -82,8 +90,8 @@ def ts_mux(es, ranges, pts, stream_id=0xE0, pid=0x100, continuity=0):
 
 
 class Encoder:
-    """Pictures on the device -> MPEG-1 elementary streams (all I pictures) on the device.  A call is a pure enqueue; sync()
-    or any reader settles it."""
+    """Pictures on the device -> MPEG-1 elementary streams on the device: all I pictures, or I + P after set_gop.  A call is a
+    pure enqueue; sync() or any reader settles it."""
 
     def __init__(self, width, height, max_pictures, max_streams, max_es_bytes, frame_rate_code=0, device=-1):
         self.L = lib()
@@ -187,6 +195,37 @@ class Encoder:
                                                       n, qs, END if end else 0, st))
         self.count = n
         self._keep = x          # the tensor stays alive until the next call
+
+    def set_gop(self, gop, search=7):
+        """gop 1: I pictures only (the default).  gop N > 1: every N-th picture of a stream is an I picture, the others are P
+        pictures predicted from the encoder's own reconstruction; search: full-pel radius 0 .. 15 of the motion search (0:
+        zero vectors only).  State of the handle: every later encode* call uses it.  Every stream of a call begins with an
+        I picture."""
+        self._ok(self.L.jsmpeg_hip_encoder_set_gop(self.h, gop, search))
+
+    def recon_ptr(self, k):
+        """device address of picture k's reconstruction (Y | Cr | Cb of the coded size) in the last call; gop > 1 only"""
+        p = self.L.jsmpeg_hip_encoder_recon(self.h, k)
+        if not p:
+            raise RuntimeError(_batch.last_error())
+        return p
+
+    def recon(self, k):
+        """picture k's reconstruction on the host: (Y, Cr, Cb) uint8 planes of the coded size -- what a decoder shows"""
+        p = self.recon_ptr(k)
+        out = np.empty(self.frame_bytes, dtype=np.uint8)
+        L = _batch.lib()
+        L.jsmpeg_hip_device_read.restype = ctypes.c_int
+        L.jsmpeg_hip_device_read.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64]
+        self._ok(L.jsmpeg_hip_device_read(out.ctypes.data, p, self.frame_bytes))
+        n, cw, ch = self.coded_width * self.coded_height, self.coded_width, self.coded_height
+        return out[:n].reshape(ch, cw), out[n:n + n // 4].reshape(ch // 2, cw // 2), out[n + n // 4:].reshape(ch // 2, cw // 2)
+
+    def picture_stats(self, k):
+        """macroblocks of picture k of the last call by kind"""
+        out = (ctypes.c_uint32 * 4)()
+        self._ok(self.L.jsmpeg_hip_encoder_picture_stats(self.h, k, out))
+        return dict(intra=int(out[0]), coded=int(out[1]), not_coded=int(out[2]), skipped=int(out[3]))
 
     def sync(self):
         self._ok(self.L.jsmpeg_hip_encoder_sync(self.h))

@@ -3,12 +3,15 @@ decoded batch (bench.py's generator, cfg2: 64 streams x 120 pictures of 1080p) t
 every stream) and for all 7680: the call's span split by jsmpeg_hip_encoder_timings, the output bytes, the bytes the two passes
 read and write per picture against a plain device copy's rate measured in the same process, and the whole pass of decode alone
 against decode + encode (what a transcode costs).  A third step: Batch.tensor(uint8) -> encode_tensor -> decode, the luma PSNR
-against the first decode.
+against the first decode.  A fourth step, `gop`: 64 streams x 12 pictures of 1080p with --gop and --search (gop 1: the intra
+pass on the same pictures): ms per pass, the output bytes, and what Batch.decode takes on the encoder's streams; its figures go
+to the bench_gop<N>_r<R> section of profiles/enc_p_notes.md.
 
 Every GPU step is a child process of this tool under its own `timeout`; the steps are chained and the tool stops at the first
 one that fails.  The figures go into the bench section of profiles/enc_notes.md (nothing is written for a step that did not
 run).
-    python tools/encode_bench.py [--steps pool64,pool7680,tensor] [--reps 8]"""
+    python tools/encode_bench.py [--steps pool64,pool7680,tensor] [--reps 8]
+    python tools/encode_bench.py --steps gop --gop 12 --search 7"""
 import argparse
 import json
 import os
@@ -23,7 +26,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 W, H = 1920, 1080
-STEPS = {"pool64": 300, "pool7680": 420, "tensor": 120}          # seconds each step may take
+STEPS = {"pool64": 300, "pool7680": 420, "tensor": 120, "gop": 300}          # seconds each step may take
 
 
 def median(v):
@@ -114,6 +117,55 @@ def step_pool(all_pictures, reps):
                         decode_alone_wall_ms=median(dec), decode_then_encode_wall_ms=median(both))
 
 
+def step_gop(gop, search, reps):
+    """64 streams x 12 pictures of 1080p from a batch's pool, q = 8, with a GOP (gop 1: the intra pass); then Batch.decode of
+    the encoder's streams, uploaded to a second batch"""
+    import bench
+    from jsmpeg_amd import batch as jb
+    from jsmpeg_amd import encode
+    streams = [g[0] for g in bench.generate_streams(0, 64, 12)]
+    total = sum(len(s) for s in streams)
+    with jb.Batch(W, H, 64, 768 + 8, total + 64 * 64 + 4096, device=0) as b:
+        b.upload(streams)
+        assert b.decode() == 768
+        infos = b.pictures()
+        pics = [p for p, i in enumerate(infos) if i.decoded]
+        sn = [infos[p].stream for p in pics]
+        ptrs = [b.frame_pool_ptr + p * b.frame_stride for p in pics]
+        with encode.Encoder(W, H, len(pics), 64, 768 << 20, device=0) as enc:
+            if gop > 1:
+                enc.set_gop(gop, search)
+            wall, split = [], []
+            for r in range(reps + 2):
+                t0 = time.perf_counter()
+                enc.encode(ptrs, sn, 8)
+                enc.sync()
+                if r >= 2:
+                    wall.append((time.perf_counter() - t0) * 1e3)
+                    split.append(enc.timings())
+            ptr, out_bytes = enc.device_es()
+            kinds = None
+            if gop > 1:
+                kinds = [sum(enc.picture_stats(k)[n] for k in range(len(pics))) for n in ("intra", "coded", "not_coded", "skipped")]
+            dec = []
+            # the streams go through the host: attach_device wants 8 bytes between streams, and the encoder's 16-byte aligned
+            # begins leave fewer where a stream ends 9 .. 16 bytes into its last 16 (the intra encoder's layout, not changed here)
+            es = [np.frombuffer(enc.es(s), dtype=np.uint8) for s in range(64)]
+            with jb.Batch(W, H, 64, 768 + 8, out_bytes + 64 * 64 + 4096, device=0) as back:
+                back.upload(es)
+                for r in range(reps + 2):
+                    t0 = time.perf_counter()
+                    n = back.decode()
+                    if r >= 2:
+                        dec.append((time.perf_counter() - t0) * 1e3)
+                assert n == len(pics)
+            ms = [s["total_ms"] for s in split]
+            return dict(step="gop", gop=gop, search=search, pictures=len(pics), streams=64, q=8, wall_ms=median(wall),
+                        measure_scan_ms=median([s["measure_ms"] for s in split]), write_ms=median([s["write_ms"] for s in split]),
+                        total_ms=median(ms), total_ms_min=round(min(ms), 3), total_ms_max=round(max(ms), 3), output_bytes=int(out_bytes),
+                        kinds=kinds, decode_of_output_wall_ms=median(dec))
+
+
 def step_tensor():
     import torch
     import enc_inputs as ei
@@ -138,7 +190,16 @@ def step_tensor():
 def notes(results):
     lines = ["## Cost on the MI355X (measured by tools/encode_bench.py)", ""]
     for r in results:
-        if r["step"].startswith("pool"):
+        if r["step"] == "gop":
+            lines = ["## gop %d, search range %d: %d pictures of 1080p in %d streams, q = %d (measured by tools/encode_bench.py)" % (r["gop"], r["search"], r["pictures"], r["streams"], r["q"]), "",
+                     "| | ms |", "|---|---|",
+                     "| call + sync, host clock | %.3f |" % r["wall_ms"],
+                     "| timings: measure + scan (the level loop) | %.3f |" % r["measure_scan_ms"],
+                     "| timings: write | %.3f |" % r["write_ms"],
+                     "| timings: total, median (min .. max) | %.3f (%.3f .. %.3f) |" % (r["total_ms"], r["total_ms_min"], r["total_ms_max"]),
+                     "| Batch.decode of the encoder's streams, host clock | %.3f |" % r["decode_of_output_wall_ms"], "",
+                     "Output %d bytes.%s" % (r["output_bytes"], "  Macroblocks intra / coded / not coded / skipped: %s." % " / ".join(str(v) for v in r["kinds"]) if r["kinds"] else ""), ""]
+        elif r["step"].startswith("pool"):
             lines += ["**%d pictures of 1080p into %d streams, q = %d, frames from a batch's pool** (cfg2 content)." % (r["pictures"], r["streams"], r["q"]), "",
                       "| | ms |", "|---|---|",
                       "| call + sync, host clock | %.3f |" % r["wall_ms"],
@@ -163,15 +224,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", default="pool64,pool7680,tensor")
     ap.add_argument("--reps", type=int, default=8)
+    ap.add_argument("--gop", type=int, default=12, help="the gop step: GOP length (1: the intra pass)")
+    ap.add_argument("--search", type=int, default=7, help="the gop step: full-pel search range 0 .. 15")
     ap.add_argument("--child")
     a = ap.parse_args()
     if a.child:
-        r = step_tensor() if a.child == "tensor" else step_pool(a.child == "pool7680", a.reps)
+        r = step_gop(a.gop, a.search, a.reps) if a.child == "gop" else step_tensor() if a.child == "tensor" else step_pool(a.child == "pool7680", a.reps)
         print("RESULT " + json.dumps(r), flush=True)
         return 0
     results = []
     for step in a.steps.split(","):
-        cmd = ["timeout", "-k", "10", str(STEPS[step]), sys.executable, os.path.abspath(__file__), "--child", step, "--reps", str(a.reps)]
+        cmd = ["timeout", "-k", "10", str(STEPS[step]), sys.executable, os.path.abspath(__file__), "--child", step, "--reps", str(a.reps),
+               "--gop", str(a.gop), "--search", str(a.search)]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
         if p.returncode != 0 or not line:
@@ -179,10 +243,14 @@ def main():
             break
         results.append(json.loads(line[-1][7:]))
         print(line[-1][7:], flush=True)
+    done = len(results)
+    from enc_quality import NOTES, replace_section
+    for r in [r for r in results if r["step"] == "gop"]:
+        replace_section(os.path.join(ROOT, "profiles", "enc_p_notes.md"), "bench_gop%d_r%d" % (r["gop"], r["search"]), notes([r]))
+    results = [r for r in results if r["step"] != "gop"]
     if results:
-        from enc_quality import NOTES, replace_section
         replace_section(NOTES, "bench", notes(results))
-    return 0 if len(results) == len(a.steps.split(",")) else 1
+    return 0 if done == len(a.steps.split(",")) else 1
 
 
 if __name__ == "__main__":
