@@ -788,7 +788,7 @@ int jsmpeg_hip_live_render_tensor_latest(jsmpeg_hip_live_t *l, const uint32_t *s
  * closed loop in jsmpeg_amd/csrc/enc_motion.h.  EVERY I picture carries its own sequence and GOP header in front (20 bytes):
  * every I picture -- with gop 1, the default, every picture -- is a joining point for a viewer and a unit for
  * jsmpeg_hip_split_gops.  Streams lie in the output from 16-byte aligned begins with 0xff in front of the first, between them
- * and 256 bytes behind the last: the buffer can be handed to jsmpeg_hip_batch_attach_device as it is.
+ * (8 bytes or more) and 256 bytes behind the last: the buffer can be handed to jsmpeg_hip_batch_attach_device as it is.
  * P CHAINS DO NOT CROSS CALLS: every stream of a call begins with an I picture, whatever the call before ended with (a live
  * stream that goes on pays one I picture per call).  Batch STREAMS, not pictures: a P picture waits for the picture before it,
  * so a call with one stream runs one picture at a time on the device.

@@ -333,23 +333,28 @@ JM_HD uint32_t jm_enc_scan_picture(uint32_t *slice_bytes, uint32_t mbh) {
 }
 
 /* The pictures of a call in order: streams ascend, each stream's pictures back to back from a 16-byte aligned begin, a
- * sequence end code behind the stream's last picture when `end`.  One step per picture. */
+ * sequence end code behind the stream's last picture when `end`, and at least JM_STREAM_GAP bytes of 0xff up to the next
+ * stream's begin (jsmpeg_hip_batch_attach_device refuses ranges that lie closer); the total is the last stream's end
+ * rounded up to 16 (0xff from there on anyway).  One step per picture. */
 struct JmEncPlace {
 	uint64_t at;         /* next free byte */
 	uint32_t stream;     /* of the previous picture, JM_NONE before the first */
 };
 JM_HD uint64_t jm_enc_align16(uint64_t v) { return (v + 15u) & ~(uint64_t)15u; }
+JM_HD uint64_t jm_enc_next_begin(uint64_t stream_end) { return jm_enc_align16(stream_end + JM_STREAM_GAP); }
 JM_HD JmEncPlace jm_enc_place_begin() { JmEncPlace p; p.at = JM_ENC_LEAD_GAP; p.stream = JM_NONE; return p; }
-JM_HD void jm_enc_place_close(JmEncPlace &p, bool end, uint64_t *stream_end) {
+/* the current stream ends; `another` follows it (else: the call ends) */
+JM_HD void jm_enc_place_end_stream(JmEncPlace &p, bool end, uint64_t *stream_end, bool another) {
 	if (p.stream == JM_NONE) return;
 	if (end) p.at += 4;
 	stream_end[p.stream] = p.at;
-	p.at = jm_enc_align16(p.at);
+	p.at = another ? jm_enc_next_begin(p.at) : jm_enc_align16(p.at);
 }
+JM_HD void jm_enc_place_close(JmEncPlace &p, bool end, uint64_t *stream_end) { jm_enc_place_end_stream(p, end, stream_end, false); }
 /* returns the picture's byte offset */
 JM_HD uint64_t jm_enc_place_picture(JmEncPlace &p, uint32_t stream, uint32_t bytes, bool end, uint64_t *stream_begin, uint64_t *stream_end) {
 	if (stream != p.stream) {
-		jm_enc_place_close(p, end, stream_end);
+		jm_enc_place_end_stream(p, end, stream_end, true);
 		stream_begin[stream] = p.at;
 		p.stream = stream;
 	}
@@ -384,11 +389,12 @@ JM_HD void jm_enc_put_slice_header(uint32_t *words, uint64_t at, uint32_t row, u
 	jm_enc_put(b, q, 5); jm_enc_put(b, 0, 1);
 	jm_enc_flush(b);
 }
-/* behind a stream's last picture: the sequence end code when `end`, then 0xff up to the next multiple of 16 */
+/* behind a stream's last picture: the sequence end code when `end`, then 0xff up to where the next stream begins (behind the call's last stream
+ * these bytes lie in the 0xff tail or are the total's rounding) */
 JM_HD void jm_enc_put_stream_tail(uint32_t *words, uint64_t at, bool end) {
 	JmEncBits b = jm_enc_bits_at(words, at * 8u);
 	if (end) { jm_enc_put(b, 0x000001B7u, 32); at += 4; }
-	for (uint64_t i = at; i < jm_enc_align16(at); i++) jm_enc_put(b, 0xffu, 8);
+	for (uint64_t i = at; i < jm_enc_next_begin(at); i++) jm_enc_put(b, 0xffu, 8);
 	jm_enc_flush(b);
 }
 

@@ -31,8 +31,18 @@ def sim():
         vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
         lib.sim_encode_p.restype = ctypes.c_int64
         lib.sim_encode_p.argtypes = [vp, u32, u32, u32, vp, vp, u32, u32, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp]
+        lib.sim_encp_recip_div.restype = None
+        lib.sim_encp_recip_div.argtypes = [vp, u32, u32, vp]
         _sim = lib
     return _sim
+
+
+def sim_recip_div(n, q):
+    """the non-intra quantiser's stand-in for n // q on an array of n"""
+    n = np.ascontiguousarray(n, dtype=np.uint32)
+    out = np.zeros_like(n)
+    sim().sim_encp_recip_div(n.ctypes.data, n.size, q, out.ctypes.data)
+    return out
 
 
 def _s8(v):
@@ -44,8 +54,9 @@ class Result:
     (Y | Cr | Cb bytes each), per picture the macroblocks' vectors [(mvh, mvv) half-pels, None for an intra one] and the
     counts by kind (intra, coded, not coded, skipped)"""
 
-    def __init__(self, buf, ranges, streams, recon, vectors, stats):
+    def __init__(self, buf, ranges, streams, recon, vectors, stats, table=None):
         self.buf, self.ranges, self.streams, self.recon, self.vectors, self.stats = buf, ranges, streams, recon, vectors, stats
+        self.table = table              # [(begin, end)] of every stream number below max_streams, absent ones included
 
     def triple(self):
         return self.buf, self.ranges, self.streams
@@ -81,7 +92,8 @@ def sim_encode_p(frames, width, height, gop, search, streams=None, qscale=8, fra
     vectors = [[None if (v & 3) == 0 else (_s8(v >> 16), _s8(v >> 24)) for v in info[k * mbs:(k + 1) * mbs].tolist()]
                for k in range(n)]
     return Result(out[:total].tobytes(), [(int(po[k]), int(pb[k])) for k in range(n)], {i: (int(sb[i]), int(se[i])) for i in present},
-                  [recon[k * fb:(k + 1) * fb].copy() for k in range(n)], vectors, [tuple(int(v) for v in stats[4 * k:4 * k + 4]) for k in range(n)])
+                  [recon[k * fb:(k + 1) * fb].copy() for k in range(n)], vectors, [tuple(int(v) for v in stats[4 * k:4 * k + 4]) for k in range(n)],
+                  [(int(sb[i]), int(se[i])) for i in range(ms)])
 
 
 # ---------------------------------------------------------------------------------------------------- inputs
@@ -135,6 +147,69 @@ def p_cases(libs):
     return out
 
 
+RADII = tuple(range(16))               # every search range the header accepts
+
+
+def checker_picture(width, height, low=20, high=220):
+    """a checkerboard of 2 x 2 cells: a shift by 2 pels in either direction is its inverse, a shift by 4 the picture itself --
+    the candidates of a search tie by the dozen"""
+    cw, ch = enc_ref.coded(width, height)
+    yy, xx = np.mgrid[0:ch, 0:cw]
+    return np.where(((yy >> 1) + (xx >> 1)) & 1, high, low).astype(np.uint8)
+
+
+def threshold_frames():
+    """64 x 16: flat 128, then four macroblocks of 130s whose first k pixels are 131, k = 127, 128, 129, 130.  Against the flat
+    picture every candidate's SAD is 512 + k; the mean rounds to 130 for k = 127 (activity 127) and to 131 from k = 128 on
+    (activity 256 - k): activity + 512 < SAD reads 639 < 639, 640 < 640 (the equality), 639 < 641, 638 < 642"""
+    y = np.full((16, 64), 130, np.uint8)
+    for col, k in enumerate((127, 128, 129, 130)):
+        mb = np.full(256, 130, np.uint8)
+        mb[:k] = 131
+        y[:, col * 16:col * 16 + 16] = mb.reshape(16, 16)
+    c = np.full((8, 32), 128, np.uint8)
+    return [ei.flat_frame(64, 16, 128), ei.frame_of(y, c, c)]
+
+
+def range_cases(libs, base=None):
+    """name -> (frames, width, height): what every search range 0 .. 15 runs over -- five of p_cases (`base`, when the caller
+    has them), a pan of (9.5, -5.5) pels per picture that every range below 10 cuts short, the checkerboard, its shift by
+    2 pels and the checkerboard again, and the pair on the intra threshold"""
+    base = base if base is not None else p_cases(libs)
+    out = {name: base[name] for name in ("noise", "whole_pel_pan", "half_pel_pan", "content_177x145", "one_macroblock")}
+    out["fast_pan"] = (pan_frames(64, 48, 3, (9, -6), half=True), 64, 48)
+    y = checker_picture(64, 48)
+    c = np.full((24, 32), 128, np.uint8)
+    out["checker_ties"] = ([ei.frame_of(y, c, c), ei.frame_of(np.roll(y, 2, axis=1), c, c), ei.frame_of(y, c, c)], 64, 48)
+    out["intra_threshold"] = (threshold_frames(), 64, 16)
+    return out
+
+
+LONG_STREAMS = [0] * 255 + [1] * 2 + [3] * 1 + [4] * 300 + [7] * 542
+LONG_MAX_STREAMS = 9
+LONG_GOPS = ((1024, 3), (300, 15), (7, 1))      # (gop, search range)
+
+
+def long_call():
+    """(frames, width, height, streams, scales): 1100 pictures of 48 x 32 (3 x 2 macroblocks: two slices, room for a skipped
+    macroblock) in five streams whose numbers have gaps and whose boundaries -- pictures 255, 257, 258 and 558 -- lie on both
+    sides of the 256-picture steps of the placement; a slow drift over one smooth picture with a rest now and then, noise at
+    every 97th picture (intra macroblocks inside P pictures), a quantiser scale per picture"""
+    w, h, n = 48, 32, len(LONG_STREAMS)
+    src = np.clip(np.rint(smooth_picture(h, w)), 0, 255).astype(np.uint8)
+    csrc = np.clip(np.rint(smooth_picture(h // 2, w // 2, seed=2)), 0, 255).astype(np.uint8)
+    frames = []
+    for t in range(n):
+        if t % 97 == 96:
+            frames.append(ei.noise_frame(w, h, 1000 + t))
+            continue
+        u = t - t % 5 if (t // 40) % 3 == 2 else t                  # a rest: the same picture five times
+        x0, y0 = 32 + int(np.rint(14 * np.sin(u / 9.0))), 32 + int(np.rint(11 * np.cos(u / 13.0)))
+        cx, cy = 32 + (x0 - 32) // 2, 32 + (y0 - 32) // 2
+        frames.append(ei.frame_of(src[y0:y0 + h, x0:x0 + w], csrc[cy:cy + h // 2, cx:cx + w // 2], 255 - csrc[cy:cy + h // 2, cx:cx + w // 2]))
+    return frames, w, h, list(LONG_STREAMS), [1 + t % 31 for t in range(n)]
+
+
 # ---------------------------------------------------------------------------------------------------- the judge
 
 def picture_types(es):
@@ -153,3 +228,34 @@ def oracle_frames(libs, es):
 
 def expected_types(n, gop):
     return [1 if k % gop == 0 else 2 for k in range(n)]
+
+
+def p_header(buf, off):
+    """(temporal_reference, picture_coding_type, full_pel_forward_vector, forward_f_code) of the P picture header at `off`"""
+    assert buf[off:off + 4] == b"\x00\x00\x01\x00", off
+    v = int.from_bytes(buf[off + 4:off + 9], "big")         # 10 + 3 + 16 (vbv_delay) + 1 + 3 bits, 7 of padding
+    return v >> 30, (v >> 27) & 7, (v >> 10) & 1, (v >> 7) & 7
+
+
+def ordinals(streams):
+    """each picture's number in its stream"""
+    out = []
+    for k, s in enumerate(streams):
+        out.append(out[-1] + 1 if k and streams[k - 1] == s else 0)
+    return out
+
+
+def wrapped_differentials(vectors, mbw, rng):
+    """how many vector components of a call (Result.vectors) differ from their predictor by less than -rng or by rng or more,
+    so that the written differential is that difference +- 2 rng.  The predictor along a slice: the vector of the macroblock
+    before -- zero at the slice's begin and after an intra macroblock; a skipped macroblock and one without motion
+    compensation have a zero vector and leave a zero predictor, which is the same"""
+    n = 0
+    for pic in vectors:
+        for first in range(0, len(pic), mbw):
+            prev = (0, 0)
+            for v in pic[first:first + mbw]:
+                if v is not None:
+                    n += sum(1 for a, b in zip(v, prev) if not -rng <= a - b < rng)
+                prev = v if v is not None else (0, 0)
+    return n

@@ -336,6 +336,7 @@ def encode(frames, width, height, gop, search_range, streams=None, qscale=8, fra
             if end:
                 out += b"\x00\x00\x01\xb7"
             sr[streams[k]][1] = len(out)
-            out += b"\xff" * (-len(out) % 16)
+            # to the next 16-byte aligned begin, at least 8 bytes away; behind the call's last stream, to the next multiple of 16
+            out += b"\xff" * (-len(out) % 16 if k + 1 == n else 8 + -(len(out) + 8) % 16)
     r.buf, r.streams = bytes(out), {s: tuple(v) for s, v in sr.items()}
     return r

@@ -48,6 +48,12 @@ static uint32_t sim_motion(const uint8_t *cur, const uint8_t *ref, uint32_t cw, 
 	return jm_encp_decide(sad, activity, mvh, mvv);
 }
 
+/* jm_encp_quant_inter's division on its own: out[i] = mulhi(2 n[i], jm_encp_recip(q)), which stands in for n[i] / q */
+extern "C" void sim_encp_recip_div(const uint32_t *n, uint32_t count, uint32_t q, uint32_t *out) {
+	const uint32_t rq = jm_encp_recip(q);
+	for (uint32_t i = 0; i < count; i++) out[i] = jm_enc_mulhi(2u * n[i], rq);
+}
+
 /* One call of the encoder with gop > 1: sim_encode's arguments, then gop and search_range; recon: count frames out (16 bytes
  * of slack behind them), info: count * macroblocks records' info words out, stats: count * 4.  Returns the total bytes or -1. */
 extern "C" int64_t sim_encode_p(const uint8_t *frames, uint32_t w, uint32_t h, uint32_t count, const uint32_t *stream, const uint8_t *q,

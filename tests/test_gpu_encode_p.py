@@ -75,6 +75,117 @@ def test_small_inputs_equal_the_simulator_and_the_restatement(torch, hip_lib, ca
             assert_equals(enc, [0], enc_p_ref.encode(frames, w, h, gop, R, qscale=q), (name, "restatement"))
 
 
+@pytest.fixture(scope="module")
+def ranged(libs, cases):
+    return ep.range_cases(libs, cases)
+
+
+@pytest.fixture(scope="module")
+def range_encoders(torch, hip_lib, ranged):
+    """one Encoder per picture size, kept from radius to radius, and every case's frames on the device"""
+    from jsmpeg_amd import encode
+    encs, dev = {}, {}
+    for name, (frames, w, h) in ranged.items():
+        if (w, h) not in encs:
+            encs[(w, h)] = encode.Encoder(w, h, 4, 1, 64 + 4 * (len(frames[0]) * 4 + 4096))
+        dev[name] = on_device(torch, frames)
+    yield encs, dev
+    for enc in encs.values():
+        enc.close()
+
+
+@pytest.mark.parametrize("R", ep.RADII)
+def test_every_search_range_equals_the_simulator(ranged, range_encoders, R):
+    """k_enc_motion at every radius -- its staged rows, its passes over the items and the partial last one, the group
+    alignment, the half-pel step at the window's edge -- against the simulator, which tests/test_enc_p_sim.py ties to the
+    restatement and the oracle on these inputs.  The handles live across the radii (set_gop between calls: nothing of the
+    radius before may stay).  `intra_threshold` (the decision at equality) and `checker_ties` (the order among equal SADs)
+    are among the cases, so the device's decision and reduction are held to those edges here too"""
+    encs, dev = range_encoders
+    for q in (1, 8):
+        for name, (frames, w, h) in ranged.items():
+            enc = encs[(w, h)]
+            enc.set_gop(4, R)
+            enc.encode(dev[name][1], None, q)
+            assert_equals(enc, [0], ep.sim_encode_p(frames, w, h, 4, R, qscale=q), (name, q, R))
+
+
+@pytest.fixture(scope="module")
+def long_call():
+    return ep.long_call()
+
+
+@pytest.fixture(scope="module")
+def long_encoder(torch, hip_lib, long_call):
+    from jsmpeg_amd import encode
+    frames, w, h, streams, qs = long_call
+    n = len(frames)
+    with encode.Encoder(w, h, n, ep.LONG_MAX_STREAMS, 64 + n * (len(frames[0]) * 4 + 4096)) as enc:
+        yield enc, on_device(torch, frames)
+
+
+_long = {}
+
+
+def long_want(long_call, gop, R):
+    if (gop, R) not in _long:
+        frames, w, h, streams, qs = long_call
+        _long[(gop, R)] = ep.sim_encode_p(frames, w, h, gop, R, streams=streams, qscale=qs, max_streams=ep.LONG_MAX_STREAMS)
+    return _long[(gop, R)]
+
+
+@pytest.mark.parametrize("gop,R", ep.LONG_GOPS)
+def test_a_call_of_1100_pictures(long_call, long_encoder, gop, R):
+    """k_enc_place's second to fifth step of 256 pictures with the state it carries across them, 18 blocks of the picture scan,
+    up to 1024 levels, stream numbers with gaps -- and the same call once more behind a short one on the same handle"""
+    frames, w, h, streams, qs = long_call
+    enc, (t, ptrs) = long_encoder
+    want = long_want(long_call, gop, R)
+    absent = [s for s in range(ep.LONG_MAX_STREAMS) if s not in streams]
+    enc.set_gop(gop, R)
+    enc.encode(ptrs, streams, qs)
+    assert_equals(enc, streams, want, "first")
+    assert [enc.stream_range(s) for s in absent] == [(0, 0)] * len(absent)
+    a, b = 556, 561                                         # two pictures of stream 4, three of stream 7
+    enc.encode(ptrs[a:b], streams[a:b], qs[a:b], end=False)
+    assert_equals(enc, streams[a:b], ep.sim_encode_p(frames[a:b], w, h, gop, R, streams=streams[a:b], qscale=qs[a:b], end=False,
+                                                      max_streams=ep.LONG_MAX_STREAMS), "short")
+    enc.encode(ptrs, streams, qs)
+    assert_equals(enc, streams, want, "again")
+    assert [enc.stream_range(s) for s in absent] == [(0, 0)] * len(absent)
+
+
+def test_round_trip_of_the_long_call(long_call, long_encoder):
+    """the 1100 pictures at gop 300, R 15, through Batch from the encoder's buffer -- the present streams' ranges, in order --
+    by decode() and by enqueue(): the encoder's own reconstructions, picture types and levels by ordinal"""
+    from jsmpeg_amd import batch as jb
+    frames, w, h, streams, qs = long_call
+    enc, (t, ptrs) = long_encoder
+    gop, n = 300, len(frames)
+    enc.set_gop(gop, 15)
+    enc.encode(ptrs, streams, qs)
+    enc.sync()
+    own = [int(hashing.frame_hash(*enc.recon(k))) for k in range(n)]
+    present = sorted(set(streams))
+    begin, end = zip(*(enc.stream_range(s) for s in present))
+    ptr, total = enc.device_es()
+    ordinal = ep.ordinals(streams)
+    with jb.Batch(w, h, len(present), n + 4, total + 4096) as dst:
+        for how in ("decode", "enqueue"):
+            dst.attach_device(ptr, total, begin, end)
+            if how == "decode":
+                assert dst.decode() == n
+            else:
+                assert dst.enqueue() == 0
+                dst.sync()
+            infos = dst.pictures()
+            assert len(infos) == n and all(i.decoded for i in infos), how
+            assert [i.stream for i in infos] == [present.index(s) for s in streams], how
+            assert [int(v) for v in dst.frame_hashes()[:n]] == own, how
+            assert [i.type for i in infos] == [1 if o % gop == 0 else 2 for o in ordinal], how
+            assert [i.level for i in infos] == [o % gop for o in ordinal], how
+
+
 def test_ragged_levels(torch, hip_lib, cases):
     """streams of 3, 1 and 2 pictures with gop 2: levels of 3 and 2 pictures, a scale per picture, the end flag on and off"""
     from jsmpeg_amd import encode
