@@ -792,7 +792,7 @@ int jsmpeg_hip_live_render_tensor_latest(jsmpeg_hip_live_t *l, const uint32_t *s
  * P CHAINS DO NOT CROSS CALLS: every stream of a call begins with an I picture, whatever the call before ended with (a live
  * stream that goes on pays one I picture per call).  Batch STREAMS, not pictures: a P picture waits for the picture before it,
  * so a call with one stream runs one picture at a time on the device.
- * OUT OF SCOPE: B pictures, rate control and quantiser changes inside a picture, custom matrices, P chains across calls, vectors
+ * OUT OF SCOPE: B pictures, quantiser changes inside a picture, a VBV model, custom matrices, P chains across calls, vectors
  * beyond +-15 pels, a Node binding, resizing of YCbCr (resize the RGB tensor).
  * A pass is a PURE ENQUEUE on hip_stream, like jsmpeg_hip_batch_enqueue: every size and offset is worked out on the device; the
  * host waits in jsmpeg_hip_encoder_sync and the readers only (they settle the pass first).  One pass at a time per handle: a
@@ -844,6 +844,21 @@ int jsmpeg_hip_encoder_set_gop(jsmpeg_hip_encoder_t *enc, uint32_t gop, uint32_t
 const void *jsmpeg_hip_encoder_recon(jsmpeg_hip_encoder_t *enc, uint32_t k);
 /* macroblocks of picture k by kind: intra, predicted + coded, predicted not coded, skipped */
 int jsmpeg_hip_encoder_picture_stats(jsmpeg_hip_encoder_t *enc, uint32_t k, uint32_t out[4]);
+/* RATE CONTROL: the quantiser scale of every picture chosen on the device, still a pure enqueue.  bytes_per_picture 0 (the
+ * default) switches it off: the scales are the caller's and every stream is what it was.  Otherwise, with m the pictures of a
+ * picture's GOP in the call (a stream's last GOP may be short; gop 1: m = 1), the GOP has m * bytes_per_picture bytes; its I
+ * picture gets the share i_weight / (i_weight + m - 1) of them, each P picture an equal share of what the pictures before it
+ * left, and a picture is coded at the SMALLEST scale of q_min .. q_max at which it is at most its budget -- measured exactly
+ * at every scale of the range, jsmpeg_hip_encoder_picture_range's bytes -- or at q_max if it is at none (the rule, in integers:
+ * jsmpeg_amd/csrc/enc_rate.h).  Budgets carry neither from GOP to GOP nor from call to call; no VBV model, the headers stay as
+ * they are.  State of the handle like the GOP; while on, the qscale / quantiser_scale arguments of the encode calls are checked
+ * as before and otherwise unused, the pass is the GOP's also at gop 1 (jsmpeg_hip_encoder_recon works), and 62 bytes per
+ * macroblock of max_pictures pictures are allocated by the first call that switches it on (with the GOP's stores, if they
+ * are not there yet).  Refused while a pass is in flight, for q_min < 1, q_max > 31, q_min > q_max, i_weight outside 1 .. 255. */
+int jsmpeg_hip_encoder_set_rate(jsmpeg_hip_encoder_t *enc, uint32_t bytes_per_picture, uint32_t q_min, uint32_t q_max, uint32_t i_weight);
+/* what the rule chose for picture k of the last call: the scale, the budget (saturated to 32 bits), the picture's bytes;
+ * refused when that call ran with rate control off */
+int jsmpeg_hip_encoder_picture_rate(jsmpeg_hip_encoder_t *enc, uint32_t k, uint32_t out[3]);
 
 /* Host-side TS mux (plain C, no device; a jsmpeg player takes TS): one PES per unit (a picture's range in `es`) with its PTS,
  * the payload in 184-byte pieces, the unit's last packet padded by adaptation-field stuffing -- what the reference's demuxer

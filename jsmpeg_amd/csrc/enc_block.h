@@ -5,7 +5,7 @@
  *
  * I pictures here, one quantiser scale per picture, the default intra matrix, one slice per macroblock row; P pictures and the
  * closed loop they need (the encoder's reference must be the decoder's reconstruction) are enc_motion.h's, built on what is
- * below.  OUT OF SCOPE (say so to whoever asks): B pictures, rate control, custom matrices, a Node binding, resizing of YCbCr
+ * below.  OUT OF SCOPE (say so to whoever asks): B pictures, a VBV model (rate control by a budget per GOP: enc_rate.h), custom matrices, a Node binding, resizing of YCbCr
  * (resize the RGB tensor with torch).
  *
  * FORWARD DCT, exactly:  with C[k][n] = round(2^14 * c_k * cos((2n + 1) k pi / 16)), c_0 = sqrt(1/8), c_k = 1/2

@@ -427,15 +427,20 @@ JM_HD void jm_encp_write_intra(JM_GLOBAL const uint8_t *frame, uint32_t cw, uint
 	}
 }
 
-/* block b of a predicted macroblock: prediction into pp, levels into zz; returns their mask */
-JM_HD uint64_t jm_encp_inter_block(JM_GLOBAL const uint8_t *frame, JM_GLOBAL const uint8_t *ref, const JmEncPlane &p, int b, int mvh, int mvv,
-                                   uint32_t rq, int16_t *zz, uint32_t zs, uint32_t *pp, uint32_t ps) {
+/* block b of a predicted macroblock: prediction into pp, the transformed residual into c8 */
+JM_HD void jm_encp_inter_c8(JM_GLOBAL const uint8_t *frame, JM_GLOBAL const uint8_t *ref, const JmEncPlane &p, int b, int mvh, int mvv,
+                            uint32_t *pp, uint32_t ps, int32_t c8[64]) {
 	uint32_t P[16];
 	jm_encp_predict8(ref + p.off, p.stride, p.ph, p.x0, p.y0, b < 4 ? mvh : mvh / 2, b < 4 ? mvv : mvv / 2, P);
 #pragma unroll
 	for (uint32_t i = 0; i < 16; i++) pp[i * ps] = P[i];
-	int32_t c8[64];
 	jm_encp_fdct<true>(frame + (p.off + (size_t)p.y0 * p.stride + (size_t)p.x0), p.stride, pp, ps, c8);
+}
+/* ... and its levels into zz; returns their mask */
+JM_HD uint64_t jm_encp_inter_block(JM_GLOBAL const uint8_t *frame, JM_GLOBAL const uint8_t *ref, const JmEncPlane &p, int b, int mvh, int mvv,
+                                   uint32_t rq, int16_t *zz, uint32_t zs, uint32_t *pp, uint32_t ps) {
+	int32_t c8[64];
+	jm_encp_inter_c8(frame, ref, p, b, mvh, mvv, pp, ps, c8);
 	return jm_encp_quant_inter(c8, rq, zz, zs);
 }
 
@@ -491,26 +496,28 @@ JM_HD uint32_t jm_encp_type(uint32_t info, bool p_picture) {
 	return (3u << 16) | 1u;
 }
 
-/* a slice of mbw macroblocks of a picture of a GOP: bit offsets and inherited state in place, the slice's kinds added to
- * kinds[4]; returns the slice's bytes */
-JM_HD uint32_t jm_encp_scan_slice(JmEncPMb *mb, uint32_t mbw, bool p_picture, uint32_t r_size, const JmEncTables *T, const JmEncPTables *PT, uint32_t kinds[4]) {
+/* THE WALK along a slice of mbw macroblocks, whatever holds them.  `mb` gives macroblock i's info(i) (kind, vector transmitted,
+ * vector), its local bits(i) and -- intra -- its DC levels dcs(i), and takes what the walk finds: count(kind), skipped(i, at),
+ * placed(i, at, inh, pred) with `at` the bit offset from the first byte of the slice.  Returns the slice's bytes. */
+template <class Row>
+JM_HD uint32_t jm_encp_walk_slice(Row &mb, uint32_t mbw, bool p_picture, uint32_t r_size, const JmEncTables *T, const JmEncPTables *PT) {
 	uint32_t pred = JM_ENC_PRED0, at = JM_ENC_SLICE_HEAD_BITS;
 	int pmh = 0, pmv = 0, last = -1;
 	for (uint32_t i = 0; i < mbw; i++) {
-		const uint32_t info = mb[i].info, kind = jm_encp_kind(info);
-		kinds[kind]++;
+		const uint32_t info = mb.info(i), kind = jm_encp_kind(info);
+		mb.count(kind);
 		if (kind == JM_ENCP_SKIPPED) {
-			mb[i].bits = at; mb[i].inh = 0; mb[i].pred = JM_ENC_PRED0;
+			mb.skipped(i, at);
 			pred = JM_ENC_PRED0; pmh = pmv = 0;
 			continue;
 		}
 		const uint32_t inc = (uint32_t)((int)i - last);
 		last = (int)i;
-		uint32_t n = jm_encp_mba<false>(inc, PT, nullptr) + (jm_encp_type(info, p_picture) >> 16) + mb[i].bits;
-		mb[i].inh = inc | (((uint32_t)pmh & 255u) << 16) | (((uint32_t)pmv & 255u) << 24);
-		mb[i].pred = pred;
+		uint32_t n = jm_encp_mba<false>(inc, PT, nullptr) + (jm_encp_type(info, p_picture) >> 16) + mb.bits(i);
+		uint32_t inh = inc | (((uint32_t)pmh & 255u) << 16) | (((uint32_t)pmv & 255u) << 24);
+		const uint32_t inherited = pred;
 		if (kind == JM_ENCP_INTRA) {
-			const uint64_t dcs = (uint64_t)mb[i].dc[0] | ((uint64_t)mb[i].dc[1] << 32);
+			const uint64_t dcs = mb.dcs(i);
 			n += jm_enc_dc_bits(dcs, pred, T);
 			pred = jm_enc_pred_of(dcs);
 			pmh = pmv = 0;
@@ -522,11 +529,28 @@ JM_HD uint32_t jm_encp_scan_slice(JmEncPMb *mb, uint32_t mbw, bool p_picture, ui
 				pmh = mvh; pmv = mvv;
 			} else pmh = pmv = 0;
 		}
-		if (i + 1 == mbw && (at & 7u) && (at & 7u) + n <= 8u) { mb[i].inh |= 1u << 12; n += PT->mba[34] >> 16; }     /* STUFFING, above */
-		mb[i].bits = at;
+		if (i + 1 == mbw && (at & 7u) && (at & 7u) + n <= 8u) { inh |= 1u << 12; n += PT->mba[34] >> 16; }     /* STUFFING, above */
+		mb.placed(i, at, inh, inherited);
 		at += n;
 	}
 	return (at + 7u) >> 3;
+}
+
+/* a slice of mbw macroblocks of a picture of a GOP: bit offsets and inherited state in place, the slice's kinds added to
+ * kinds[4]; returns the slice's bytes */
+struct JmEncPRow {
+	JmEncPMb *mb;
+	uint32_t *kinds;
+	JM_HD uint32_t info(uint32_t i) const { return mb[i].info; }
+	JM_HD uint32_t bits(uint32_t i) const { return mb[i].bits; }
+	JM_HD uint64_t dcs(uint32_t i) const { return (uint64_t)mb[i].dc[0] | ((uint64_t)mb[i].dc[1] << 32); }
+	JM_HD void count(uint32_t kind) { kinds[kind]++; }
+	JM_HD void skipped(uint32_t i, uint32_t at) { mb[i].bits = at; mb[i].inh = 0; mb[i].pred = JM_ENC_PRED0; }
+	JM_HD void placed(uint32_t i, uint32_t at, uint32_t inh, uint32_t pred) { mb[i].bits = at; mb[i].inh = inh; mb[i].pred = pred; }
+};
+JM_HD uint32_t jm_encp_scan_slice(JmEncPMb *mb, uint32_t mbw, bool p_picture, uint32_t r_size, const JmEncTables *T, const JmEncPTables *PT, uint32_t kinds[4]) {
+	JmEncPRow row = { mb, kinds };
+	return jm_encp_walk_slice(row, mbw, p_picture, r_size, T, PT);
 }
 JM_HD uint32_t jm_encp_scan_picture(uint32_t *slice_bytes, uint32_t mbh, uint32_t head_bytes) {
 	uint32_t at = head_bytes;

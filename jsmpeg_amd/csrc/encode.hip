@@ -21,10 +21,22 @@
  * then k_enc_scan_slices_p / k_enc_scan_pictures_p (the neighbour-dependent codes, the kinds), place and clear as above, and
  * ONE k_enc_write_p over every macroblock of the call: it recomputes a macroblock's levels from the source and the kept
  * reconstruction of the picture before.  The host builds the level lists from the stream numbers; it never reads the device.
+ *
+ * With RATE CONTROL (jsmpeg_hip_encoder_set_rate; the rule: enc_rate.h) the pass is always the level loop, also at gop 1, and
+ * per level, between k_enc_motion and k_enc_measure_p, the quantiser scale of the level's pictures is chosen on the device:
+ *   k_enc_rate_measure   a macroblock per lane: each block transformed once, quantised and counted at every scale of the range;
+ *                        16 bits per (macroblock, scale) out
+ *   k_enc_rate_scan      a (picture, slice, scale) per lane: the slice's walk over those records, its bytes
+ *   k_enc_rate_pick      a wavefront per picture, lanes over the scales: the picture's bytes at each, the budget from the final
+ *                        bytes of its GOP's earlier levels, the smallest scale that fits -- into the picture's JmEncPic::q
+ * and the kernels behind them read that q as they read the caller's.  EXTRA DEVICE MEMORY, allocated by the first
+ * jsmpeg_hip_encoder_set_rate that switches rate control on: per picture of max_pictures 62 bytes per macroblock (31 records of
+ * 16 bits; 506 KB at 1080p), 124 bytes per macroblock row and 16 bytes -- and the stores of a GOP, if they are not there yet.
  */
 #include "engine_internal.h"
 #include "enc_block.h"
 #include "enc_motion.h"
+#include "enc_rate.h"
 
 #define JM_ENC_LANES 64
 #define JM_ENC_MOTION_WAVES 4    /* macroblocks (one wavefront each) of a k_enc_motion workgroup */
@@ -33,6 +45,7 @@ struct JmEncPic {
 	const uint8_t *frame;    /* Y | Cr | Cb of the coded size */
 	uint32_t stream, ordinal, q;
 	uint32_t last;           /* the last picture of its stream in this call */
+	uint32_t m;              /* the pictures of its GOP in this call (rate control) */
 };
 
 struct JmEncArgs {
@@ -272,6 +285,66 @@ __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_measure_p(JmEncArgs a, JmE
 	*rec = out;
 }
 
+/* ------------------------------------------------------------------ kernels of rate control (enc_rate.h) */
+
+struct JmEncRArgs {
+	uint16_t *rec;               /* [count][mbh][mbw][JM_ENCR_MAX_Q]: jm_encr_record */
+	uint32_t *slice;             /* [count][mbh][JM_ENCR_MAX_Q]: a slice's bytes at every scale */
+	uint32_t *out;               /* [count][4]: q, budget (saturated), bytes, 0 */
+	uint64_t T;
+	uint32_t q_min, nq, W;
+};
+
+__global__ void __launch_bounds__(JM_ENC_LANES) k_enc_rate_measure(JmEncArgs a, JmEncPArgs p, JmEncRArgs r, uint32_t first, uint32_t n) {
+	__shared__ int16_t zz[64 * JM_ENC_LANES];
+	__shared__ uint32_t pp[16 * JM_ENC_LANES];
+	__shared__ uint32_t acc[JM_ENCR_MAX_Q * JM_ENC_LANES];
+	const uint64_t g = (uint64_t)blockIdx.x * JM_ENC_LANES + threadIdx.x;
+	if (g >= (uint64_t)n * a.mbw * a.mbh) return;
+	const EncPLane l = encp_lane(a, p, first, g);
+	const JmEncPic pic = a.pics[l.k];
+	const size_t at = (size_t)l.k * a.mbw * a.mbh + l.m;
+	JmEncPMb *rec = p.pmb + at;
+	JM_GLOBAL const uint8_t *ref = (JM_GLOBAL const uint8_t *)p.recon + (size_t)l.k * p.frame_bytes - p.frame_bytes;    /* only read in a P picture, never a call's first */
+	const uint32_t found = (pic.ordinal % p.gop) ? rec->info : 0u;
+	uint64_t dcs;
+	if (jm_encr_measure((JM_GLOBAL const uint8_t *)pic.frame, ref, a.cw, a.ch, a.mbw, l.col, l.row, found, r.q_min, r.nq, a.tables, p.ptables,
+	                    zz + threadIdx.x, JM_ENC_LANES, pp + threadIdx.x, JM_ENC_LANES, acc + threadIdx.x, JM_ENC_LANES, r.rec + at * JM_ENCR_MAX_Q, &dcs)) {
+		rec->dc[0] = (uint32_t)dcs; rec->dc[1] = (uint32_t)(dcs >> 32);
+	}
+}
+
+__global__ void __launch_bounds__(64) k_enc_rate_scan(JmEncArgs a, JmEncPArgs p, JmEncRArgs r, uint32_t first, uint32_t n) {
+	const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= (uint64_t)n * a.mbh * r.nq) return;
+	const uint32_t qi = (uint32_t)(g % r.nq), row = (uint32_t)((g / r.nq) % a.mbh), k = p.list[first + (uint32_t)(g / ((uint64_t)r.nq * a.mbh))];
+	const size_t s = (size_t)k * a.mbh + row;
+	r.slice[s * JM_ENCR_MAX_Q + qi] = jm_encr_scan(r.rec + s * a.mbw * JM_ENCR_MAX_Q, p.pmb + s * a.mbw, qi, a.mbw, (a.pics[k].ordinal % p.gop) != 0, p.r_size, a.tables, p.ptables);
+}
+
+/* a wavefront per picture of the n pictures list[first ..]; lane qi: the picture at scale q_min + qi */
+__global__ void __launch_bounds__(64) k_enc_rate_pick(JmEncArgs a, JmEncPArgs p, JmEncRArgs r, uint32_t first, uint32_t n) {
+	if (blockIdx.x >= n) return;
+	const uint32_t lane = threadIdx.x, k = p.list[first + blockIdx.x];
+	const JmEncPic pic = a.pics[k];
+	const uint32_t level = pic.ordinal % p.gop;
+	uint32_t bytes = level ? JM_ENC_P_HEAD_BYTES : JM_ENC_PIC_HEAD_BYTES;
+	if (lane < r.nq)
+		for (uint32_t row = 0; row < a.mbh; row++) bytes += r.slice[((size_t)k * a.mbh + row) * JM_ENCR_MAX_Q + lane];
+	/* the GOP's pictures at the levels before are the `level` pictures in front of this one: their final bytes */
+	uint64_t spent = 0;
+	for (uint32_t j = 1 + lane; j <= level; j += 64u) spent += r.out[(size_t)(k - j) * 4 + 2];
+#pragma unroll
+	for (int o = 32; o; o >>= 1) spent += __shfl_xor((unsigned long long)spent, o);
+	const uint64_t budget = jm_encr_budget(r.T, pic.m, level, r.W, spent);
+	const uint32_t fit = (uint32_t)enc_wave_min(lane < r.nq && bytes <= budget ? lane : r.nq - 1u);
+	const uint32_t taken = __shfl(bytes, (int)fit);
+	if (lane == 0) {
+		const_cast<JmEncPic *>(a.pics)[k].q = r.q_min + fit;
+		r.out[(size_t)k * 4] = r.q_min + fit; r.out[(size_t)k * 4 + 1] = jm_encr_saturate(budget); r.out[(size_t)k * 4 + 2] = taken; r.out[(size_t)k * 4 + 3] = 0;
+	}
+}
+
 __global__ void __launch_bounds__(64) k_enc_scan_slices_p(JmEncArgs a, JmEncPArgs p) {
 	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
 	if (s >= a.count * a.mbh) return;
@@ -345,16 +418,24 @@ struct jsmpeg_hip_encoder_t {
 	uint32_t *d_list, *h_list;       /* the pictures by level; h_list: pinned */
 	uint32_t *d_slice_kinds, *d_stats, *h_stats;   /* h_stats: pinned */
 	bool gop_ready;                  /* all of the stores above are there */
-	bool pass_gop;                   /* the last call ran with gop > 1 */
+	bool pass_gop;                   /* the last call ran the level loop: gop > 1, or rate control */
+	/* rate control (jsmpeg_hip_encoder_set_rate); the stores are allocated by the first call that switches it on */
+	uint32_t rate_bytes, q_min, q_max, i_weight;   /* rate_bytes 0: off */
+	uint16_t *d_rate_rec;
+	uint32_t *d_rate_slice, *d_rate_out, *h_rate;  /* h_rate: pinned */
+	bool rate_ready;
+	bool pass_rate;                  /* the last call ran with rate control */
 };
 
 static void enc_free_gop(jsmpeg_hip_encoder_t *e);
+static void enc_free_rate(jsmpeg_hip_encoder_t *e);
 static void enc_free(jsmpeg_hip_encoder_t *e) {
 	if (!e) return;
 	hipSetDevice(e->device);
 	if (e->pending) hipEventSynchronize(e->ev_done);
 	hipFree(e->d_tables); hipFree(e->d_pics); hipFree(e->d_mb); hipFree(e->d_slice); hipFree(e->d_result); hipFree(e->d_es); hipFree(e->d_store);
 	enc_free_gop(e);
+	enc_free_rate(e);
 	if (e->h_pics) hipHostFree(e->h_pics);
 	if (e->h_result) hipHostFree(e->h_result);
 	for (hipEvent_t &v : e->ev) if (v) hipEventDestroy(v);
@@ -406,6 +487,7 @@ extern "C" jsmpeg_hip_encoder_t *jsmpeg_hip_encoder_create(const jsmpeg_hip_enco
 	e->cw = e->mbw * 16; e->ch = e->mbh * 16;
 	e->frame_bytes = (uint64_t)e->cw * e->ch * 3 / 2;
 	e->gop = 1; e->search = 0;
+	e->q_min = 1; e->q_max = JM_ENCR_MAX_Q; e->i_weight = 1;
 	if (enc_alloc(e) != 0) { enc_free(e); return nullptr; }
 	return e;
 }
@@ -465,7 +547,40 @@ extern "C" int jsmpeg_hip_encoder_set_gop(jsmpeg_hip_encoder_t *e, uint32_t gop,
 	return 0;
 }
 
-/* the gop > 1 pass between ev[1] and ev[3]; `a` is complete */
+static void enc_free_rate(jsmpeg_hip_encoder_t *e) {
+	hipFree(e->d_rate_rec); hipFree(e->d_rate_slice); hipFree(e->d_rate_out);
+	if (e->h_rate) hipHostFree(e->h_rate);
+	e->d_rate_rec = nullptr; e->d_rate_slice = nullptr; e->d_rate_out = nullptr; e->h_rate = nullptr;
+	e->rate_ready = false;
+}
+
+/* the stores only rate control needs; the caller frees what a failure leaves behind (enc_free_rate) */
+static int enc_alloc_rate(jsmpeg_hip_encoder_t *e) {
+	const size_t mbs = (size_t)e->mbw * e->mbh, np = e->cfg.max_pictures;
+	HIP_TRY(hipSetDevice(e->device));
+	HIP_TRY(jm_malloc(&e->d_rate_rec, sizeof(uint16_t) * JM_ENCR_MAX_Q * mbs * np));
+	HIP_TRY(jm_malloc(&e->d_rate_slice, sizeof(uint32_t) * JM_ENCR_MAX_Q * e->mbh * np));
+	HIP_TRY(jm_malloc(&e->d_rate_out, sizeof(uint32_t) * 4 * np));
+	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_rate), sizeof(uint32_t) * 4 * np, hipHostMallocDefault));
+	e->rate_ready = true;
+	return 0;
+}
+
+extern "C" int jsmpeg_hip_encoder_set_rate(jsmpeg_hip_encoder_t *e, uint32_t bytes_per_picture, uint32_t q_min, uint32_t q_max, uint32_t i_weight) {
+	g_err[0] = 0;
+	if (!e) return fail("encoder: NULL handle");
+	if (e->pending) return fail("encoder: an encode is in flight: jsmpeg_hip_encoder_sync (or a reader) settles it first");
+	if (q_min < 1 || q_max > JM_ENCR_MAX_Q || q_min > q_max) return fail("encoder: q_min %u, q_max %u: 1 <= q_min <= q_max <= 31 is needed", q_min, q_max);
+	if (i_weight < 1 || i_weight > 255) return fail("encoder: i_weight %u, must be 1 .. 255", i_weight);
+	if (bytes_per_picture) {                                                               /* on a failure the handle's rate stays as it was */
+		if (!e->gop_ready && enc_alloc_gop(e) != 0) { enc_free_gop(e); return -1; }
+		if (!e->rate_ready && enc_alloc_rate(e) != 0) { enc_free_rate(e); return -1; }
+	}
+	e->rate_bytes = bytes_per_picture; e->q_min = q_min; e->q_max = q_max; e->i_weight = i_weight;
+	return 0;
+}
+
+/* the level loop (gop > 1, or rate control) between ev[1] and ev[3]; `a` is complete */
 static int enc_run_gop(jsmpeg_hip_encoder_t *e, const JmEncArgs &a, uint32_t count, hipStream_t st) {
 	JmEncPArgs p;
 	p.recon = e->d_recon; p.frame_bytes = e->frame_bytes; p.pmb = e->d_pmb; p.ptables = e->d_ptables; p.list = e->d_list;
@@ -483,10 +598,18 @@ static int enc_run_gop(jsmpeg_hip_encoder_t *e, const JmEncArgs &a, uint32_t cou
 	}
 	HIP_TRY(hipMemcpyAsync(e->d_list, e->h_list, sizeof(uint32_t) * count, hipMemcpyHostToDevice, st));
 	const uint64_t mbs = (uint64_t)e->mbw * e->mbh;
+	JmEncRArgs r;
+	r.rec = e->d_rate_rec; r.slice = e->d_rate_slice; r.out = e->d_rate_out;
+	r.T = e->rate_bytes; r.q_min = e->q_min; r.nq = e->q_max - e->q_min + 1u; r.W = e->i_weight;
 	for (uint32_t l = 0; l < levels; l++) {
 		const uint32_t first = begin[l], n = begin[l + 1] - begin[l];
 		if (!n) continue;
 		if (l) k_enc_motion<<<dim3((uint32_t)((n * mbs + JM_ENC_MOTION_WAVES - 1) / JM_ENC_MOTION_WAVES)), dim3(64 * JM_ENC_MOTION_WAVES), 0, st>>>(a, p, first, n);
+		if (e->pass_rate) {
+			k_enc_rate_measure<<<dim3((uint32_t)((n * mbs + JM_ENC_LANES - 1) / JM_ENC_LANES)), dim3(JM_ENC_LANES), 0, st>>>(a, p, r, first, n);
+			k_enc_rate_scan<<<dim3((uint32_t)(((uint64_t)n * e->mbh * r.nq + 63) / 64)), dim3(64), 0, st>>>(a, p, r, first, n);
+			k_enc_rate_pick<<<dim3(n), dim3(64), 0, st>>>(a, p, r, first, n);
+		}
 		k_enc_measure_p<<<dim3((uint32_t)((n * mbs + JM_ENC_LANES - 1) / JM_ENC_LANES)), dim3(JM_ENC_LANES), 0, st>>>(a, p, first, n);
 	}
 	k_enc_scan_slices_p<<<dim3((count * e->mbh + 63) / 64), dim3(64), 0, st>>>(a, p);
@@ -497,6 +620,7 @@ static int enc_run_gop(jsmpeg_hip_encoder_t *e, const JmEncArgs &a, uint32_t cou
 	k_enc_write_p<<<dim3((uint32_t)((count * mbs + JM_ENC_LANES - 1) / JM_ENC_LANES)), dim3(JM_ENC_LANES), 0, st>>>(a, p);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(e->h_stats, e->d_stats, sizeof(uint32_t) * 4 * count, hipMemcpyDeviceToHost, st));
+	if (e->pass_rate) HIP_TRY(hipMemcpyAsync(e->h_rate, e->d_rate_out, sizeof(uint32_t) * 4 * count, hipMemcpyDeviceToHost, st));
 	return 0;
 }
 
@@ -531,6 +655,11 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 		p.stream = s; p.ordinal = ordinal; p.q = qscale ? qscale[k] : quantiser_scale;
 		p.last = (k + 1 == count || (stream && stream[k + 1] != s)) ? 1u : 0u;
 	}
+	for (uint32_t k = count, len = 0; k-- > 0;) {              /* m: the GOP's pictures, the stream's last GOP in the call cut short */
+		JmEncPic &p = e->h_pics[k];
+		if (p.last) len = p.ordinal + 1;
+		p.m = std::min(e->gop, len - (p.ordinal - p.ordinal % e->gop));
+	}
 	JmEncArgs a;
 	a.width = (uint32_t)e->cfg.width; a.height = (uint32_t)e->cfg.height; a.cw = e->cw; a.ch = e->ch; a.mbw = e->mbw; a.mbh = e->mbh;
 	a.count = count; a.frame_rate_code = e->cfg.frame_rate_code; a.end = (flags & JSMPEG_HIP_ENC_END) ? 1u : 0u;
@@ -549,7 +678,8 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 		k_enc_rgb<<<dim3((uint32_t)((quads + 255) / 256)), dim3(256), 0, st>>>(a, (const uint8_t *)dev_rgb, layout, order);
 	}
 	HIP_TRY(hipEventRecord(e->ev[1], st));
-	e->pass_gop = e->gop > 1;
+	e->pass_rate = e->rate_bytes != 0;
+	e->pass_gop = e->gop > 1 || e->pass_rate;
 	if (e->pass_gop) {
 		if (enc_run_gop(e, a, count, st) != 0) return -1;
 	} else {
@@ -645,6 +775,15 @@ extern "C" int jsmpeg_hip_encoder_picture_stats(jsmpeg_hip_encoder_t *e, uint32_
 	if (!out) return fail("encoder: NULL out");
 	const uint32_t mbs = e->mbw * e->mbh;
 	for (int i = 0; i < 4; i++) out[i] = e->pass_gop ? e->h_stats[(size_t)k * 4 + i] : (i == 0 ? mbs : 0u);
+	return 0;
+}
+
+extern "C" int jsmpeg_hip_encoder_picture_rate(jsmpeg_hip_encoder_t *e, uint32_t k, uint32_t out[3]) {
+	if (enc_ready(e) < 0) return -1;
+	if (!e->pass_rate) return fail("encoder: the last call ran with rate control off (jsmpeg_hip_encoder_set_rate)");
+	if (k >= e->count) return fail("encoder: picture %u of %u", k, e->count);
+	if (!out) return fail("encoder: NULL out");
+	for (int i = 0; i < 3; i++) out[i] = e->h_rate[(size_t)k * 4 + i];
 	return 0;
 }
 

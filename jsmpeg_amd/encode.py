@@ -1,7 +1,8 @@
 """The MPEG-1 encoder on the device (I pictures, or I + P with a GOP): the Python side of C ABI part 8 (include/jsmpeg_hip.h, jsmpeg_hip_encoder_*) and
 the host-side TS mux.  Frames in HBM (a Batch's pool, a Live tick's pictures, any device pointers) or uint8 RGB torch tensors
 -> elementary streams in a device buffer that Batch.attach_device takes as it is.  I pictures, or -- Encoder.set_gop -- I + P
-with motion search on the device and a closed loop; one quantiser scale per picture.  torch is imported only when a tensor is
+with motion search on the device and a closed loop; one quantiser scale per picture, the caller's or -- Encoder.set_rate --
+chosen on the device for a budget in bytes.  torch is imported only when a tensor is
 handed in."""
 import ctypes
 
@@ -14,7 +15,18 @@ END = 1
 SYMBOLS = ("jsmpeg_hip_encoder_create", "jsmpeg_hip_encoder_destroy", "jsmpeg_hip_encoder_encode", "jsmpeg_hip_encoder_encode_rgb",
            "jsmpeg_hip_encoder_sync", "jsmpeg_hip_encoder_query", "jsmpeg_hip_encoder_es", "jsmpeg_hip_encoder_stream_range",
            "jsmpeg_hip_encoder_picture_range", "jsmpeg_hip_encoder_read_es", "jsmpeg_hip_encoder_timings", "jsmpeg_hip_ts_mux_host",
-           "jsmpeg_hip_encoder_set_gop", "jsmpeg_hip_encoder_recon", "jsmpeg_hip_encoder_picture_stats")
+           "jsmpeg_hip_encoder_set_gop", "jsmpeg_hip_encoder_recon", "jsmpeg_hip_encoder_picture_stats",
+           "jsmpeg_hip_encoder_set_rate", "jsmpeg_hip_encoder_picture_rate")
+
+FRAME_RATES = {1: (24000, 1001), 2: (24, 1), 3: (25, 1), 4: (30000, 1001), 5: (30, 1), 6: (50, 1), 7: (60000, 1001), 8: (60, 1)}
+
+
+def bytes_per_picture(bits_per_second, frame_rate_code=5):
+    """the target of Encoder.set_rate for a bit rate: bits per second over 8 and the pictures per second of the sequence
+    header's frame_rate_code (0: 5, as the handle reads it), rounded down, at least 1"""
+    num, den = FRAME_RATES[frame_rate_code or 5]
+    return max(1, int(bits_per_second) * den // (8 * num))
+
 
 
 class EncoderConfig(ctypes.Structure):
@@ -59,6 +71,10 @@ def lib():
         L.jsmpeg_hip_encoder_recon.argtypes = [vp, u32]
         L.jsmpeg_hip_encoder_picture_stats.restype = ctypes.c_int
         L.jsmpeg_hip_encoder_picture_stats.argtypes = [vp, u32, ctypes.POINTER(u32)]
+        L.jsmpeg_hip_encoder_set_rate.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_set_rate.argtypes = [vp, u32, u32, u32, u32]
+        L.jsmpeg_hip_encoder_picture_rate.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_picture_rate.argtypes = [vp, u32, ctypes.POINTER(u32)]
         L.jsmpeg_hip_ts_mux_host.restype = ctypes.c_int64
         L.jsmpeg_hip_ts_mux_host.argtypes = [vp, vp, vp, vp, u32, u32, u32, ctypes.POINTER(ctypes.c_uint8), vp, u64]
         _bound = L
@@ -100,6 +116,7 @@ class Encoder:
         self.coded_width, self.coded_height = (width + 15) & ~15, (height + 15) & ~15
         self.frame_bytes = self.coded_width * self.coded_height * 3 // 2
         self.max_pictures, self.max_streams = max_pictures, max_streams
+        self.frame_rate_code = frame_rate_code or 5
         self.h = self.L.jsmpeg_hip_encoder_create(ctypes.byref(cfg))
         if not self.h:
             raise RuntimeError("jsmpeg_hip_encoder_create: " + _batch.last_error())
@@ -226,6 +243,21 @@ class Encoder:
         out = (ctypes.c_uint32 * 4)()
         self._ok(self.L.jsmpeg_hip_encoder_picture_stats(self.h, k, out))
         return dict(intra=int(out[0]), coded=int(out[1]), not_coded=int(out[2]), skipped=int(out[3]))
+
+    def set_rate(self, bytes_per_picture, q_min=1, q_max=31, i_weight=4):
+        """Rate control: 0 switches it off (the default; the qscale arguments hold).  Otherwise every GOP of a call has
+        bytes_per_picture bytes per picture, its I picture i_weight shares of them against one per P picture, and each
+        picture is coded at the smallest scale of q_min .. q_max at which it fits its budget, measured exactly on the device
+        (q_max if it fits at none).  State of the handle, like set_gop; bytes_per_picture(bits_per_second,
+        self.frame_rate_code) turns a bit rate into the target."""
+        self._ok(self.L.jsmpeg_hip_encoder_set_rate(self.h, bytes_per_picture, q_min, q_max, i_weight))
+
+    def picture_rate(self, k):
+        """what rate control chose for picture k of the last call: the scale, the budget in bytes (saturated to 32 bits) and
+        the picture's bytes"""
+        out = (ctypes.c_uint32 * 3)()
+        self._ok(self.L.jsmpeg_hip_encoder_picture_rate(self.h, k, out))
+        return dict(q=int(out[0]), budget=int(out[1]), bytes=int(out[2]))
 
     def sync(self):
         self._ok(self.L.jsmpeg_hip_encoder_sync(self.h))

@@ -5,13 +5,16 @@ read and write per picture against a plain device copy's rate measured in the sa
 against decode + encode (what a transcode costs).  A third step: Batch.tensor(uint8) -> encode_tensor -> decode, the luma PSNR
 against the first decode.  A fourth step, `gop`: 64 streams x 12 pictures of 1080p with --gop and --search (gop 1: the intra
 pass on the same pictures): ms per pass, the output bytes, and what Batch.decode takes on the encoder's streams; its figures go
-to the bench_gop<N>_r<R> section of profiles/enc_p_notes.md.
+to the bench_gop<N>_r<R> section of profiles/enc_p_notes.md.  A fifth step, `rate`: the same 768 pictures with --gop and --search
+at a fixed scale, with rate control over 1 .. 31 and over 4 .. 16 (--rate bytes per picture): ms per pass each way, and the
+registers, LDS and occupancy of the three rate kernels; its figures go to the bench section of profiles/enc_rate_notes.md.
 
 Every GPU step is a child process of this tool under its own `timeout`; the steps are chained and the tool stops at the first
 one that fails.  The figures go into the bench section of profiles/enc_notes.md (nothing is written for a step that did not
 run).
     python tools/encode_bench.py [--steps pool64,pool7680,tensor] [--reps 8]
-    python tools/encode_bench.py --steps gop --gop 12 --search 7"""
+    python tools/encode_bench.py --steps gop --gop 12 --search 7
+    python tools/encode_bench.py --steps rate --gop 12 --search 7 --rate 40000"""
 import argparse
 import json
 import os
@@ -26,7 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 W, H = 1920, 1080
-STEPS = {"pool64": 300, "pool7680": 420, "tensor": 120, "gop": 300}          # seconds each step may take
+STEPS = {"pool64": 300, "pool7680": 420, "tensor": 120, "gop": 300, "rate": 420}          # seconds each step may take
 
 
 def median(v):
@@ -166,6 +169,51 @@ def step_gop(gop, search, reps):
                         kinds=kinds, decode_of_output_wall_ms=median(dec))
 
 
+RATE_KERNELS = ("k_enc_rate_measure", "k_enc_rate_scan", "k_enc_rate_pick")
+
+
+def step_rate(gop, search, target, reps):
+    """64 streams x 12 pictures of 1080p from a batch's pool with a GOP: the pass at q = 8, with rate control over 1 .. 31 and
+    over 4 .. 16; what the compiler gave the three rate kernels (no device needed for that part)"""
+    import bench
+    from jsmpeg_amd import batch as jb
+    from jsmpeg_amd import build, encode
+    usage = build.check_kernel_resources()
+    kernels = {k: {n: v[n] for n in ("VGPRs", "LDS Size", "Occupancy", "ScratchSize")} for k in RATE_KERNELS for name, v in usage.items() if k in name}
+    streams = [g[0] for g in bench.generate_streams(0, 64, 12)]
+    total = sum(len(s) for s in streams)
+    with jb.Batch(W, H, 64, 768 + 8, total + 64 * 64 + 4096, device=0) as b:
+        b.upload(streams)
+        assert b.decode() == 768
+        infos = b.pictures()
+        pics = [p for p, i in enumerate(infos) if i.decoded]
+        sn = [infos[p].stream for p in pics]
+        ptrs = [b.frame_pool_ptr + p * b.frame_stride for p in pics]
+        ways = []
+        with encode.Encoder(W, H, len(pics), 64, 768 << 20, device=0) as enc:
+            enc.set_gop(gop, search)
+            for name, rule in (("fixed scale 8", None), ("rate control, 1 .. 31", (target, 1, 31, 4)), ("rate control, 4 .. 16", (target, 4, 16, 4))):
+                enc.set_rate(*(rule or (0,)))
+                wall, split = [], []
+                for r in range(reps + 2):
+                    t0 = time.perf_counter()
+                    enc.encode(ptrs, sn, 8)
+                    enc.sync()
+                    if r >= 2:
+                        wall.append((time.perf_counter() - t0) * 1e3)
+                        split.append(enc.timings())
+                ms = [s["total_ms"] for s in split]
+                way = dict(name=name, wall_ms=median(wall), measure_scan_ms=median([s["measure_ms"] for s in split]), write_ms=median([s["write_ms"] for s in split]),
+                           total_ms=median(ms), total_ms_min=round(min(ms), 3), total_ms_max=round(max(ms), 3), output_bytes=int(enc.device_es()[1]))
+                if rule:
+                    chosen = [enc.picture_rate(k) for k in range(len(pics))]
+                    way["picture_bytes"] = sum(c["bytes"] for c in chosen)
+                    way["over_budget"] = sum(1 for c in chosen if c["bytes"] > c["budget"])
+                    way["q_mean"] = round(float(np.mean([c["q"] for c in chosen])), 2)
+                ways.append(way)
+        return dict(step="rate", gop=gop, search=search, target=target, pictures=len(pics), streams=64, ways=ways, kernels=kernels)
+
+
 def step_tensor():
     import torch
     import enc_inputs as ei
@@ -190,7 +238,19 @@ def step_tensor():
 def notes(results):
     lines = ["## Cost on the MI355X (measured by tools/encode_bench.py)", ""]
     for r in results:
-        if r["step"] == "gop":
+        if r["step"] == "rate":
+            lines = ["## Cost on the MI355X: gop %d, search range %d, %d pictures of 1080p in %d streams, target %d bytes per picture (measured by tools/encode_bench.py)"
+                     % (r["gop"], r["search"], r["pictures"], r["streams"], r["target"]), "",
+                     "| | call + sync, host clock, ms | measure + scan (the level loop), ms | write, ms | total, median (min .. max), ms | output bytes | pictures' bytes of %d | over budget | mean q |" % (r["pictures"] * r["target"]),
+                     "|---|---|---|---|---|---|---|---|---|"]
+            for w in r["ways"]:
+                lines.append("| %s | %.3f | %.3f | %.3f | %.3f (%.3f .. %.3f) | %d | %s | %s | %s |" % (
+                    w["name"], w["wall_ms"], w["measure_scan_ms"], w["write_ms"], w["total_ms"], w["total_ms_min"], w["total_ms_max"], w["output_bytes"],
+                    w.get("picture_bytes", ""), w.get("over_budget", ""), w.get("q_mean", "")))
+            lines += ["", "| kernel | VGPRs | LDS bytes | occupancy (waves per SIMD) | scratch |", "|---|---|---|---|---|"]
+            lines += ["| %s | %d | %d | %d | %d |" % (k, v["VGPRs"], v["LDS Size"], v["Occupancy"], v["ScratchSize"]) for k, v in r["kernels"].items()]
+            lines.append("")
+        elif r["step"] == "gop":
             lines = ["## gop %d, search range %d: %d pictures of 1080p in %d streams, q = %d (measured by tools/encode_bench.py)" % (r["gop"], r["search"], r["pictures"], r["streams"], r["q"]), "",
                      "| | ms |", "|---|---|",
                      "| call + sync, host clock | %.3f |" % r["wall_ms"],
@@ -226,16 +286,17 @@ def main():
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--gop", type=int, default=12, help="the gop step: GOP length (1: the intra pass)")
     ap.add_argument("--search", type=int, default=7, help="the gop step: full-pel search range 0 .. 15")
+    ap.add_argument("--rate", type=int, default=40000, help="the rate step: target bytes per picture")
     ap.add_argument("--child")
     a = ap.parse_args()
     if a.child:
-        r = step_gop(a.gop, a.search, a.reps) if a.child == "gop" else step_tensor() if a.child == "tensor" else step_pool(a.child == "pool7680", a.reps)
+        r = step_rate(a.gop, a.search, a.rate, a.reps) if a.child == "rate" else step_gop(a.gop, a.search, a.reps) if a.child == "gop" else step_tensor() if a.child == "tensor" else step_pool(a.child == "pool7680", a.reps)
         print("RESULT " + json.dumps(r), flush=True)
         return 0
     results = []
     for step in a.steps.split(","):
         cmd = ["timeout", "-k", "10", str(STEPS[step]), sys.executable, os.path.abspath(__file__), "--child", step, "--reps", str(a.reps),
-               "--gop", str(a.gop), "--search", str(a.search)]
+               "--gop", str(a.gop), "--search", str(a.search), "--rate", str(a.rate)]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
         if p.returncode != 0 or not line:
@@ -247,7 +308,9 @@ def main():
     from enc_quality import NOTES, replace_section
     for r in [r for r in results if r["step"] == "gop"]:
         replace_section(os.path.join(ROOT, "profiles", "enc_p_notes.md"), "bench_gop%d_r%d" % (r["gop"], r["search"]), notes([r]))
-    results = [r for r in results if r["step"] != "gop"]
+    for r in [r for r in results if r["step"] == "rate"]:
+        replace_section(os.path.join(ROOT, "profiles", "enc_rate_notes.md"), "bench", notes([r]))
+    results = [r for r in results if r["step"] not in ("gop", "rate")]
     if results:
         replace_section(NOTES, "bench", notes(results))
     return 0 if done == len(a.steps.split(",")) else 1
