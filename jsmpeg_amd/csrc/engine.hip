@@ -307,6 +307,7 @@ static int upload_ts_impl(jsmpeg_hip_batch_t *b, uint32_t n_streams, const uint8
 	 * back from a 16-byte aligned start, 16 readable bytes behind each stream */
 	std::vector<std::vector<JmTsRun>> runs(n_streams);
 	std::vector<uint64_t> begin(n_streams), len(n_streams);
+	std::vector<JmTsWriteEnd> ends;
 	b->ts_pkt_first.assign(n_streams + 1, 0);
 	uint64_t off = 0;
 	uint32_t max_packets = 0;
@@ -315,8 +316,11 @@ static int upload_ts_impl(jsmpeg_hip_batch_t *b, uint32_t n_streams, const uint8
 		const uint32_t nw = n_writes ? n_writes[i] : 0;
 		/* with a write table, zero writes deliver nothing (bytes beyond the writes are never written); without one the
 		 * whole buffer is one write */
-		const uint64_t pk = n_writes && nw == 0 ? 0 : jm_ts_sync_runs(ts[i], ts_bytes[i], nw ? wb : nullptr, nw, runs[i], nullptr);
+		const uint64_t pk = n_writes && nw == 0 ? 0 : jm_ts_sync_runs(ts[i], ts_bytes[i], nw ? wb : nullptr, nw, runs[i], nullptr, &ends);
 		if (n_writes) wb += nw;
+		/* the kernels parse framed packets: refuse the input for which that is not what ts.js parses (ts_sync.h) */
+		const int64_t bad = pk ? jm_ts_header_spill_differs(ts[i], runs[i], ends) : -1;
+		if (bad >= 0) return fail("stream %u: TS packet %lld: a payload start reads past the packet's end, and what follows it in the written bytes is not the next packet", i, (long long)bad);
 		begin[i] = off; len[i] = pk * 188;
 		off += (len[i] + 16 + 15) & ~15ull;
 		if (b->ts_pkt_first[i] + pk > 0x3fffffffull) return fail("too many TS packets in one batch");

@@ -426,7 +426,7 @@ extern "C" int jsmpeg_hip_ts_demux_host(const uint8_t *ts, uint64_t ts_bytes, co
 		const uint64_t n = std::min(write_bytes[w], ts_bytes - at);
 		live_ts_feed(T, ts + at, n, stream_id, [&](double p, const uint8_t *pes, uint32_t m) {
 			if (calls < cap) { if (pts) pts[calls] = p; if (offset) offset[calls] = total; if (length) length[calls] = m; }
-			if (es && total + m <= es_cap) memcpy(es + total, pes, m);
+			if (es && m && total + m <= es_cap) memcpy(es + total, pes, m);
 			total += m; calls++;
 		});
 		at += n;

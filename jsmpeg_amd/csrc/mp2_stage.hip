@@ -281,11 +281,14 @@ extern "C" int jsmpeg_hip_mp2_batch_upload_ts(jsmpeg_hip_mp2_batch_t *b, uint32_
 	MP2_TRY(hipSetDevice(b->device));
 	std::vector<uint64_t> begin(n_streams), len(n_streams);
 	std::vector<std::vector<JmTsRun>> runs(n_streams);       /* where ts.js's packets lie (sync, resync: ts_sync.h) */
+	std::vector<JmTsWriteEnd> ends;
 	b->ts_pkt_first.assign(n_streams + 1, 0);
 	uint64_t off = 0;
 	uint32_t max_packets = 0;
 	for (uint32_t i = 0; i < n_streams; i++) {
-		const uint64_t pk = jm_ts_sync_runs(ts[i], ts_bytes[i], nullptr, 0, runs[i], nullptr);
+		const uint64_t pk = jm_ts_sync_runs(ts[i], ts_bytes[i], nullptr, 0, runs[i], nullptr, &ends);
+		const int64_t bad = pk ? jm_ts_header_spill_differs(ts[i], runs[i], ends) : -1;      /* as in jsmpeg_hip_batch_upload_ts */
+		if (bad >= 0) return mp2_fail("stream %s%ld: a payload start reads past the packet's end, and what follows it in the written bytes is not the next packet", "", i);
 		begin[i] = off; len[i] = pk * 188;
 		off += (len[i] + 16 + 15) & ~15ull;                    /* 16-byte aligned regions, 16 readable bytes behind each */
 		if (b->ts_pkt_first[i] + pk > 0x3fffffffull) return mp2_fail("too many TS packets in one batch");

@@ -15,7 +15,7 @@
 struct LiveTs {
 	std::vector<uint8_t> left;                         /* leftoverBytes */
 	std::vector<std::pair<uint16_t, uint8_t>> pids;    /* pidsToStreamIds */
-	uint32_t cur_len, total_len;                       /* pesPacketInfo[stream id]: currentLength, totalLength, pts, buffers */
+	int64_t cur_len, total_len;                        /* pesPacketInfo[stream id]: currentLength, totalLength, pts, buffers */
 	double pts;
 	std::vector<uint8_t> pes;
 	std::vector<uint8_t> joined;                       /* scratch: leftover + the new bytes */
@@ -53,29 +53,33 @@ static void live_ts_feed(LiveTs &T, const uint8_t *buf, uint64_t len, uint32_t s
 			for (const auto &e : T.pids) if (e.first == pid) sid = e.second;
 			if (start && sid == stream_id && T.cur_len) complete();        /* a new payload of the stream: the frame before it is over (ts.js:65-73) */
 			if (!(af & 1)) continue;
-			uint32_t at = 4;
-			if (af & 2) at = 5u + p[4];
-			if (at >= 188) continue;                                        /* (a header that runs past its packet: outside what a muxer writes; nothing of it is payload) */
-			if (start && at + 9 <= 188 && p[at] == 0 && p[at + 1] == 0 && p[at + 2] == 1) {
-				sid = p[at + 3];
+			/* the header fields are read like ts.js reads them: on in the buffer of this write() where they run past the packet,
+			 * as zeros behind its end -- and a start code is also "seen" at the end of the buffer (buffer.js:140-150) */
+			const uint64_t o = r.src + 188ull * k;
+			auto byte = [&](uint64_t i) -> uint32_t { return i < len ? buf[i] : 0u; };
+			uint64_t at = o + 4;
+			if (af & 2) at = o + 5 + p[4];
+			if (start && (at >= len || (buf[at] == 0 && at + 2 < len && buf[at + 1] == 0 && buf[at + 2] == 1))) {
+				sid = byte(at + 3);
 				bool known = false;
 				for (auto &e : T.pids) if (e.first == pid) { e.second = (uint8_t)sid; known = true; }
 				if (!known) T.pids.push_back({ pid, (uint8_t)sid });
-				const uint32_t packet_length = ((uint32_t)p[at + 4] << 8) | p[at + 5], flags = p[at + 7] >> 6, header_length = p[at + 8];
+				const uint32_t packet_length = (byte(at + 4) << 8) | byte(at + 5), flags = byte(at + 7) >> 6, header_length = byte(at + 8);
 				if (sid == stream_id) {
 					double pts = 0;
-					if ((flags & 2) && at + 14 <= 188) {                    /* the 33-bit PTS in its five bytes (ts.js:96-113) */
-						const uint8_t *q = p + at + 9;
-						const double p32_30 = (q[0] >> 1) & 7, p29_15 = (((uint32_t)q[1] << 8) | q[2]) >> 1, p14_0 = (((uint32_t)q[3] << 8) | q[4]) >> 1;
+					if (flags & 2) {                                        /* the 33-bit PTS in its five bytes (ts.js:96-113) */
+						const double p32_30 = (byte(at + 9) >> 1) & 7, p29_15 = ((byte(at + 10) << 8) | byte(at + 11)) >> 1,
+						             p14_0 = ((byte(at + 12) << 8) | byte(at + 13)) >> 1;
 						pts = (p32_30 * 1073741824.0 + p29_15 * 32768.0 + p14_0) / 90000.0;
 					}
-					T.total_len = packet_length ? packet_length - header_length - 3 : 0;      /* packetStart (ts.js:189-193) */
+					T.total_len = packet_length ? (int64_t)packet_length - (int64_t)header_length - 3 : 0;      /* packetStart (ts.js:189-193); may be negative */
 					T.cur_len = 0; T.pts = pts;
 				}
 				at += 9 + header_length;
 			}
 			if (sid != stream_id) continue;
-			if (at < 188) { T.pes.insert(T.pes.end(), p + at, p + 188); T.cur_len += 188 - at; }
+			if (at < o + 188) T.pes.insert(T.pes.end(), buf + at, buf + o + 188);
+			T.cur_len += (int64_t)(o + 188) - (int64_t)at;                 /* a header past its packet adds no bytes, but the length still moves (ts.js:195-199) */
 			const bool full = T.total_len != 0 && T.cur_len >= T.total_len;
 			const bool padded = !start && (af & 2);                                     /* the video frame end guess (ts.js:127-147) */
 			if (full || padded) complete();

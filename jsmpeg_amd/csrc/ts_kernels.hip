@@ -18,8 +18,13 @@
  * Contract (checked, reported per stream in `status`): packets start at multiples of 188 bytes from the
  * first byte -- a missing sync byte is an error here, not a resync (ts.js:150-187 is inherently serial
  * over bytes; feed such input through ts.js).  A trailing partial packet is ignored like ts.js keeps it
- * as leftover.  Header fields that run past their packet read the following bytes of the stream, like
- * the reference reading on in its buffer.
+ * as leftover.  Header fields that run past their packet read the following bytes of the FRAMED stream
+ * (the next packet; nothing behind the last one: there a start code is "seen" and the fields read 0, like
+ * buffer.js:140-150 at the end of its buffer).  ts.js reads on in the bytes of the current write() instead:
+ * where those differ for a payload start -- junk or a partial packet behind it, the end of an inner
+ * write() -- the host refuses the input before anything is launched (jm_ts_header_spill_differs,
+ * ts_sync.h).  Also refused, through `status`: a PES / adaptation-field header of the connected stream that
+ * puts the payload behind the packet's end (3), and more than JM_TS_PIDS PIDs with PES headers (2).
  */
 #include "kernels.h"
 

@@ -63,3 +63,13 @@ def oracle_ts_demux(oracle_path, ts, stream_id=0xE0, write_sizes=None):
     if n < 0 or n > cap:
         raise RuntimeError("ts_oracle_demux failed (%d)" % n)
     return es[:n_es.value].copy(), [(writes[i].pts, writes[i].offset, writes[i].length) for i in range(n)]
+
+
+def oracle_ts_write_reasons(oracle_path):
+    """CHECKER ONLY: why each destination.write call of the LAST oracle_ts_demux was made -- 1: the next payload start
+    (ts.js:65-69), 2: PES_packet_length reached, 4: the frame-end guess of a stuffed packet (6: both)."""
+    lib = ctypes.CDLL(oracle_path)
+    n = lib.ts_oracle_write_reasons(None, 0)
+    out = np.zeros(max(1, n), dtype=np.uint8)
+    lib.ts_oracle_write_reasons(ctypes.c_void_p(out.ctypes.data), ctypes.c_int(n))
+    return [int(x) for x in out[:n]]

@@ -47,7 +47,12 @@ typedef struct {
 	int overflow;
 } demux_t;
 
-static void packet_complete(demux_t *d) {                                                               /* ts.js:205-210 */
+/* test hook: why each destination.write call of the last demux was made (1: the next payload start, ts.js:65-69;
+ * 2: PES_packet_length reached; 4: the frame-end guess of a stuffed packet, ts.js:143-146 -- 6 where both held) */
+static uint8_t g_reason[1 << 16]; static int g_n_reason;
+
+static void packet_complete(demux_t *d, int reason) {                                                   /* ts.js:205-210 */
+	if (d->n_writes >= 0 && d->n_writes < (int)sizeof(g_reason)) { g_reason[d->n_writes] = (uint8_t)reason; g_n_reason = d->n_writes + 1; }
 	if (d->n_writes < d->writes_cap) {
 		d->writes[d->n_writes].pts = d->pts;
 		d->writes[d->n_writes].offset = (uint32_t)d->pending_begin;
@@ -88,7 +93,7 @@ static int parse_packet(demux_t *d, bits_t *s) {                                
 
 	int stream_id = d->pid_to_sid[pid];
 	if (payload_start && stream_id) {
-		if (stream_id == d->connected_id && d->current_length) packet_complete(d);
+		if (stream_id == d->connected_id && d->current_length) packet_complete(d, 1);
 	}
 	if (adaptation_field & 1) {
 		if (adaptation_field & 2) {
@@ -133,7 +138,7 @@ static int parse_packet(demux_t *d, bits_t *s) {                                
 			d->current_length += (long)end - (long)start;
 			const int complete = d->total_length != 0 && d->current_length >= d->total_length;
 			const int has_padding = !payload_start && (adaptation_field & 2);
-			if (complete || has_padding) packet_complete(d);      /* guessVideoFrameEnd is always true, ts.js:11 */
+			if (complete || has_padding) packet_complete(d, (complete ? 2 : 0) | (has_padding ? 4 : 0));      /* guessVideoFrameEnd is always true, ts.js:11 */
 		}
 	}
 	s->index = end << 3;
@@ -146,7 +151,7 @@ static int parse_packet(demux_t *d, bits_t *s) {                                
 int ts_oracle_demux(const uint8_t *ts, size_t n, int stream_id, uint8_t *es_out, size_t es_cap, size_t *es_bytes,
                     ts_oracle_write_t *writes, int writes_cap) {
 	static demux_t d;
-	memset(&d, 0, sizeof(d));
+	memset(&d, 0, sizeof(d)); g_n_reason = 0;
 	d.connected_id = stream_id; d.es = es_out; d.es_cap = es_cap; d.writes = writes; d.writes_cap = writes_cap;
 	bits_t s = { ts, n, 0 };
 	while (bits_has(&s, 188 << 3) && parse_packet(&d, &s)) {}
@@ -159,7 +164,7 @@ int ts_oracle_demux(const uint8_t *ts, size_t n, int stream_id, uint8_t *es_out,
 int ts_oracle_demux_writes(const uint8_t *ts, size_t n, const uint64_t *write_bytes, int n_writes, int stream_id, uint8_t *es_out,
                            size_t es_cap, size_t *es_bytes, ts_oracle_write_t *writes, int writes_cap) {
 	static demux_t d;
-	memset(&d, 0, sizeof(d));
+	memset(&d, 0, sizeof(d)); g_n_reason = 0;
 	d.connected_id = stream_id; d.es = es_out; d.es_cap = es_cap; d.writes = writes; d.writes_cap = writes_cap;
 	size_t leftover = 0, end = 0;
 	for (int w = 0; w < n_writes; w++) {
@@ -174,13 +179,20 @@ int ts_oracle_demux_writes(const uint8_t *ts, size_t n, const uint64_t *write_by
 	return d.overflow && d.es_len > es_cap ? -1 : d.n_writes;
 }
 
+/* The reasons (see g_reason) of the destination.write calls of the last ts_oracle_demux / ts_oracle_demux_writes;
+ * returns their number (fills at most cap). */
+int ts_oracle_write_reasons(uint8_t *out, int cap) {
+	for (int i = 0; i < g_n_reason && i < cap; i++) out[i] = g_reason[i];
+	return g_n_reason;
+}
+
 /* The packets ts.js parses (byte offsets of their sync bytes) and the leftover position, for the framing tests of the
  * ingest stage's host pre-pass.  Returns the number of packets. */
 long ts_oracle_packets(const uint8_t *ts, size_t n, const uint64_t *write_bytes, int n_writes, uint64_t *packet_at, size_t cap,
                        uint64_t *leftover_at) {
 	static demux_t d;
 	static uint8_t sink[1 << 16];
-	memset(&d, 0, sizeof(d));
+	memset(&d, 0, sizeof(d)); g_n_reason = 0;
 	d.connected_id = 0xE0; d.es = sink; d.es_cap = 0; d.writes = NULL; d.writes_cap = 0;
 	g_packet_at = packet_at; g_packet_cap = cap; g_packet_n = 0; g_packet_base = ts;
 	static uint64_t one_dummy;

@@ -5,6 +5,7 @@ Ingest side.  Each crafted TS (tests/ts_craft.py, deterministic
      connected -- and, for the cases of ts_craft.WRITES, the same buffer in several write() calls (leftover bytes);
   2. the CPU restatement oracle/ts_oracle.c.
 The fixture (md5 of the TS, and per destination.write call its pts, byte count and md5) is written only if both agree.
+The cases of ts_craft.REFUSED -- input the device demux refuses with a message -- become excluded_ts_*.json.
 
     python tests/golden/make_golden_ts.py
 """
@@ -50,6 +51,10 @@ def one(name, ts, write_sizes):
     if write_sizes:
         out["write_sizes"] = write_sizes
         fname = "ts_%s__in_%d_writes.json" % (name, len(write_sizes))
+    refused = ts_craft.REFUSED.get((name, bool(write_sizes)))
+    if refused:                    # ts.js and the restatement agree on it; the device demux refuses it (not in the ts_*.json glob)
+        out["refused"] = refused
+        fname = "excluded_" + fname
     with open(os.path.join(HERE, fname), "w") as fh:
         json.dump(out, fh, indent=1)
     print(fname, "ok:", len(mine), "writes,", sum(w["length"] for w in mine), "bytes")

@@ -1,7 +1,11 @@
 """Ingest side: MPEG-TS demux with the reference's semantics (src/ts.js:25-210).
 The fixtures tests/golden/ts_*.json were agreed between the unmodified ts.js under Node and the CPU restatement
 (tests/golden/make_golden_ts.py).  CPU tests pin the restatement; GPU tests compare the device demux (k_ts_* behind
-jsmpeg_hip_batch_upload_ts) with both, then decode what it left in HBM."""
+jsmpeg_hip_batch_upload_ts) with both, then decode what it left in HBM.
+The device demux is held to ts.js at the edges of its own structure too: the scripted cases of tests/ts_craft.py (state
+carried between the 256-packet chunks of k_ts_walk, lookups across waves, the candidate walk in groups of eight, 33-bit
+PTS, the 16-PID limit) are fixtures here, tests/test_ts_walk_cases.py proves their placement on the CPU, and
+tests/test_gpu_ts_walk.py adds the input it must refuse and a random sweep of ragged batches against the restatement."""
 import glob
 import hashlib
 import json
