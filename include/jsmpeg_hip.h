@@ -789,10 +789,11 @@ int jsmpeg_hip_live_render_tensor_latest(jsmpeg_hip_live_t *l, const uint32_t *s
  * every I picture -- with gop 1, the default, every picture -- is a joining point for a viewer and a unit for
  * jsmpeg_hip_split_gops.  Streams lie in the output from 16-byte aligned begins with 0xff in front of the first, between them
  * (8 bytes or more) and 256 bytes behind the last: the buffer can be handed to jsmpeg_hip_batch_attach_device as it is.
- * P CHAINS DO NOT CROSS CALLS: every stream of a call begins with an I picture, whatever the call before ended with (a live
- * stream that goes on pays one I picture per call).  Batch STREAMS, not pictures: a P picture waits for the picture before it,
+ * P CHAINS CROSS CALLS ONLY WHEN ASKED: without JSMPEG_HIP_ENC_CHAIN every stream of a call begins with an I picture, whatever
+ * the call before ended with; with it a stream goes on where its last chained call left it (below, at the flag) -- a live relay
+ * that encodes one picture per stream and tick gets its GOPs and its rate control that way.  Batch STREAMS, not pictures: a P picture waits for the picture before it,
  * so a call with one stream runs one picture at a time on the device.
- * OUT OF SCOPE: B pictures, quantiser changes inside a picture, a VBV model, custom matrices, P chains across calls, vectors
+ * OUT OF SCOPE: B pictures, quantiser changes inside a picture, a VBV model, custom matrices, vectors
  * beyond +-15 pels, a Node binding, resizing of YCbCr (resize the RGB tensor).
  * A pass is a PURE ENQUEUE on hip_stream, like jsmpeg_hip_batch_enqueue: every size and offset is worked out on the device; the
  * host waits in jsmpeg_hip_encoder_sync and the readers only (they settle the pass first).  One pass at a time per handle: a
@@ -811,6 +812,33 @@ typedef struct jsmpeg_hip_encoder_config_t {
 	int32_t device;               /* -1: current */
 } jsmpeg_hip_encoder_config_t;
 #define JSMPEG_HIP_ENC_END 1u     /* close every stream of the call with a sequence end code */
+/* CONTINUE the call's streams (the rule: jsmpeg_amd/csrc/enc_chain.h).  The handle keeps, per stream number below max_streams,
+ * whether the stream has chain state and how many pictures it has coded; the stream NUMBER is the stream's identity from call
+ * to call (numbers still ascend within a call and may have gaps).  In a call with this flag the first picture of stream s has
+ * the ordinal the stream's last chained call left (0 for a stream without state), and the ordinal drives the level in the GOP,
+ * the picture type, the temporal reference and the GOP's time code as in one call over all the pictures: the call's first
+ * picture of s is a P picture -- predicted from the reconstruction the call before left on the device -- unless that ordinal
+ * is a multiple of gop.  The pieces of a stream, concatenated in call order, ARE the stream one call over all its pictures
+ * writes (with rate control: when m below is gop for every picture, that is when every GOP is complete).  Still a pure enqueue:
+ * the host needs nothing from the device for it.  A call without the flag neither reads nor writes this state and is byte for
+ * byte what it was.
+ * A PIECE THAT BEGINS WITH A P PICTURE begins at its picture start code (jsmpeg_hip_encoder_stream_range, _picture_range): it is
+ * for concatenation, or for a live stream that already holds the sequence header -- not for jsmpeg_hip_batch_attach_device or
+ * jsmpeg_hip_split_gops on its own.
+ * A stream's chain ENDS, so that its next picture has ordinal 0 and is an I picture with sequence and GOP header: by
+ * JSMPEG_HIP_ENC_END together with this flag (the end code is written, then every stream of the call is reset); by
+ * jsmpeg_hip_encoder_chain_reset; by jsmpeg_hip_encoder_set_gop (every stream); by a chained call that overflowed (every
+ * stream of that call, when the pass is settled).  Before an ordinal would pass 2^32 - 1 a GOP begins at ordinal 0 again: the
+ * first multiple of gop above 2^32 - 1025 is replaced by 0.
+ * RATE CONTROL in a chained call budgets every GOP for gop pictures (m = gop: later calls are taken to complete it, the call's
+ * last GOP is not cut short), and the bytes a GOP's pictures took in earlier calls count as spent whichever call coded them --
+ * kept on the device, written by a stream's last picture of a call.  Only calls with rate control keep that sum: bytes coded
+ * by a chained call without it, and those of the same GOP before them, are not counted.  jsmpeg_hip_encoder_set_rate does
+ * not reset chains; the rule runs with the handle's values at the time of the call.  Budgets still do not carry from GOP to GOP.
+ * EXTRA DEVICE MEMORY, allocated by the first chained call with gop > 1 or rate control: two reconstructed frames and 16 bytes
+ * per stream number of max_streams.  A stream's last picture of a chained call is reconstructed there (jsmpeg_hip_encoder_recon
+ * returns that address); nothing is copied. */
+#define JSMPEG_HIP_ENC_CHAIN 2u
 
 jsmpeg_hip_encoder_t *jsmpeg_hip_encoder_create(const jsmpeg_hip_encoder_config_t *config);
 void jsmpeg_hip_encoder_destroy(jsmpeg_hip_encoder_t *enc);
@@ -837,20 +865,29 @@ int jsmpeg_hip_encoder_timings(jsmpeg_hip_encoder_t *enc, float out_ms[4]);     
  * of the picture before -- exactly the frame a decoder holds.  jsmpeg_hip_encoder_picture_range of a P picture begins at its
  * picture start code.  search_range: full-pel radius 0 .. 15; 0 = zero vectors only, no half-pel step (conditional
  * replenishment); forward_f_code is 1 up to 7 and 2 above.  Refused while a pass is in flight, for gop 0, gop > 1024,
- * search_range > 15.  The stores only a GOP needs -- a reconstructed frame per picture of a call, the macroblocks' motion
+ * search_range > 15.  Ends every stream's chain (JSMPEG_HIP_ENC_CHAIN).  The stores only a GOP needs -- a reconstructed frame per picture of a call, the macroblocks' motion
  * records -- are allocated by the first call that asks for gop > 1. */
 int jsmpeg_hip_encoder_set_gop(jsmpeg_hip_encoder_t *enc, uint32_t gop, uint32_t search_range);
-/* device pointer of picture k's reconstruction in the last call (Y | Cr | Cb, coded size); NULL with a message when gop is 1 */
+/* device pointer of picture k's reconstruction in the last call (Y | Cr | Cb, coded size), wherever it lies: the call's store, or
+ * -- a chained stream's last picture -- the stream's carry frame, which the stream's next chained call reads and the one after
+ * that overwrites; NULL with a message when gop is 1 */
 const void *jsmpeg_hip_encoder_recon(jsmpeg_hip_encoder_t *enc, uint32_t k);
 /* macroblocks of picture k by kind: intra, predicted + coded, predicted not coded, skipped */
 int jsmpeg_hip_encoder_picture_stats(jsmpeg_hip_encoder_t *enc, uint32_t k, uint32_t out[4]);
+/* ends the chain of `stream` (UINT32_MAX: of every stream): its next chained picture is an I picture with ordinal 0 -- how a
+ * relay gives a joining viewer a picture to start from, or drops a stream.  Refused while a pass is in flight and for a
+ * stream >= max_streams. */
+int jsmpeg_hip_encoder_chain_reset(jsmpeg_hip_encoder_t *enc, uint32_t stream);
+/* out[0]: whether `stream` has chain state; out[1]: the pictures it has coded = the ordinal of its next chained picture.
+ * Settles a pass in flight first (an overflow resets the call's streams). */
+int jsmpeg_hip_encoder_chain_info(jsmpeg_hip_encoder_t *enc, uint32_t stream, uint32_t out[2]);
 /* RATE CONTROL: the quantiser scale of every picture chosen on the device, still a pure enqueue.  bytes_per_picture 0 (the
  * default) switches it off: the scales are the caller's and every stream is what it was.  Otherwise, with m the pictures of a
- * picture's GOP in the call (a stream's last GOP may be short; gop 1: m = 1), the GOP has m * bytes_per_picture bytes; its I
+ * picture's GOP in the call (a stream's last GOP may be short; gop 1: m = 1; in a chained call m = gop), the GOP has m * bytes_per_picture bytes; its I
  * picture gets the share i_weight / (i_weight + m - 1) of them, each P picture an equal share of what the pictures before it
  * left, and a picture is coded at the SMALLEST scale of q_min .. q_max at which it is at most its budget -- measured exactly
  * at every scale of the range, jsmpeg_hip_encoder_picture_range's bytes -- or at q_max if it is at none (the rule, in integers:
- * jsmpeg_amd/csrc/enc_rate.h).  Budgets carry neither from GOP to GOP nor from call to call; no VBV model, the headers stay as
+ * jsmpeg_amd/csrc/enc_rate.h).  Budgets do not carry from GOP to GOP, and from call to call only with JSMPEG_HIP_ENC_CHAIN; no VBV model, the headers stay as
  * they are.  State of the handle like the GOP; while on, the qscale / quantiser_scale arguments of the encode calls are checked
  * as before and otherwise unused, the pass is the GOP's also at gop 1 (jsmpeg_hip_encoder_recon works), and 62 bytes per
  * macroblock of max_pictures pictures are allocated by the first call that switches it on (with the GOP's stores, if they

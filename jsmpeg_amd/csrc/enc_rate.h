@@ -17,8 +17,13 @@
  *    "The picture's bytes at q" is exact: what jsmpeg_hip_encoder_picture_range reports for the picture coded at q with every
  *    earlier picture as chosen -- headers, per-slice padding, increments over skipped runs, vector differentials, DC codes and
  *    the STUFFING code included; the stream's end code and the gaps are not.  Sizes need not fall with q: every q of the range is
- *    measured, nothing is bisected.  Budgets carry neither from GOP to GOP nor from call to call; there is no VBV model and the
+ *    measured, nothing is bisected.  Budgets do not carry from GOP to GOP; there is no VBV model and the
  *    headers (bit_rate, vbv_delay) stay as they are.
+ *    ACROSS CALLS (JSMPEG_HIP_ENC_CHAIN; enc_chain.h): in a chained call m = gop for every picture -- a GOP is assumed to be
+ *    completed by later calls, the call's last GOP is not cut short -- and `spent` is the final bytes of the GOP's earlier levels
+ *    WHICHEVER CALL CODED THEM: a uint64 per stream on the device, written by the pick of the stream's last picture of a call
+ *    (its spent + its bytes) and added by the pick of a picture whose GOP began in an earlier call; a level-0 picture ignores
+ *    it.  An unchained call is as above: nothing carries from call to call.
  *
  * HOW.  The transform, the mode decision and the vectors do not depend on q, so per level, behind the motion search:
  *    jm_encr_measure   a macroblock: each block transformed ONCE, then quantised and counted at every q; per (macroblock, q) a

@@ -32,20 +32,32 @@
  * and the kernels behind them read that q as they read the caller's.  EXTRA DEVICE MEMORY, allocated by the first
  * jsmpeg_hip_encoder_set_rate that switches rate control on: per picture of max_pictures 62 bytes per macroblock (31 records of
  * 16 bits; 506 KB at 1080p), 124 bytes per macroblock row and 16 bytes -- and the stores of a GOP, if they are not there yet.
+ *
+ * ACROSS CALLS (JSMPEG_HIP_ENC_CHAIN; the rule: enc_chain.h) a stream's P chain and its GOP's budget go on where the call before
+ * left them.  No kernel of its own and no copy: every picture carries the addresses of its reference and of its reconstruction
+ * (JmEncPic::ref, ::recon, filled by the host, which needs nothing from the device for it), a chained stream's last picture
+ * of a call is reconstructed into one of the stream's two carry frames and the next call's first picture reads it there;
+ * k_enc_rate_pick adds the bytes the GOP's pictures took in earlier calls and leaves the sum for the next one.  EXTRA DEVICE
+ * MEMORY, allocated by the first chained call that runs the level loop: two frames and 16 bytes per stream of max_streams.
  */
 #include "engine_internal.h"
 #include "enc_block.h"
 #include "enc_motion.h"
 #include "enc_rate.h"
+#include "enc_chain.h"
 
 #define JM_ENC_LANES 64
 #define JM_ENC_MOTION_WAVES 4    /* macroblocks (one wavefront each) of a k_enc_motion workgroup */
 
 struct JmEncPic {
 	const uint8_t *frame;    /* Y | Cr | Cb of the coded size */
+	const uint8_t *ref;      /* a P picture's reference: the reconstruction of the picture before (enc_chain.h, WHERE); level loop only */
+	uint8_t *recon;          /* where the picture is reconstructed; level loop only */
 	uint32_t stream, ordinal, q;
 	uint32_t last;           /* the last picture of its stream in this call */
-	uint32_t m;              /* the pictures of its GOP in this call (rate control) */
+	uint32_t m;              /* the pictures its GOP is budgeted for (rate control) */
+	uint32_t before;         /* pictures of its GOP in front of it in this call (rate control) */
+	uint32_t carry;          /* JM_ENCC_READ | JM_ENCC_WRITE | JM_ENCC_ODD (rate control across calls) */
 };
 
 struct JmEncArgs {
@@ -182,8 +194,6 @@ __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_write(JmEncArgs a) {
 /* ------------------------------------------------------------------ kernels of a GOP (gop > 1) */
 
 struct JmEncPArgs {
-	uint8_t *recon;              /* [count] reconstructed frames, Y | Cr | Cb of the coded size */
-	uint64_t frame_bytes;
 	JmEncPMb *pmb;               /* [count][mbh][mbw] */
 	const JmEncPTables *ptables;
 	const uint32_t *list;        /* the call's picture numbers, sorted by level */
@@ -216,7 +226,7 @@ __global__ void __launch_bounds__(64 * JM_ENC_MOTION_WAVES) k_enc_motion(JmEncAr
 	if (!live) g = total - 1;                  /* a wavefront without a macroblock repeats the last one and stores nothing */
 	const uint32_t k = p.list[first + (uint32_t)(g / mbs)], m = (uint32_t)(g % mbs), row = m / a.mbw, col = m % a.mbw;
 	JM_GLOBAL const uint8_t *cur = (JM_GLOBAL const uint8_t *)a.pics[k].frame + ((size_t)row * 16u * a.cw + (size_t)col * 16u);
-	JM_GLOBAL const uint8_t *ref = (JM_GLOBAL const uint8_t *)p.recon + (size_t)(k - 1) * p.frame_bytes;   /* a P picture is never a call's first */
+	JM_GLOBAL const uint8_t *ref = (JM_GLOBAL const uint8_t *)a.pics[k].ref;
 	uint32_t *win = s_win[wave], *mb = s_cur[wave];
 	const uint32_t R = p.search;
 	/* the rows a search of radius R and its half-pel step read: 15 - R .. 32 + R */
@@ -268,12 +278,12 @@ __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_measure_p(JmEncArgs a, JmE
 	const EncPLane l = encp_lane(a, p, first, g);
 	const JmEncPic pic = a.pics[l.k];
 	JmEncPMb *rec = p.pmb + ((size_t)l.k * a.mbw * a.mbh + l.m);
-	JM_GLOBAL uint8_t *recon = (JM_GLOBAL uint8_t *)p.recon + (size_t)l.k * p.frame_bytes;
+	JM_GLOBAL uint8_t *recon = (JM_GLOBAL uint8_t *)pic.recon;
 	const uint32_t found = (pic.ordinal % p.gop) ? rec->info : 0u;
 	JmEncPMb out;
 	out.dc[0] = out.dc[1] = 0; out.inh = 0; out.pred = 0;
 	if (found & 1u) {
-		out.bits = jm_encp_measure_inter((JM_GLOBAL const uint8_t *)pic.frame, recon - p.frame_bytes, recon, a.cw, a.ch, a.mbw, l.col, l.row,
+		out.bits = jm_encp_measure_inter((JM_GLOBAL const uint8_t *)pic.frame, (JM_GLOBAL const uint8_t *)pic.ref, recon, a.cw, a.ch, a.mbw, l.col, l.row,
 		                                 jm_encp_mvh(found), jm_encp_mvv(found), pic.q, a.tables, p.ptables, zz + threadIdx.x, JM_ENC_LANES,
 		                                 pp + threadIdx.x, JM_ENC_LANES, &out.info);
 	} else {
@@ -291,6 +301,7 @@ struct JmEncRArgs {
 	uint16_t *rec;               /* [count][mbh][mbw][JM_ENCR_MAX_Q]: jm_encr_record */
 	uint32_t *slice;             /* [count][mbh][JM_ENCR_MAX_Q]: a slice's bytes at every scale */
 	uint32_t *out;               /* [count][4]: q, budget (saturated), bytes, 0 */
+	uint64_t *spent;             /* [2][max_streams]: the final bytes of a stream's unfinished GOP, from call to call (enc_chain.h, RATE); chained calls only */
 	uint64_t T;
 	uint32_t q_min, nq, W;
 };
@@ -305,7 +316,7 @@ __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_rate_measure(JmEncArgs a, 
 	const JmEncPic pic = a.pics[l.k];
 	const size_t at = (size_t)l.k * a.mbw * a.mbh + l.m;
 	JmEncPMb *rec = p.pmb + at;
-	JM_GLOBAL const uint8_t *ref = (JM_GLOBAL const uint8_t *)p.recon + (size_t)l.k * p.frame_bytes - p.frame_bytes;    /* only read in a P picture, never a call's first */
+	JM_GLOBAL const uint8_t *ref = (JM_GLOBAL const uint8_t *)pic.ref;    /* only read in a P picture */
 	const uint32_t found = (pic.ordinal % p.gop) ? rec->info : 0u;
 	uint64_t dcs;
 	if (jm_encr_measure((JM_GLOBAL const uint8_t *)pic.frame, ref, a.cw, a.ch, a.mbw, l.col, l.row, found, r.q_min, r.nq, a.tables, p.ptables,
@@ -331,17 +342,21 @@ __global__ void __launch_bounds__(64) k_enc_rate_pick(JmEncArgs a, JmEncPArgs p,
 	uint32_t bytes = level ? JM_ENC_P_HEAD_BYTES : JM_ENC_PIC_HEAD_BYTES;
 	if (lane < r.nq)
 		for (uint32_t row = 0; row < a.mbh; row++) bytes += r.slice[((size_t)k * a.mbh + row) * JM_ENCR_MAX_Q + lane];
-	/* the GOP's pictures at the levels before are the `level` pictures in front of this one: their final bytes */
+	/* the GOP's pictures at the levels before: the `before` pictures in front of this one (all `level` of them unless the GOP
+	 * began in an earlier call) -- their final bytes -- and what the earlier calls left */
 	uint64_t spent = 0;
-	for (uint32_t j = 1 + lane; j <= level; j += 64u) spent += r.out[(size_t)(k - j) * 4 + 2];
+	for (uint32_t j = 1 + lane; j <= pic.before; j += 64u) spent += r.out[(size_t)(k - j) * 4 + 2];
 #pragma unroll
 	for (int o = 32; o; o >>= 1) spent += __shfl_xor((unsigned long long)spent, o);
+	const uint32_t odd = (pic.carry & JM_ENCC_ODD) ? 1u : 0u;
+	if (pic.carry & JM_ENCC_READ) spent += r.spent[(size_t)odd * a.max_streams + pic.stream];
 	const uint64_t budget = jm_encr_budget(r.T, pic.m, level, r.W, spent);
 	const uint32_t fit = (uint32_t)enc_wave_min(lane < r.nq && bytes <= budget ? lane : r.nq - 1u);
 	const uint32_t taken = __shfl(bytes, (int)fit);
 	if (lane == 0) {
 		const_cast<JmEncPic *>(a.pics)[k].q = r.q_min + fit;
 		r.out[(size_t)k * 4] = r.q_min + fit; r.out[(size_t)k * 4 + 1] = jm_encr_saturate(budget); r.out[(size_t)k * 4 + 2] = taken; r.out[(size_t)k * 4 + 3] = 0;
+		if (pic.carry & JM_ENCC_WRITE) r.spent[(size_t)(odd ^ 1u) * a.max_streams + pic.stream] = spent + taken;
 	}
 }
 
@@ -386,7 +401,7 @@ __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_write_p(JmEncArgs a, JmEnc
 	}
 	const JmEncPMb rec = p.pmb[g];
 	JmEncBits bw = jm_enc_bits_at(a.words, slice_at * 8u + rec.bits);
-	JM_GLOBAL const uint8_t *ref = (JM_GLOBAL const uint8_t *)p.recon + (size_t)(p_picture ? k - 1 : k) * p.frame_bytes;
+	JM_GLOBAL const uint8_t *ref = (JM_GLOBAL const uint8_t *)pic.ref;
 	jm_encp_write(rec, (JM_GLOBAL const uint8_t *)pic.frame, ref, a.cw, a.ch, col, row, p_picture, p.r_size, pic.q, a.tables, p.ptables, zz + threadIdx.x, JM_ENC_LANES,
 	              pp + threadIdx.x, JM_ENC_LANES, bw);
 	jm_enc_flush(bw);
@@ -425,6 +440,12 @@ struct jsmpeg_hip_encoder_t {
 	uint32_t *d_rate_slice, *d_rate_out, *h_rate;  /* h_rate: pinned */
 	bool rate_ready;
 	bool pass_rate;                  /* the last call ran with rate control */
+	/* chains across calls (JSMPEG_HIP_ENC_CHAIN; the rule: enc_chain.h) */
+	std::vector<JmEncChain> chain;   /* [max_streams], host only */
+	std::vector<JmEncPlan> plan;     /* scratch of a call */
+	uint8_t *d_carry;                /* two frames per stream number, allocated by the first chained call that runs the level loop */
+	uint64_t *d_spent;               /* [2][max_streams], with d_carry */
+	bool pass_chain;                 /* the last call was chained: an overflow resets its streams */
 };
 
 static void enc_free_gop(jsmpeg_hip_encoder_t *e);
@@ -436,6 +457,7 @@ static void enc_free(jsmpeg_hip_encoder_t *e) {
 	hipFree(e->d_tables); hipFree(e->d_pics); hipFree(e->d_mb); hipFree(e->d_slice); hipFree(e->d_result); hipFree(e->d_es); hipFree(e->d_store);
 	enc_free_gop(e);
 	enc_free_rate(e);
+	hipFree(e->d_carry); hipFree(e->d_spent);
 	if (e->h_pics) hipHostFree(e->h_pics);
 	if (e->h_result) hipHostFree(e->h_result);
 	for (hipEvent_t &v : e->ev) if (v) hipEventDestroy(v);
@@ -488,6 +510,8 @@ extern "C" jsmpeg_hip_encoder_t *jsmpeg_hip_encoder_create(const jsmpeg_hip_enco
 	e->frame_bytes = (uint64_t)e->cw * e->ch * 3 / 2;
 	e->gop = 1; e->search = 0;
 	e->q_min = 1; e->q_max = JM_ENCR_MAX_Q; e->i_weight = 1;
+	e->chain.assign(config->max_streams, JmEncChain{ 0, 0, 0, 0 });
+	e->plan.resize(config->max_pictures);
 	if (enc_alloc(e) != 0) { enc_free(e); return nullptr; }
 	return e;
 }
@@ -502,6 +526,8 @@ static int enc_settle(jsmpeg_hip_encoder_t *e) {
 	HIP_TRY(hipEventSynchronize(e->ev_done));
 	if (e->h_result[1]) {
 		e->valid = false;
+		if (e->pass_chain)                                       /* what the call's streams were continued with is not there */
+			for (uint32_t k = 0; k < e->count; k++) jm_encc_reset(e->chain[e->h_pics[k].stream]);
 		return fail("encoder: the call's streams need %llu bytes, max_es_bytes is %llu: nothing of the call is valid",
 		            (unsigned long long)e->h_result[0], (unsigned long long)e->cfg.max_es_bytes);
 	}
@@ -544,6 +570,30 @@ extern "C" int jsmpeg_hip_encoder_set_gop(jsmpeg_hip_encoder_t *e, uint32_t gop,
 	if (search_range > JM_ENC_MAX_SEARCH) return fail("encoder: search_range %u, must be 0 .. %u", search_range, JM_ENC_MAX_SEARCH);
 	if (gop > 1 && !e->gop_ready && enc_alloc_gop(e) != 0) { enc_free_gop(e); return -1; }     /* gop and search_range stay as they were */
 	e->gop = gop; e->search = search_range;
+	for (JmEncChain &c : e->chain) jm_encc_reset(c);           /* levels and forward_f_code change */
+	return 0;
+}
+
+/* the carry frames and the GOPs' spent bytes; a failure leaves neither */
+static int enc_alloc_carry(jsmpeg_hip_encoder_t *e) {
+	const size_t ns = e->cfg.max_streams;
+	HIP_TRY(hipSetDevice(e->device));
+	if (jm_malloc(&e->d_carry, 2 * ns * (size_t)e->frame_bytes + 16) != hipSuccess || jm_malloc(&e->d_spent, sizeof(uint64_t) * 2 * ns) != hipSuccess ||
+	    hipMemset(e->d_spent, 0, sizeof(uint64_t) * 2 * ns) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {   /* the caller's stream may not wait for the null stream */
+		hipFree(e->d_carry); hipFree(e->d_spent);
+		e->d_carry = nullptr; e->d_spent = nullptr;
+		return fail("encoder: no memory for the carry frames of %u streams", e->cfg.max_streams);
+	}
+	return 0;
+}
+
+extern "C" int jsmpeg_hip_encoder_chain_reset(jsmpeg_hip_encoder_t *e, uint32_t stream) {
+	g_err[0] = 0;
+	if (!e) return fail("encoder: NULL handle");
+	if (e->pending) return fail("encoder: an encode is in flight: jsmpeg_hip_encoder_sync (or a reader) settles it first");
+	if (stream != UINT32_MAX && stream >= e->cfg.max_streams) return fail("encoder: stream %u >= max_streams %u", stream, e->cfg.max_streams);
+	for (uint32_t s = 0; s < e->cfg.max_streams; s++)
+		if (stream == UINT32_MAX || s == stream) jm_encc_reset(e->chain[s]);
 	return 0;
 }
 
@@ -583,7 +633,7 @@ extern "C" int jsmpeg_hip_encoder_set_rate(jsmpeg_hip_encoder_t *e, uint32_t byt
 /* the level loop (gop > 1, or rate control) between ev[1] and ev[3]; `a` is complete */
 static int enc_run_gop(jsmpeg_hip_encoder_t *e, const JmEncArgs &a, uint32_t count, hipStream_t st) {
 	JmEncPArgs p;
-	p.recon = e->d_recon; p.frame_bytes = e->frame_bytes; p.pmb = e->d_pmb; p.ptables = e->d_ptables; p.list = e->d_list;
+	p.pmb = e->d_pmb; p.ptables = e->d_ptables; p.list = e->d_list;
 	p.slice_kinds = e->d_slice_kinds; p.stats = e->d_stats;
 	p.gop = e->gop; p.search = e->search; p.r_size = jm_encp_r_size(e->search);
 	/* the pictures by level = ordinal mod gop: a counting sort of what the host already has */
@@ -599,7 +649,7 @@ static int enc_run_gop(jsmpeg_hip_encoder_t *e, const JmEncArgs &a, uint32_t cou
 	HIP_TRY(hipMemcpyAsync(e->d_list, e->h_list, sizeof(uint32_t) * count, hipMemcpyHostToDevice, st));
 	const uint64_t mbs = (uint64_t)e->mbw * e->mbh;
 	JmEncRArgs r;
-	r.rec = e->d_rate_rec; r.slice = e->d_rate_slice; r.out = e->d_rate_out;
+	r.rec = e->d_rate_rec; r.slice = e->d_rate_slice; r.out = e->d_rate_out; r.spent = e->d_spent;
 	r.T = e->rate_bytes; r.q_min = e->q_min; r.nq = e->q_max - e->q_min + 1u; r.W = e->i_weight;
 	for (uint32_t l = 0; l < levels; l++) {
 		const uint32_t first = begin[l], n = begin[l + 1] - begin[l];
@@ -630,7 +680,7 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 	if (!e) return fail("encoder: NULL handle");
 	if (e->pending) return fail("encoder: an encode is in flight: jsmpeg_hip_encoder_sync (or a reader) settles it first");
 	if (count > e->cfg.max_pictures) return fail("encoder: %u pictures > max_pictures %u", count, e->cfg.max_pictures);
-	if (flags & ~JSMPEG_HIP_ENC_END) return fail("encoder: unknown flags 0x%x", flags);
+	if (flags & ~(JSMPEG_HIP_ENC_END | JSMPEG_HIP_ENC_CHAIN)) return fail("encoder: unknown flags 0x%x", flags);
 	if (count && !frames && !dev_rgb) return fail("encoder: NULL frames");
 	if (dev_rgb && (layout > JSMPEG_HIP_TENSOR_NHWC || order > JSMPEG_HIP_TENSOR_BGR)) return fail("encoder: layout %u / order %u unknown", layout, order);
 	if (!qscale && (quantiser_scale < 1 || quantiser_scale > 31)) return fail("encoder: quantiser_scale %u, must be 1 .. 31", quantiser_scale);
@@ -643,26 +693,41 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 	}
 	HIP_TRY(hipSetDevice(e->device));
 	hipStream_t st = (hipStream_t)hip_stream;
+	const bool chained = (flags & JSMPEG_HIP_ENC_CHAIN) != 0, end = (flags & JSMPEG_HIP_ENC_END) != 0;
+	const bool rate = e->rate_bytes != 0, level_loop = e->gop > 1 || rate;
+	if (chained && count && level_loop) {
+		if (!e->gop_ready && enc_alloc_gop(e) != 0) { enc_free_gop(e); return -1; }
+		if (!e->d_carry && enc_alloc_carry(e) != 0) return -1;
+	}
 	e->count = count;
 	e->have_pass = true;
+	e->pass_chain = chained;
 	if (count == 0) { e->valid = true; e->h_result[0] = 0; e->h_result[1] = 0; return 0; }
 	if (dev_rgb && !e->d_store) HIP_TRY(jm_malloc(&e->d_store, (size_t)e->frame_bytes * e->cfg.max_pictures));
-	for (uint32_t k = 0, ordinal = 0; k < count; k++) {
-		const uint32_t s = stream ? stream[k] : 0;
-		ordinal = (k && s == e->h_pics[k - 1].stream) ? ordinal + 1 : 0;
+	for (uint32_t k0 = 0; k0 < count;) {                       /* stream by stream: ordinals, GOP sizes, where the reconstructions lie (enc_chain.h) */
+		const uint32_t s = stream ? stream[k0] : 0;
+		uint32_t n = 1;
+		while (k0 + n < count && (!stream || stream[k0 + n] == s)) n++;
+		jm_encc_plan(chained ? &e->chain[s] : nullptr, s, rate, e->gop, k0, n, &e->plan[k0]);
+		if (chained) jm_encc_advance(e->chain[s], e->plan[k0 + n - 1], rate, end, e->gop);
+		k0 += n;
+	}
+	for (uint32_t k = 0; k < count; k++) {
+		const JmEncPlan &pl = e->plan[k];
 		JmEncPic &p = e->h_pics[k];
 		p.frame = frames ? (const uint8_t *)frames[k] : e->d_store + (size_t)k * e->frame_bytes;
-		p.stream = s; p.ordinal = ordinal; p.q = qscale ? qscale[k] : quantiser_scale;
-		p.last = (k + 1 == count || (stream && stream[k + 1] != s)) ? 1u : 0u;
-	}
-	for (uint32_t k = count, len = 0; k-- > 0;) {              /* m: the GOP's pictures, the stream's last GOP in the call cut short */
-		JmEncPic &p = e->h_pics[k];
-		if (p.last) len = p.ordinal + 1;
-		p.m = std::min(e->gop, len - (p.ordinal - p.ordinal % e->gop));
+		p.stream = stream ? stream[k] : 0; p.ordinal = pl.ordinal; p.q = qscale ? qscale[k] : quantiser_scale;
+		p.last = pl.last; p.m = pl.m; p.before = pl.before; p.carry = pl.carry;
+		uint8_t *where[2];
+		const uint32_t frame_of[2] = { pl.ref, pl.recon };
+		for (int i = 0; i < 2; i++)
+			where[i] = !level_loop ? nullptr : (frame_of[i] & JM_ENCC_SLOT) ? e->d_carry + (size_t)(frame_of[i] & ~JM_ENCC_SLOT) * e->frame_bytes
+			                                                                : e->d_recon + (size_t)frame_of[i] * e->frame_bytes;
+		p.ref = where[0]; p.recon = where[1];
 	}
 	JmEncArgs a;
 	a.width = (uint32_t)e->cfg.width; a.height = (uint32_t)e->cfg.height; a.cw = e->cw; a.ch = e->ch; a.mbw = e->mbw; a.mbh = e->mbh;
-	a.count = count; a.frame_rate_code = e->cfg.frame_rate_code; a.end = (flags & JSMPEG_HIP_ENC_END) ? 1u : 0u;
+	a.count = count; a.frame_rate_code = e->cfg.frame_rate_code; a.end = end ? 1u : 0u;
 	a.cap = e->cfg.max_es_bytes;
 	a.pics = e->d_pics; a.tables = e->d_tables; a.mb = e->d_mb; a.slice = e->d_slice; a.result = e->d_result;
 	a.max_streams = e->cfg.max_streams; a.max_pictures = e->cfg.max_pictures;
@@ -678,8 +743,8 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 		k_enc_rgb<<<dim3((uint32_t)((quads + 255) / 256)), dim3(256), 0, st>>>(a, (const uint8_t *)dev_rgb, layout, order);
 	}
 	HIP_TRY(hipEventRecord(e->ev[1], st));
-	e->pass_rate = e->rate_bytes != 0;
-	e->pass_gop = e->gop > 1 || e->pass_rate;
+	e->pass_rate = rate;
+	e->pass_gop = level_loop;
 	if (e->pass_gop) {
 		if (enc_run_gop(e, a, count, st) != 0) return -1;
 	} else {
@@ -766,7 +831,17 @@ extern "C" const void *jsmpeg_hip_encoder_recon(jsmpeg_hip_encoder_t *e, uint32_
 	if (enc_ready(e) < 0) return nullptr;
 	if (!e->pass_gop) { fail("encoder: the last call ran with gop 1: it keeps no reconstruction (jsmpeg_hip_encoder_set_gop)"); return nullptr; }
 	if (k >= e->count) { fail("encoder: picture %u of %u", k, e->count); return nullptr; }
-	return e->d_recon + (size_t)k * e->frame_bytes;
+	return e->h_pics[k].recon;                                 /* the call's store, or a chained stream's carry frame */
+}
+
+extern "C" int jsmpeg_hip_encoder_chain_info(jsmpeg_hip_encoder_t *e, uint32_t stream, uint32_t out[2]) {
+	g_err[0] = 0;
+	if (!e) return fail("encoder: NULL handle");
+	if (!out) return fail("encoder: NULL out");
+	if (stream >= e->cfg.max_streams) return fail("encoder: stream %u >= max_streams %u", stream, e->cfg.max_streams);
+	if (e->pending) { enc_settle(e); g_err[0] = 0; }           /* an overflow resets the call's streams; sync and the readers report it */
+	out[0] = e->chain[stream].have; out[1] = e->chain[stream].n;
+	return 0;
 }
 
 extern "C" int jsmpeg_hip_encoder_picture_stats(jsmpeg_hip_encoder_t *e, uint32_t k, uint32_t out[4]) {

@@ -11,12 +11,13 @@ import numpy as np
 from . import batch as _batch
 
 END = 1
+CHAIN = 2        # continue the call's streams where their last chained call left them (JSMPEG_HIP_ENC_CHAIN)
 
 SYMBOLS = ("jsmpeg_hip_encoder_create", "jsmpeg_hip_encoder_destroy", "jsmpeg_hip_encoder_encode", "jsmpeg_hip_encoder_encode_rgb",
            "jsmpeg_hip_encoder_sync", "jsmpeg_hip_encoder_query", "jsmpeg_hip_encoder_es", "jsmpeg_hip_encoder_stream_range",
            "jsmpeg_hip_encoder_picture_range", "jsmpeg_hip_encoder_read_es", "jsmpeg_hip_encoder_timings", "jsmpeg_hip_ts_mux_host",
            "jsmpeg_hip_encoder_set_gop", "jsmpeg_hip_encoder_recon", "jsmpeg_hip_encoder_picture_stats",
-           "jsmpeg_hip_encoder_set_rate", "jsmpeg_hip_encoder_picture_rate")
+           "jsmpeg_hip_encoder_set_rate", "jsmpeg_hip_encoder_picture_rate", "jsmpeg_hip_encoder_chain_reset", "jsmpeg_hip_encoder_chain_info")
 
 FRAME_RATES = {1: (24000, 1001), 2: (24, 1), 3: (25, 1), 4: (30000, 1001), 5: (30, 1), 6: (50, 1), 7: (60000, 1001), 8: (60, 1)}
 
@@ -75,6 +76,10 @@ def lib():
         L.jsmpeg_hip_encoder_set_rate.argtypes = [vp, u32, u32, u32, u32]
         L.jsmpeg_hip_encoder_picture_rate.restype = ctypes.c_int
         L.jsmpeg_hip_encoder_picture_rate.argtypes = [vp, u32, ctypes.POINTER(u32)]
+        L.jsmpeg_hip_encoder_chain_reset.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_chain_reset.argtypes = [vp, u32]
+        L.jsmpeg_hip_encoder_chain_info.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_chain_info.argtypes = [vp, u32, ctypes.POINTER(u32)]
         L.jsmpeg_hip_ts_mux_host.restype = ctypes.c_int64
         L.jsmpeg_hip_ts_mux_host.argtypes = [vp, vp, vp, vp, u32, u32, u32, ctypes.POINTER(ctypes.c_uint8), vp, u64]
         _bound = L
@@ -107,7 +112,10 @@ def ts_mux(es, ranges, pts, stream_id=0xE0, pid=0x100, continuity=0):
 
 class Encoder:
     """Pictures on the device -> MPEG-1 elementary streams on the device: all I pictures, or I + P after set_gop.  A call is a
-    pure enqueue; sync() or any reader settles it."""
+    pure enqueue; sync() or any reader settles it.  chain=True on a call continues its streams -- the stream NUMBER is a
+    stream's identity from call to call -- where their last chained call left them: ordinals, P chain and GOP budget go on,
+    and the pieces concatenated are the stream one call over all the pictures writes.  A piece that begins with a P picture
+    begins at its picture start code: for concatenation or a Live that holds the sequence header already."""
 
     def __init__(self, width, height, max_pictures, max_streams, max_es_bytes, frame_rate_code=0, device=-1):
         self.L = lib()
@@ -151,19 +159,24 @@ class Encoder:
             raise ValueError("qscale: an integer or one per picture")
         return s, np.ascontiguousarray(q, dtype=np.uint8), 0
 
-    def encode(self, frame_ptrs, streams=None, qscale=8, end=True, stream=None):
+    @staticmethod
+    def _flags(end, chain):
+        return (END if end else 0) | (CHAIN if chain else 0)
+
+    def encode(self, frame_ptrs, streams=None, qscale=8, end=True, stream=None, chain=False):
         """frame_ptrs: device addresses of Y | Cr | Cb planes of the coded size, one per picture; streams: ascending stream
         numbers (None: all stream 0); qscale: 1 .. 31, or one per picture; end: close every stream with a sequence end
-        code; stream: the HIP stream to enqueue on -- the one the frames were produced on (ordering is the caller's)."""
+        code; stream: the HIP stream to enqueue on -- the one the frames were produced on (ordering is the caller's); chain:
+        continue the streams (end=True then closes them AND ends their chains)."""
         ptrs = [int(p) if p else 0 for p in frame_ptrs]
         n = len(ptrs)
         arr = (ctypes.c_void_p * max(1, n))(*ptrs)
         s, q, qs = self._lists(n, streams, qscale)
         self._ok(self.L.jsmpeg_hip_encoder_encode(self.h, arr, None if s is None else s.ctypes.data, None if q is None else q.ctypes.data,
-                                                  n, qs, END if end else 0, stream))
+                                                  n, qs, self._flags(end, chain), stream))
         self.count = n
 
-    def encode_batch(self, batch, pictures, streams=None, qscale=8, end=True, stream=None):
+    def encode_batch(self, batch, pictures, streams=None, qscale=8, end=True, stream=None, chain=False):
         """pictures of a Batch's last decode, straight from its frame pool (the batch is synchronised first; a picture that was
         not decoded is refused).  streams None: each picture's own stream number, which must then ascend."""
         batch.sync()
@@ -174,23 +187,31 @@ class Encoder:
         if streams is None:
             streams = [info.stream for info in infos]
         base = batch.frame_pool_ptr
-        self.encode([base + int(p) * batch.frame_stride for p in pictures], streams, qscale, end, stream)
+        self.encode([base + int(p) * batch.frame_stride for p in pictures], streams, qscale, end, stream, chain)
 
-    def encode_live(self, live, pictures=None, streams=None, qscale=8, end=True, stream=None):
+    def encode_live(self, live, pictures=None, streams=None, qscale=8, end=True, stream=None, chain=False):
         """pictures of a Live's last tick (None: all of them, in tick order), from their device_frame pointers.  streams
-        None: the pictures are sorted by their live stream id (stable) and numbered 0, 1, .. in that order"""
+        None: the pictures are sorted by their live stream id (stable) and numbered 0, 1, .. in that order -- or, with
+        chain=True, each picture's live stream id IS its stream number (an id at or above max_streams is refused), so that a
+        stream keeps its identity when others join or leave.  Returns the pictures in the order they were encoded in."""
         pics = live.pictures()
         if pictures is not None:
             pics = [pics[int(i)] for i in pictures]
         if streams is None:
             order = sorted(range(len(pics)), key=lambda i: pics[i].stream)
             pics = [pics[i] for i in order]
-            ids = sorted({p.stream for p in pics})
-            streams = [ids.index(p.stream) for p in pics]
-        self.encode([p.device_frame for p in pics], streams, qscale, end, stream)
+            if chain:
+                for p in pics:
+                    if p.stream >= self.max_streams:
+                        raise ValueError("encode_live: live stream id %d >= max_streams %d" % (p.stream, self.max_streams))
+                streams = [p.stream for p in pics]
+            else:
+                ids = sorted({p.stream for p in pics})
+                streams = [ids.index(p.stream) for p in pics]
+        self.encode([p.device_frame for p in pics], streams, qscale, end, stream, chain)
         return pics
 
-    def encode_tensor(self, x, streams=None, qscale=8, end=True, order="rgb"):
+    def encode_tensor(self, x, streams=None, qscale=8, end=True, order="rgb", chain=False):
         """x: a contiguous torch uint8 CUDA tensor [N, 3, H, W] or [N, H, W, 3] of the display size; runs on torch's current
         stream of the tensor's device"""
         import torch
@@ -209,7 +230,7 @@ class Encoder:
         st = torch.cuda.current_stream(x.device).cuda_stream
         self._ok(self.L.jsmpeg_hip_encoder_encode_rgb(self.h, x.data_ptr() if n else None, layout, 1 if str(order).lower() == "bgr" else 0,
                                                       None if s is None else s.ctypes.data, None if q is None else q.ctypes.data,
-                                                      n, qs, END if end else 0, st))
+                                                      n, qs, self._flags(end, chain), st))
         self.count = n
         self._keep = x          # the tensor stays alive until the next call
 
@@ -217,8 +238,19 @@ class Encoder:
         """gop 1: I pictures only (the default).  gop N > 1: every N-th picture of a stream is an I picture, the others are P
         pictures predicted from the encoder's own reconstruction; search: full-pel radius 0 .. 15 of the motion search (0:
         zero vectors only).  State of the handle: every later encode* call uses it.  Every stream of a call begins with an
-        I picture."""
+        I picture unless the call is chained (chain=True).  Ends every stream's chain."""
         self._ok(self.L.jsmpeg_hip_encoder_set_gop(self.h, gop, search))
+
+    def chain_reset(self, stream=None):
+        """ends the chain of `stream` (None: of every stream): its next chained picture is an I picture with its sequence header
+        -- for a viewer that joins, or a stream number that is handed to another source.  Refused while a pass is in flight."""
+        self._ok(self.L.jsmpeg_hip_encoder_chain_reset(self.h, 0xffffffff if stream is None else stream))
+
+    def chain_info(self, stream):
+        """(whether `stream` has chain state, the pictures it has coded = the ordinal of its next chained picture)"""
+        out = (ctypes.c_uint32 * 2)()
+        self._ok(self.L.jsmpeg_hip_encoder_chain_info(self.h, stream, out))
+        return bool(out[0]), int(out[1])
 
     def recon_ptr(self, k):
         """device address of picture k's reconstruction (Y | Cr | Cb of the coded size) in the last call; gop > 1 only"""

@@ -8,13 +8,19 @@ pass on the same pictures): ms per pass, the output bytes, and what Batch.decode
 to the bench_gop<N>_r<R> section of profiles/enc_p_notes.md.  A fifth step, `rate`: the same 768 pictures with --gop and --search
 at a fixed scale, with rate control over 1 .. 31 and over 4 .. 16 (--rate bytes per picture): ms per pass each way, and the
 registers, LDS and occupancy of the three rate kernels; its figures go to the bench section of profiles/enc_rate_notes.md.
+A sixth step, `chain`: what a live relay runs -- 64 streams of 1080p, ONE picture per stream per call, 24 calls, with --gop and
+--search, at a fixed scale and with rate control (--rate): bytes per picture and ms per call.  With chained calls
+(Encoder.encode(chain=True)) the calls continue their streams; on a tree whose encoder has no chains the same calls are all I
+pictures -- that is the figure to hold against.  Its figures go to the bench (or, without chains, bench_unchained) section of
+profiles/enc_chain_notes.md.
 
 Every GPU step is a child process of this tool under its own `timeout`; the steps are chained and the tool stops at the first
 one that fails.  The figures go into the bench section of profiles/enc_notes.md (nothing is written for a step that did not
 run).
     python tools/encode_bench.py [--steps pool64,pool7680,tensor] [--reps 8]
     python tools/encode_bench.py --steps gop --gop 12 --search 7
-    python tools/encode_bench.py --steps rate --gop 12 --search 7 --rate 40000"""
+    python tools/encode_bench.py --steps rate --gop 12 --search 7 --rate 40000
+    python tools/encode_bench.py --steps chain --gop 12 --search 7 --rate 40000 --reps 3"""
 import argparse
 import json
 import os
@@ -29,7 +35,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 W, H = 1920, 1080
-STEPS = {"pool64": 300, "pool7680": 420, "tensor": 120, "gop": 300, "rate": 420}          # seconds each step may take
+STEPS = {"pool64": 300, "pool7680": 420, "tensor": 120, "gop": 300, "rate": 420, "chain": 420}          # seconds each step may take
 
 
 def median(v):
@@ -214,6 +220,62 @@ def step_rate(gop, search, target, reps):
         return dict(step="rate", gop=gop, search=search, target=target, pictures=len(pics), streams=64, ways=ways, kernels=kernels)
 
 
+CHAIN_CALLS = 24
+
+
+def step_chain(gop, search, target, reps):
+    """64 streams x 24 pictures of 1080p from a batch's pool, a picture per stream per call (24 calls a round, one round to warm
+    up and `reps` measured), q = 8 and rate control over 1 .. 31; chained where the encoder has chains"""
+    import bench
+    from jsmpeg_amd import batch as jb
+    from jsmpeg_amd import encode
+    chained = hasattr(encode, "CHAIN")
+    streams = [g[0] for g in bench.generate_streams(0, 64, CHAIN_CALLS)]
+    total = sum(len(s) for s in streams)
+    n = 64 * CHAIN_CALLS
+    with jb.Batch(W, H, 64, n + 8, total + 64 * 64 + 4096, device=0) as b:
+        b.upload(streams)
+        assert b.decode() == n
+        infos = b.pictures()
+        by_stream = {}
+        for p, i in enumerate(infos):
+            if i.decoded:
+                by_stream.setdefault(i.stream, []).append(p)
+        assert sorted(by_stream) == list(range(64)) and all(len(v) == CHAIN_CALLS for v in by_stream.values())
+        calls = [[b.frame_pool_ptr + by_stream[s][t] * b.frame_stride for s in range(64)] for t in range(CHAIN_CALLS)]
+        sn = list(range(64))
+        ways = []
+        with encode.Encoder(W, H, 64, 64, 128 << 20, device=0) as enc:
+            enc.set_gop(gop, search)
+            for name, rule in (("fixed scale 8", None), ("rate control, 1 .. 31", (target, 1, 31, 4))):
+                enc.set_rate(*(rule or (0,)))
+                wall, dev, size, first = [], [], [], []
+                for r in range(reps + 1):
+                    if chained:
+                        enc.chain_reset()
+                    for t, ptrs in enumerate(calls):
+                        t0 = time.perf_counter()
+                        if chained:
+                            enc.encode(ptrs, sn, 8, end=False, chain=True)
+                        else:
+                            enc.encode(ptrs, sn, 8, end=False)
+                        enc.sync()
+                        if r >= 1:
+                            wall.append((time.perf_counter() - t0) * 1e3)
+                            dev.append(enc.timings()["total_ms"])
+                            first.append(t % gop == 0)
+                            if r == 1:
+                                size.append(sum(v for _, v in enc.picture_ranges()))
+                i_calls = [k for k in range(CHAIN_CALLS) if k % gop == 0] if chained else list(range(CHAIN_CALLS))
+                p_calls = [k for k in range(CHAIN_CALLS) if k not in i_calls]
+                pick = lambda v, flag: [x for x, f in zip(v, first) if f == flag or not chained]
+                ways.append(dict(name=name, calls=len(wall), wall_ms=median(wall), total_ms=median(dev), total_ms_min=round(min(dev), 3), total_ms_max=round(max(dev), 3),
+                                 i_call_ms=median(pick(dev, True)), p_call_ms=median(pick(dev, False)) if p_calls else None,
+                                 bytes_per_picture=round(sum(size) / n), i_bytes_per_picture=round(sum(size[k] for k in i_calls) / (64 * len(i_calls))),
+                                 p_bytes_per_picture=round(sum(size[k] for k in p_calls) / (64 * len(p_calls))) if p_calls else None))
+        return dict(step="chain", chained=chained, gop=gop, search=search, target=target, streams=64, calls=CHAIN_CALLS, reps=reps, ways=ways)
+
+
 def step_tensor():
     import torch
     import enc_inputs as ei
@@ -238,7 +300,17 @@ def step_tensor():
 def notes(results):
     lines = ["## Cost on the MI355X (measured by tools/encode_bench.py)", ""]
     for r in results:
-        if r["step"] == "rate":
+        if r["step"] == "chain":
+            lines = ["## %s: %d streams of 1080p, one picture per stream per call, %d calls, gop %d, search range %d, target %d bytes per picture (measured on an MI355X by tools/encode_bench.py)"
+                     % ("Chained calls" if r["chained"] else "The same calls WITHOUT chains (every picture an I picture)", r["streams"], r["calls"], r["gop"], r["search"], r["target"]), "",
+                     "| | bytes per picture | of I pictures | of P pictures | call + sync, host clock, ms | device, median (min .. max), ms per call | calls with I pictures, ms | calls with P pictures, ms |",
+                     "|---|---|---|---|---|---|---|---|"]
+            for w in r["ways"]:
+                lines.append("| %s | %d | %d | %s | %.3f | %.3f (%.3f .. %.3f) | %.3f | %s |" % (
+                    w["name"], w["bytes_per_picture"], w["i_bytes_per_picture"], w["p_bytes_per_picture"] if w["p_bytes_per_picture"] is not None else "-", w["wall_ms"],
+                    w["total_ms"], w["total_ms_min"], w["total_ms_max"], w["i_call_ms"], "%.3f" % w["p_call_ms"] if w["p_call_ms"] is not None else "-"))
+            lines += ["", "Medians over %d measured calls each (%d rounds of %d behind one round to warm up)." % (r["ways"][0]["calls"], r["reps"], r["calls"]), ""]
+        elif r["step"] == "rate":
             lines = ["## Cost on the MI355X: gop %d, search range %d, %d pictures of 1080p in %d streams, target %d bytes per picture (measured by tools/encode_bench.py)"
                      % (r["gop"], r["search"], r["pictures"], r["streams"], r["target"]), "",
                      "| | call + sync, host clock, ms | measure + scan (the level loop), ms | write, ms | total, median (min .. max), ms | output bytes | pictures' bytes of %d | over budget | mean q |" % (r["pictures"] * r["target"]),
@@ -290,7 +362,7 @@ def main():
     ap.add_argument("--child")
     a = ap.parse_args()
     if a.child:
-        r = step_rate(a.gop, a.search, a.rate, a.reps) if a.child == "rate" else step_gop(a.gop, a.search, a.reps) if a.child == "gop" else step_tensor() if a.child == "tensor" else step_pool(a.child == "pool7680", a.reps)
+        r = step_chain(a.gop, a.search, a.rate, a.reps) if a.child == "chain" else step_rate(a.gop, a.search, a.rate, a.reps) if a.child == "rate" else step_gop(a.gop, a.search, a.reps) if a.child == "gop" else step_tensor() if a.child == "tensor" else step_pool(a.child == "pool7680", a.reps)
         print("RESULT " + json.dumps(r), flush=True)
         return 0
     results = []
@@ -310,7 +382,9 @@ def main():
         replace_section(os.path.join(ROOT, "profiles", "enc_p_notes.md"), "bench_gop%d_r%d" % (r["gop"], r["search"]), notes([r]))
     for r in [r for r in results if r["step"] == "rate"]:
         replace_section(os.path.join(ROOT, "profiles", "enc_rate_notes.md"), "bench", notes([r]))
-    results = [r for r in results if r["step"] not in ("gop", "rate")]
+    for r in [r for r in results if r["step"] == "chain"]:
+        replace_section(os.path.join(ROOT, "profiles", "enc_chain_notes.md"), "bench" if r["chained"] else "bench_unchained", notes([r]))
+    results = [r for r in results if r["step"] not in ("gop", "rate", "chain")]
     if results:
         replace_section(NOTES, "bench", notes(results))
     return 0 if done == len(a.steps.split(",")) else 1
