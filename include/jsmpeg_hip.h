@@ -794,7 +794,7 @@ int jsmpeg_hip_live_render_tensor_latest(jsmpeg_hip_live_t *l, const uint32_t *s
  * that encodes one picture per stream and tick gets its GOPs and its rate control that way.  Batch STREAMS, not pictures: a P picture waits for the picture before it,
  * so a call with one stream runs one picture at a time on the device.
  * OUT OF SCOPE: B pictures, quantiser changes inside a picture, a VBV model, custom matrices, vectors
- * beyond +-15 pels, a Node binding, resizing of YCbCr (resize the RGB tensor).
+ * beyond +-15 pels, a Node binding.
  * A pass is a PURE ENQUEUE on hip_stream, like jsmpeg_hip_batch_enqueue: every size and offset is worked out on the device; the
  * host waits in jsmpeg_hip_encoder_sync and the readers only (they settle the pass first).  One pass at a time per handle: a
  * second encode before the first is settled is refused.  ORDERING AGAINST THE PRODUCER OF THE FRAMES IS THE CALLER'S: pass the
@@ -851,6 +851,28 @@ int jsmpeg_hip_encoder_encode(jsmpeg_hip_encoder_t *enc, const void *const *fram
  * into a frame store of the handle's own (max_pictures frames, allocated by the first call) */
 int jsmpeg_hip_encoder_encode_rgb(jsmpeg_hip_encoder_t *enc, const void *dev_rgb, uint32_t layout, uint32_t order, const uint32_t *stream,
                                   const uint8_t *qscale, uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream);
+/* A RENDITION: the same from frames of ANOTHER size, cropped and scaled on the device into the handle's frame store (the one
+ * jsmpeg_hip_encoder_encode_rgb fills; the first call of either allocates it) -- planes to planes, no RGB in between.  frames[k]:
+ * Y | Cr | Cb of the SOURCE's coded size (a pool slot of a batch or live of `source->width` x `source->height`), one geometry for
+ * all the pictures of the call.  The three planes are scaled independently with torch's bilinear / antialiased-bilinear filter
+ * shapes (align_corners = False) stated as integer ratios with 14-bit weights, horizontal pass, then vertical, and the coded
+ * size is filled by edge replication: the rule, bit for bit, is jsmpeg_amd/csrc/enc_scale.h.  A source of the encoder's size
+ * without a crop is a copy.  The pass behind it -- GOP, rate control, JSMPEG_HIP_ENC_CHAIN, flags, readers, overflow -- is the
+ * one of the other two entry points; jsmpeg_hip_encoder_timings' "convert" covers the scale.  Still a pure enqueue: the tap
+ * table is built on the host in pinned memory and goes up on hip_stream.  A NULL descriptor, a size of 0 or above 4095, a crop
+ * outside the picture, an odd crop_x or crop_y, antialias > 1: < 0 with jsmpeg_hip_last_error, nothing is launched. */
+typedef struct jsmpeg_hip_enc_source_t {
+	uint32_t width, height;                               /* display size of the SOURCE frames, 1..4095; planes of its coded size */
+	uint32_t crop_x, crop_y, crop_width, crop_height;     /* display pixels, x / y even; all 0: the whole picture */
+	uint32_t antialias;                                   /* 0 / 1 */
+} jsmpeg_hip_enc_source_t;
+int jsmpeg_hip_encoder_encode_scaled(jsmpeg_hip_encoder_t *enc, const void *const *frames, const jsmpeg_hip_enc_source_t *source,
+                                     const uint32_t *stream, const uint8_t *qscale, uint32_t count, uint32_t quantiser_scale,
+                                     uint32_t flags, void *hip_stream);
+/* device pointer of the planes picture k of the last call was coded FROM (Y | Cr | Cb, the encoder's coded size): the caller's
+ * frames[k] after jsmpeg_hip_encoder_encode, the handle's store after _encode_rgb (converted) and _encode_scaled (scaled).
+ * Settles the pass first, like the other readers. */
+const void *jsmpeg_hip_encoder_source(jsmpeg_hip_encoder_t *enc, uint32_t k);
 int jsmpeg_hip_encoder_sync(jsmpeg_hip_encoder_t *enc);             /* settles; < 0 with a message on overflow: nothing of the call is valid */
 int jsmpeg_hip_encoder_query(jsmpeg_hip_encoder_t *enc);            /* 1 finished, 0 not; never blocks */
 void *jsmpeg_hip_encoder_es(jsmpeg_hip_encoder_t *enc, uint64_t *total_bytes);   /* device buffer of the last call; NULL after an overflow */

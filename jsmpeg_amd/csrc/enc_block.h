@@ -5,8 +5,8 @@
  *
  * I pictures here, one quantiser scale per picture, the default intra matrix, one slice per macroblock row; P pictures and the
  * closed loop they need (the encoder's reference must be the decoder's reconstruction) are enc_motion.h's, built on what is
- * below.  OUT OF SCOPE (say so to whoever asks): B pictures, a VBV model (rate control by a budget per GOP: enc_rate.h), custom matrices, a Node binding, resizing of YCbCr
- * (resize the RGB tensor with torch).
+ * below.  OUT OF SCOPE (say so to whoever asks): B pictures, a VBV model (rate control by a budget per GOP: enc_rate.h), custom matrices, a Node binding.
+ * (Scaled and cropped YCbCr input: enc_scale.h.)
  *
  * FORWARD DCT, exactly:  with C[k][n] = round(2^14 * c_k * cos((2n + 1) k pi / 16)), c_0 = sqrt(1/8), c_k = 1/2
  * (jm_enc_make_const below, 16-bit signed), and the block's pixels x[y][n] in 0 .. 255 (MPEG-1 intra blocks are not level-shifted),

@@ -6,6 +6,7 @@
  *
  * A pass on the caller's stream, every size and offset worked out on the device:
  *   k_enc_rgb            tensor input only: RGB -> Y | Cr | Cb of the coded size in the encoder's frame store
+ *   k_enc_scale          scaled input only: planes of another size, cropped and scaled into the same store (the rule: enc_scale.h)
  *   k_enc_measure        a macroblock per lane: transform, quantise, count bits; 12 bytes per macroblock out
  *   k_enc_scan_slices    a slice per lane: the macroblocks' bit offsets (their DC codes depend on the predecessor), the slice's bytes
  *   k_enc_scan_pictures  a picture per lane: the slices' offsets, the picture's bytes
@@ -45,6 +46,7 @@
 #include "enc_motion.h"
 #include "enc_rate.h"
 #include "enc_chain.h"
+#include "enc_scale.h"
 
 #define JM_ENC_LANES 64
 #define JM_ENC_MOTION_WAVES 4    /* macroblocks (one wavefront each) of a k_enc_motion workgroup */
@@ -88,6 +90,113 @@ __global__ void __launch_bounds__(256) k_enc_rgb(JmEncArgs a, const uint8_t *rgb
 	const uint32_t k = (uint32_t)(g / ((uint64_t)qw * qh)), r = (uint32_t)(g % ((uint64_t)qw * qh));
 	jm_enc_rgb_quad(rgb + (size_t)k * a.width * a.height * 3, layout, order, a.width, a.height, r % qw, r / qw,
 	                const_cast<uint8_t *>(a.pics[k].frame), a.cw, a.ch);
+}
+
+/* Scaled input (the rule, the table and the tile plan: enc_scale.h; the CPU simulator tests/sim/sim_encode_scale.cpp runs the
+ * same taps pixel by pixel).  A workgroup owns a tile of JM_ES_TW x JM_ES_TH samples of one plane of the CODED size of one
+ * picture -- a sample beyond the scaled picture takes the taps of the last column / row, which is the edge replication -- and
+ * walks the source rows its vertical taps need in chunks of at most JM_ES_CR rows, as k_tensor does:
+ *   1. stage: the chunk's rows of the tile's source span into LDS, 16-byte loads from the coded luma row, 8-byte loads from
+ *      the chroma row (its stride is a multiple of 8 only);
+ *   2. horizontal pass: thread = output column (two row groups), each weight read once for the thread's 16 rows of the chunk,
+ *      into LDS as 16-bit t;
+ *   3. vertical pass: a thread owns four adjacent columns of four rows of the tile; the chunk's rows inside their taps are added
+ *      in registers, across chunks.
+ * Then a whole word per thread and row is stored.  The weights come from the host's table (built by enc_scale.h's functions
+ * in pinned memory, uploaded on the call's stream).  Any number of taps works: a source row is at most 4096 bytes, so a chunk
+ * has at least four rows.  24.25 KiB of LDS. */
+struct JmEncScaleArgs {
+	JmEsPlan plan;
+	const uint8_t *const *src;   /* [count]: the source frames */
+	const uint32_t *tab;
+};
+
+__global__ void __launch_bounds__(256) k_enc_scale(JmEncArgs a, JmEncScaleArgs s) {
+	__shared__ __attribute__((aligned(16))) uint8_t src[JM_ES_SRC];
+	__shared__ __attribute__((aligned(16))) uint16_t ts[JM_ES_CR][JM_ES_TW];
+	__shared__ uint32_t vt[JM_ES_TH][2];
+	const uint32_t nl = s.plan.pl[0].tiles_x * s.plan.pl[0].tiles_y, nc = s.plan.pl[1].tiles_x * s.plan.pl[1].tiles_y;
+	uint32_t tile = blockIdx.x, comp = 0;
+	if (tile >= nl) { tile -= nl; comp = 1; if (tile >= nc) { tile -= nc; comp = 2; } }
+	const JmEsPlane q = comp ? s.plan.pl[1] : s.plan.pl[0];
+	const uint32_t ox0 = (tile % q.tiles_x) * JM_ES_TW, oy0 = (tile / q.tiles_x) * JM_ES_TH;
+	const uint32_t nw = min(JM_ES_TW, q.out_w - ox0), nh = min(JM_ES_TH, q.out_h - oy0);
+	const uint32_t *ex = s.tab + q.ent_x, *ey = s.tab + q.ent_y;
+	const uint16_t *wt = reinterpret_cast<const uint16_t *>(s.tab + s.plan.wts);
+	const uint32_t tid = threadIdx.x;
+	if (tid < nh) {
+		const uint32_t i = min(oy0 + tid, q.ay.n_out - 1u);
+		vt[tid][0] = ey[2u * i]; vt[tid][1] = ey[2u * i + 1u];
+	}
+	const uint32_t col = tid & (JM_ES_TW - 1u), rg = tid / JM_ES_TW;
+	const bool hcol = col < nw;
+	const uint32_t ci = min(ox0 + min(col, nw - 1u), q.ax.n_out - 1u);
+	const uint32_t he = ex[2u * ci], hoff = ex[2u * ci + 1u], hsize = he >> 16;
+	/* the tile's source rectangle (xmin and xmin + xsize do not decrease with the output index) */
+	const uint32_t ef = ex[2u * ox0], el = ex[2u * min(ox0 + nw - 1u, q.ax.n_out - 1u)];
+	const uint32_t vf = ey[2u * oy0], vl = ey[2u * min(oy0 + nh - 1u, q.ay.n_out - 1u)];
+	const uint32_t gran = comp ? 8u : 16u;
+	const uint32_t ax0 = (q.x0 + (ef & 0xffffu)) & ~(gran - 1u), ax1 = (q.x0 + (el & 0xffffu) + (el >> 16) + gran - 1u) & ~(gran - 1u);
+	const uint32_t stride = ax1 - ax0, cr_max = min(JM_ES_CR, JM_ES_SRC / stride);
+	const uint32_t sy0 = vf & 0xffffu, sy1 = (vl & 0xffffu) + (vl >> 16);
+	const uint32_t hbase = q.x0 - ax0 + (he & 0xffffu);
+	const uint32_t src_off = comp == 0 ? 0u : comp == 1 ? s.plan.src_luma : s.plan.src_luma + s.plan.src_chroma;
+	const uint32_t out_off = comp == 0 ? 0u : comp == 1 ? s.plan.out_luma : s.plan.out_luma + s.plan.out_chroma;
+	for (uint32_t k = blockIdx.y; k < a.count; k += gridDim.y) {
+		const uint8_t *P = s.src[k] + src_off + (size_t)q.y0 * q.src_w + ax0;
+		uint8_t *O = const_cast<uint8_t *>(a.pics[k].frame) + out_off;
+		uint32_t acc[4][4] = {};
+		for (uint32_t r0 = sy0; r0 < sy1; r0 += cr_max) {
+			const uint32_t cn = min(cr_max, sy1 - r0);
+			__syncthreads();                                       /* the last chunk's (or picture's) readers are done */
+			if (comp == 0) {
+				const uint32_t gpr = stride / 16u;
+				for (uint32_t g = tid; g < cn * gpr; g += 256u) {
+					const uint32_t r = g / gpr, x = (g - r * gpr) * 16u;
+					*reinterpret_cast<uint4 *>(src + r * stride + x) = *reinterpret_cast<const uint4 *>(P + (size_t)(r0 + r) * q.src_w + x);
+				}
+			} else {
+				const uint32_t gpr = stride / 8u;
+				for (uint32_t g = tid; g < cn * gpr; g += 256u) {
+					const uint32_t r = g / gpr, x = (g - r * gpr) * 8u;
+					*reinterpret_cast<uint2 *>(src + r * stride + x) = *reinterpret_cast<const uint2 *>(P + (size_t)(r0 + r) * q.src_w + x);
+				}
+			}
+			__syncthreads();
+			if (hcol) {
+				uint32_t h[JM_ES_CR / 2u] = {};
+				for (uint32_t j = 0; j < hsize; j++) {
+					const uint32_t w = wt[hoff + j];
+#pragma unroll
+					for (uint32_t i = 0; i < JM_ES_CR / 2u; i++) h[i] += w * src[min(rg + 2u * i, cn - 1u) * stride + hbase + j];
+				}
+#pragma unroll
+				for (uint32_t i = 0; i < JM_ES_CR / 2u; i++)
+					if (rg + 2u * i < cn) ts[rg + 2u * i][col] = (uint16_t)jm_es_round_h(h[i]);
+			}
+			__syncthreads();
+#pragma unroll
+			for (uint32_t i = 0; i < 4u; i++) {
+				const uint32_t idx = tid + 256u * i, ol = idx / (JM_ES_TW / 4u), cg = idx % (JM_ES_TW / 4u);
+				if (ol >= nh || cg * 4u >= nw) continue;
+				const uint32_t xmin = vt[ol][0] & 0xffffu, xsize = vt[ol][0] >> 16, woff = vt[ol][1];
+				const uint32_t lo = max(xmin, r0), hi = min(xmin + xsize, r0 + cn);
+				for (uint32_t sr = lo; sr < hi; sr++) {
+					const uint32_t w = wt[woff + sr - xmin];
+					const uint2 v = *reinterpret_cast<const uint2 *>(&ts[sr - r0][cg * 4u]);
+					acc[i][0] += w * (v.x & 0xffffu); acc[i][1] += w * (v.x >> 16);
+					acc[i][2] += w * (v.y & 0xffffu); acc[i][3] += w * (v.y >> 16);
+				}
+			}
+		}
+#pragma unroll
+		for (uint32_t i = 0; i < 4u; i++) {
+			const uint32_t idx = tid + 256u * i, ol = idx / (JM_ES_TW / 4u), cg = idx % (JM_ES_TW / 4u);
+			if (ol >= nh || cg * 4u >= nw) continue;
+			*reinterpret_cast<uint32_t *>(O + (size_t)(oy0 + ol) * q.out_w + ox0 + cg * 4u) =
+				jm_es_round_v(acc[i][0]) | (jm_es_round_v(acc[i][1]) << 8) | (jm_es_round_v(acc[i][2]) << 16) | (jm_es_round_v(acc[i][3]) << 24);
+		}
+	}
 }
 
 /* the macroblock of lane g: picture, row, column and the three plane pointers */
@@ -420,7 +529,13 @@ struct jsmpeg_hip_encoder_t {
 	uint32_t *d_slice;
 	uint64_t *d_result, *h_result;   /* h_result: pinned */
 	uint8_t *d_es;
-	uint8_t *d_store;                /* frames of the tensor input, allocated by the first jsmpeg_hip_encoder_encode_rgb */
+	uint8_t *d_store;                /* frames of the tensor and the scaled input, allocated by the first jsmpeg_hip_encoder_encode_rgb / _encode_scaled */
+	/* scaled input (jsmpeg_hip_encoder_encode_scaled; enc_scale.h), allocated by its first call */
+	uint32_t *d_scale_tab, *h_scale_tab;          /* the tap table; h_: pinned */
+	const uint8_t **d_scale_src, **h_scale_src;   /* [max_pictures] source frames; h_: pinned */
+	jsmpeg_hip_enc_source_t scale_key;            /* the geometry scale_plan and d_scale_tab were made for */
+	JmEsPlan scale_plan;
+	bool scale_have;
 	hipStream_t stream;
 	hipEvent_t ev[4], ev_done;
 	bool pending, valid, have_pass;
@@ -460,6 +575,9 @@ static void enc_free(jsmpeg_hip_encoder_t *e) {
 	hipFree(e->d_carry); hipFree(e->d_spent);
 	if (e->h_pics) hipHostFree(e->h_pics);
 	if (e->h_result) hipHostFree(e->h_result);
+	hipFree(e->d_scale_tab); hipFree(e->d_scale_src);
+	if (e->h_scale_tab) hipHostFree(e->h_scale_tab);
+	if (e->h_scale_src) hipHostFree(e->h_scale_src);
 	for (hipEvent_t &v : e->ev) if (v) hipEventDestroy(v);
 	if (e->ev_done) hipEventDestroy(e->ev_done);
 	delete e;
@@ -630,6 +748,16 @@ extern "C" int jsmpeg_hip_encoder_set_rate(jsmpeg_hip_encoder_t *e, uint32_t byt
 	return 0;
 }
 
+/* the stores of the scaled input, and the plan and table of `source` (kept while the geometry stays) */
+static int enc_alloc_scale(jsmpeg_hip_encoder_t *e) {
+	const size_t words = jm_es_table_bound((uint32_t)e->cfg.width, (uint32_t)e->cfg.height), np = e->cfg.max_pictures;
+	if (!e->d_scale_tab) HIP_TRY(jm_malloc(&e->d_scale_tab, 4 * words));
+	if (!e->h_scale_tab) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_scale_tab), 4 * words, hipHostMallocDefault));
+	if (!e->d_scale_src) HIP_TRY(jm_malloc(&e->d_scale_src, sizeof(uint8_t *) * np));
+	if (!e->h_scale_src) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_scale_src), sizeof(uint8_t *) * np, hipHostMallocDefault));
+	return 0;
+}
+
 /* the level loop (gop > 1, or rate control) between ev[1] and ev[3]; `a` is complete */
 static int enc_run_gop(jsmpeg_hip_encoder_t *e, const JmEncArgs &a, uint32_t count, hipStream_t st) {
 	JmEncPArgs p;
@@ -675,7 +803,7 @@ static int enc_run_gop(jsmpeg_hip_encoder_t *e, const JmEncArgs &a, uint32_t cou
 }
 
 static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const void *dev_rgb, uint32_t layout, uint32_t order,
-                   const uint32_t *stream, const uint8_t *qscale, uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream) {
+                   const jsmpeg_hip_enc_source_t *source, const uint32_t *stream, const uint8_t *qscale, uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream) {
 	g_err[0] = 0;
 	if (!e) return fail("encoder: NULL handle");
 	if (e->pending) return fail("encoder: an encode is in flight: jsmpeg_hip_encoder_sync (or a reader) settles it first");
@@ -684,6 +812,10 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 	if (count && !frames && !dev_rgb) return fail("encoder: NULL frames");
 	if (dev_rgb && (layout > JSMPEG_HIP_TENSOR_NHWC || order > JSMPEG_HIP_TENSOR_BGR)) return fail("encoder: layout %u / order %u unknown", layout, order);
 	if (!qscale && (quantiser_scale < 1 || quantiser_scale > 31)) return fail("encoder: quantiser_scale %u, must be 1 .. 31", quantiser_scale);
+	if (source) {
+		const char *why = jm_es_check(source);
+		if (why) return fail("encoder: %s", why);
+	}
 	for (uint32_t k = 0; k < count; k++) {
 		if (frames && !frames[k]) return fail("encoder: frames[%u] is NULL", k);
 		if (frames && ((uintptr_t)frames[k] & 15u)) return fail("encoder: frames[%u] is not 16-byte aligned", k);
@@ -698,6 +830,15 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 	if (chained && count && level_loop) {
 		if (!e->gop_ready && enc_alloc_gop(e) != 0) { enc_free_gop(e); return -1; }
 		if (!e->d_carry && enc_alloc_carry(e) != 0) return -1;
+	}
+	if (source && count) {
+		if (enc_alloc_scale(e) != 0) return -1;
+		if (!e->d_store) HIP_TRY(jm_malloc(&e->d_store, (size_t)e->frame_bytes * e->cfg.max_pictures));
+		if (!e->scale_have || memcmp(&e->scale_key, source, sizeof(*source)) != 0) {
+			e->scale_have = false;
+			e->scale_plan = jm_es_plan(source, (uint32_t)e->cfg.width, (uint32_t)e->cfg.height);
+			if (e->scale_plan.words > jm_es_table_bound((uint32_t)e->cfg.width, (uint32_t)e->cfg.height)) return fail("encoder: the tap table is larger than its bound");
+		}
 	}
 	e->count = count;
 	e->have_pass = true;
@@ -715,7 +856,7 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 	for (uint32_t k = 0; k < count; k++) {
 		const JmEncPlan &pl = e->plan[k];
 		JmEncPic &p = e->h_pics[k];
-		p.frame = frames ? (const uint8_t *)frames[k] : e->d_store + (size_t)k * e->frame_bytes;
+		p.frame = frames && !source ? (const uint8_t *)frames[k] : e->d_store + (size_t)k * e->frame_bytes;
 		p.stream = stream ? stream[k] : 0; p.ordinal = pl.ordinal; p.q = qscale ? qscale[k] : quantiser_scale;
 		p.last = pl.last; p.m = pl.m; p.before = pl.before; p.carry = pl.carry;
 		uint8_t *where[2];
@@ -742,6 +883,19 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 		const uint64_t quads = (uint64_t)count * (e->cw >> 1) * (e->ch >> 1);
 		k_enc_rgb<<<dim3((uint32_t)((quads + 255) / 256)), dim3(256), 0, st>>>(a, (const uint8_t *)dev_rgb, layout, order);
 	}
+	if (source) {
+		JmEncScaleArgs s;
+		if (!e->scale_have) {                                   /* (no pass is in flight: the pinned table is free) */
+			jm_es_table(e->scale_plan, e->h_scale_tab);
+			HIP_TRY(hipMemcpyAsync(e->d_scale_tab, e->h_scale_tab, 4 * (size_t)e->scale_plan.words, hipMemcpyHostToDevice, st));
+			e->scale_key = *source;
+			e->scale_have = true;
+		}
+		for (uint32_t k = 0; k < count; k++) e->h_scale_src[k] = (const uint8_t *)frames[k];
+		HIP_TRY(hipMemcpyAsync(e->d_scale_src, e->h_scale_src, sizeof(uint8_t *) * count, hipMemcpyHostToDevice, st));
+		s.plan = e->scale_plan; s.src = e->d_scale_src; s.tab = e->d_scale_tab;
+		k_enc_scale<<<dim3(s.plan.tiles, std::min(count, 65535u)), dim3(256), 0, st>>>(a, s);
+	}
 	HIP_TRY(hipEventRecord(e->ev[1], st));
 	e->pass_rate = rate;
 	e->pass_gop = level_loop;
@@ -767,13 +921,21 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 extern "C" int jsmpeg_hip_encoder_encode(jsmpeg_hip_encoder_t *e, const void *const *frames, const uint32_t *stream, const uint8_t *qscale,
                                          uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream) {
 	if (count && !frames) { g_err[0] = 0; return fail("encoder: NULL frames"); }
-	return enc_run(e, frames, nullptr, 0, 0, stream, qscale, count, quantiser_scale, flags, hip_stream);
+	return enc_run(e, frames, nullptr, 0, 0, nullptr, stream, qscale, count, quantiser_scale, flags, hip_stream);
+}
+
+extern "C" int jsmpeg_hip_encoder_encode_scaled(jsmpeg_hip_encoder_t *e, const void *const *frames, const jsmpeg_hip_enc_source_t *source,
+                                                const uint32_t *stream, const uint8_t *qscale, uint32_t count, uint32_t quantiser_scale,
+                                                uint32_t flags, void *hip_stream) {
+	if (!source) { g_err[0] = 0; return fail("encoder: null source descriptor"); }
+	if (count && !frames) { g_err[0] = 0; return fail("encoder: NULL frames"); }
+	return enc_run(e, frames, nullptr, 0, 0, source, stream, qscale, count, quantiser_scale, flags, hip_stream);
 }
 
 extern "C" int jsmpeg_hip_encoder_encode_rgb(jsmpeg_hip_encoder_t *e, const void *dev_rgb, uint32_t layout, uint32_t order, const uint32_t *stream,
                                              const uint8_t *qscale, uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream) {
 	if (count && !dev_rgb) { g_err[0] = 0; return fail("encoder: NULL tensor"); }
-	return enc_run(e, nullptr, dev_rgb, layout, order, stream, qscale, count, quantiser_scale, flags, hip_stream);
+	return enc_run(e, nullptr, dev_rgb, layout, order, nullptr, stream, qscale, count, quantiser_scale, flags, hip_stream);
 }
 
 extern "C" int jsmpeg_hip_encoder_sync(jsmpeg_hip_encoder_t *e) {
@@ -832,6 +994,12 @@ extern "C" const void *jsmpeg_hip_encoder_recon(jsmpeg_hip_encoder_t *e, uint32_
 	if (!e->pass_gop) { fail("encoder: the last call ran with gop 1: it keeps no reconstruction (jsmpeg_hip_encoder_set_gop)"); return nullptr; }
 	if (k >= e->count) { fail("encoder: picture %u of %u", k, e->count); return nullptr; }
 	return e->h_pics[k].recon;                                 /* the call's store, or a chained stream's carry frame */
+}
+
+extern "C" const void *jsmpeg_hip_encoder_source(jsmpeg_hip_encoder_t *e, uint32_t k) {
+	if (enc_ready(e) < 0) return nullptr;
+	if (k >= e->count) { fail("encoder: picture %u of %u", k, e->count); return nullptr; }
+	return e->h_pics[k].frame;                                 /* the caller's frame, or the handle's store (converted / scaled) */
 }
 
 extern "C" int jsmpeg_hip_encoder_chain_info(jsmpeg_hip_encoder_t *e, uint32_t stream, uint32_t out[2]) {

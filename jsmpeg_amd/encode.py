@@ -2,8 +2,8 @@
 the host-side TS mux.  Frames in HBM (a Batch's pool, a Live tick's pictures, any device pointers) or uint8 RGB torch tensors
 -> elementary streams in a device buffer that Batch.attach_device takes as it is.  I pictures, or -- Encoder.set_gop -- I + P
 with motion search on the device and a closed loop; one quantiser scale per picture, the caller's or -- Encoder.set_rate --
-chosen on the device for a budget in bytes.  torch is imported only when a tensor is
-handed in."""
+chosen on the device for a budget in bytes.  Frames of another size than the encoder's are cropped and scaled on the device,
+plane by plane (Encoder.encode_scaled: renditions).  torch is imported only when a tensor is handed in."""
 import ctypes
 
 import numpy as np
@@ -17,7 +17,8 @@ SYMBOLS = ("jsmpeg_hip_encoder_create", "jsmpeg_hip_encoder_destroy", "jsmpeg_hi
            "jsmpeg_hip_encoder_sync", "jsmpeg_hip_encoder_query", "jsmpeg_hip_encoder_es", "jsmpeg_hip_encoder_stream_range",
            "jsmpeg_hip_encoder_picture_range", "jsmpeg_hip_encoder_read_es", "jsmpeg_hip_encoder_timings", "jsmpeg_hip_ts_mux_host",
            "jsmpeg_hip_encoder_set_gop", "jsmpeg_hip_encoder_recon", "jsmpeg_hip_encoder_picture_stats",
-           "jsmpeg_hip_encoder_set_rate", "jsmpeg_hip_encoder_picture_rate", "jsmpeg_hip_encoder_chain_reset", "jsmpeg_hip_encoder_chain_info")
+           "jsmpeg_hip_encoder_set_rate", "jsmpeg_hip_encoder_picture_rate", "jsmpeg_hip_encoder_chain_reset", "jsmpeg_hip_encoder_chain_info",
+           "jsmpeg_hip_encoder_encode_scaled", "jsmpeg_hip_encoder_source")
 
 FRAME_RATES = {1: (24000, 1001), 2: (24, 1), 3: (25, 1), 4: (30000, 1001), 5: (30, 1), 6: (50, 1), 7: (60000, 1001), 8: (60, 1)}
 
@@ -34,6 +35,11 @@ class EncoderConfig(ctypes.Structure):
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("max_pictures", ctypes.c_uint32),
                 ("max_streams", ctypes.c_uint32), ("max_es_bytes", ctypes.c_uint64), ("frame_rate_code", ctypes.c_uint32),
                 ("device", ctypes.c_int32)]
+
+
+class EncSource(ctypes.Structure):
+    """jsmpeg_hip_enc_source_t: the geometry of the frames an Encoder.encode_scaled call scales"""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("width", "height", "crop_x", "crop_y", "crop_width", "crop_height", "antialias")]
 
 
 _bound = None
@@ -80,6 +86,10 @@ def lib():
         L.jsmpeg_hip_encoder_chain_reset.argtypes = [vp, u32]
         L.jsmpeg_hip_encoder_chain_info.restype = ctypes.c_int
         L.jsmpeg_hip_encoder_chain_info.argtypes = [vp, u32, ctypes.POINTER(u32)]
+        L.jsmpeg_hip_encoder_encode_scaled.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_encode_scaled.argtypes = [vp, vp, ctypes.POINTER(EncSource), vp, vp, u32, u32, u32, vp]
+        L.jsmpeg_hip_encoder_source.restype = vp
+        L.jsmpeg_hip_encoder_source.argtypes = [vp, u32]
         L.jsmpeg_hip_ts_mux_host.restype = ctypes.c_int64
         L.jsmpeg_hip_ts_mux_host.argtypes = [vp, vp, vp, vp, u32, u32, u32, ctypes.POINTER(ctypes.c_uint8), vp, u64]
         _bound = L
@@ -176,9 +186,32 @@ class Encoder:
                                                   n, qs, self._flags(end, chain), stream))
         self.count = n
 
-    def encode_batch(self, batch, pictures, streams=None, qscale=8, end=True, stream=None, chain=False):
+    def encode_scaled(self, frame_ptrs, source_size, crop=None, antialias=True, streams=None, qscale=8, end=True, stream=None, chain=False):
+        """encode() from frames of ANOTHER size: frame_ptrs are Y | Cr | Cb planes of the coded size of source_size = (width,
+        height), e.g. pool slots of a Batch or Live of that size; crop = (x, y, width, height) in display pixels, x / y even
+        (None: the whole picture).  The planes are cropped and scaled on the device into the encoder's own frame store --
+        torch's bilinear / antialiased filter in integers, bit for bit jsmpeg_amd/csrc/enc_scale.h -- and coded from there:
+        GOP, rate control and chain behave as in encode().  source(k) returns what was coded."""
+        ptrs = [int(p) if p else 0 for p in frame_ptrs]
+        n = len(ptrs)
+        arr = (ctypes.c_void_p * max(1, n))(*ptrs)
+        s, q, qs = self._lists(n, streams, qscale)
+        src = EncSource(int(source_size[0]), int(source_size[1]), *([int(v) for v in crop] if crop is not None else [0, 0, 0, 0]), 1 if antialias else 0)
+        self._ok(self.L.jsmpeg_hip_encoder_encode_scaled(self.h, arr, ctypes.byref(src), None if s is None else s.ctypes.data,
+                                                         None if q is None else q.ctypes.data, n, qs, self._flags(end, chain), stream))
+        self.count = n
+
+    def _encode_from(self, ptrs, size, crop, antialias, streams, qscale, end, stream, chain):
+        """planes of `size`: straight in when that is the encoder's size and nothing is cropped, scaled otherwise"""
+        if crop is None and tuple(size) == (self.width, self.height):
+            self.encode(ptrs, streams, qscale, end, stream, chain)
+        else:
+            self.encode_scaled(ptrs, size, crop, antialias, streams, qscale, end, stream, chain)
+
+    def encode_batch(self, batch, pictures, streams=None, qscale=8, end=True, stream=None, chain=False, crop=None, antialias=True):
         """pictures of a Batch's last decode, straight from its frame pool (the batch is synchronised first; a picture that was
-        not decoded is refused).  streams None: each picture's own stream number, which must then ascend."""
+        not decoded is refused).  streams None: each picture's own stream number, which must then ascend.  A batch of another
+        size than the encoder's, or a crop, goes through encode_scaled."""
         batch.sync()
         infos = [batch.picture_info(int(p)) for p in pictures]
         for p, info in zip(pictures, infos):
@@ -187,13 +220,15 @@ class Encoder:
         if streams is None:
             streams = [info.stream for info in infos]
         base = batch.frame_pool_ptr
-        self.encode([base + int(p) * batch.frame_stride for p in pictures], streams, qscale, end, stream, chain)
+        self._encode_from([base + int(p) * batch.frame_stride for p in pictures], (batch.width, batch.height), crop, antialias,
+                          streams, qscale, end, stream, chain)
 
-    def encode_live(self, live, pictures=None, streams=None, qscale=8, end=True, stream=None, chain=False):
+    def encode_live(self, live, pictures=None, streams=None, qscale=8, end=True, stream=None, chain=False, crop=None, antialias=True):
         """pictures of a Live's last tick (None: all of them, in tick order), from their device_frame pointers.  streams
         None: the pictures are sorted by their live stream id (stable) and numbered 0, 1, .. in that order -- or, with
         chain=True, each picture's live stream id IS its stream number (an id at or above max_streams is refused), so that a
-        stream keeps its identity when others join or leave.  Returns the pictures in the order they were encoded in."""
+        stream keeps its identity when others join or leave.  A live of another size than the encoder's, or a crop, goes
+        through encode_scaled: a rendition.  Returns the pictures in the order they were encoded in."""
         pics = live.pictures()
         if pictures is not None:
             pics = [pics[int(i)] for i in pictures]
@@ -208,7 +243,7 @@ class Encoder:
             else:
                 ids = sorted({p.stream for p in pics})
                 streams = [ids.index(p.stream) for p in pics]
-        self.encode([p.device_frame for p in pics], streams, qscale, end, stream, chain)
+        self._encode_from([p.device_frame for p in pics], (live.width, live.height), crop, antialias, streams, qscale, end, stream, chain)
         return pics
 
     def encode_tensor(self, x, streams=None, qscale=8, end=True, order="rgb", chain=False):
@@ -259,9 +294,23 @@ class Encoder:
             raise RuntimeError(_batch.last_error())
         return p
 
+    def source_ptr(self, k):
+        """device address of the planes picture k of the last call was coded from (Y | Cr | Cb of the coded size): the caller's
+        frame after encode, the encoder's store after encode_tensor (converted) and encode_scaled (scaled)"""
+        p = self.L.jsmpeg_hip_encoder_source(self.h, k)
+        if not p:
+            raise RuntimeError(_batch.last_error())
+        return p
+
+    def source(self, k):
+        """those planes on the host: (Y, Cr, Cb) uint8 of the coded size"""
+        return self._read_planes(self.source_ptr(k))
+
     def recon(self, k):
         """picture k's reconstruction on the host: (Y, Cr, Cb) uint8 planes of the coded size -- what a decoder shows"""
-        p = self.recon_ptr(k)
+        return self._read_planes(self.recon_ptr(k))
+
+    def _read_planes(self, p):
         out = np.empty(self.frame_bytes, dtype=np.uint8)
         L = _batch.lib()
         L.jsmpeg_hip_device_read.restype = ctypes.c_int

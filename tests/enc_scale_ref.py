@@ -1,0 +1,97 @@
+"""TEST INFRASTRUCTURE ONLY -- the numpy restatement of the encoder's scaled input (jsmpeg_amd/csrc/enc_scale.h), written from
+the rule's text and sharing nothing with the header: the taps of an axis as a dense weight matrix, the two passes as exact
+matrix products, the three planes, the edge replication."""
+import numpy as np
+
+ONE = 16384
+
+
+def coded(width, height):
+    return (width + 15) & ~15, (height + 15) & ~15
+
+
+def axis_taps(n_in, n_out, aa):
+    """[(first tap, [weights])] per output index"""
+    out = []
+    for i in range(n_out):
+        if n_in == n_out:
+            out.append((i, [ONE]))
+            continue
+        if aa and n_in > n_out:
+            c = (2 * i + 1) * n_in
+            j = np.arange(n_in, dtype=np.int64)
+            n = 2 * n_in - np.abs((2 * j + 1) * n_out - c)
+            js = np.nonzero(n > 0)[0]
+            first, ns = int(js[0]), [int(v) for v in n[js]]
+            assert list(js) == list(range(first, first + len(js))), "one contiguous run"
+        else:
+            num = max(0, (2 * i + 1) * n_in - n_out)
+            i0, r = divmod(num, 2 * n_out)
+            if i0 >= n_in - 1:
+                first, ns = n_in - 1, [1]
+            elif r == 0:
+                first, ns = i0, [1]
+            else:
+                first, ns = i0, [2 * n_out - r, r]
+        N = sum(ns)
+        w = [(2 * ONE * v + N) // (2 * N) for v in ns]
+        w[w.index(max(w))] += ONE - sum(w)
+        out.append((first, w))
+    return out
+
+
+def axis_matrix(n_in, n_out, aa):
+    """[n_out, n_in] int64"""
+    m = np.zeros((n_out, n_in), dtype=np.int64)
+    for i, (first, w) in enumerate(axis_taps(n_in, n_out, aa)):
+        m[i, first:first + len(w)] = w
+    return m
+
+
+def _product(a, b):
+    """a @ b for non-negative integers whose sums stay below 2^53: exact in float64, and BLAS does it"""
+    return np.rint(a.astype(np.float64) @ b.astype(np.float64)).astype(np.int64)
+
+
+def scale_plane(p, out_w, out_h, aa):
+    """p: [n_in_y, n_in_x] uint8 (the crop) -> [out_h, out_w] int64 in 0 .. 255"""
+    n_in_y, n_in_x = p.shape
+    t = (_product(p.astype(np.int64), axis_matrix(n_in_x, out_w, aa).T) + 32) >> 6
+    assert t.max() <= 65280
+    v = (_product(axis_matrix(n_in_y, out_h, aa), t) + (1 << 21)) >> 22
+    assert v.min() >= 0 and v.max() <= 255
+    return v
+
+
+def _extend(p, w, h):
+    ph, pw = p.shape
+    return np.pad(p, ((0, h - ph), (0, w - pw)), mode="edge")
+
+
+def source_planes(frame, width, height):
+    cw, ch = coded(width, height)
+    n = cw * ch
+    f = np.asarray(frame, dtype=np.uint8)
+    return f[:n].reshape(ch, cw), f[n:n + n // 4].reshape(ch // 2, cw // 2), f[n + n // 4:].reshape(ch // 2, cw // 2)
+
+
+def crops(frame, width, height, crop):
+    """the three crops the rule scales: [luma, Cr, Cb]"""
+    x, y, w, h = crop if crop and tuple(crop) != (0, 0, 0, 0) else (0, 0, width, height)
+    assert x % 2 == 0 and y % 2 == 0 and w >= 1 and h >= 1 and x + w <= width and y + h <= height
+    Y, Cr, Cb = source_planes(frame, width, height)
+    c = lambda p: p[y >> 1:(y >> 1) + ((h + 1) >> 1), x >> 1:(x >> 1) + ((w + 1) >> 1)]
+    return [Y[y:y + h, x:x + w], c(Cr), c(Cb)]
+
+
+def scaled_planes(frame, width, height, out_w, out_h, crop=None, aa=True):
+    """the scaled planes before the extension: [luma out_h x out_w, Cr, Cb ((out + 1) >> 1)]"""
+    sizes = [(out_w, out_h), ((out_w + 1) >> 1, (out_h + 1) >> 1), ((out_w + 1) >> 1, (out_h + 1) >> 1)]
+    return [scale_plane(p, w, h, aa) for p, (w, h) in zip(crops(frame, width, height, crop), sizes)]
+
+
+def scale_frame(frame, width, height, out_w, out_h, crop=None, aa=True):
+    """the encoder's frame: Y | Cr | Cb of the coded size of out_w x out_h, uint8"""
+    cw, ch = coded(out_w, out_h)
+    y, cr, cb = scaled_planes(frame, width, height, out_w, out_h, crop, aa)
+    return np.concatenate([_extend(y, cw, ch).ravel(), _extend(cr, cw // 2, ch // 2).ravel(), _extend(cb, cw // 2, ch // 2).ravel()]).astype(np.uint8)

@@ -13,6 +13,10 @@ A sixth step, `chain`: what a live relay runs -- 64 streams of 1080p, ONE pictur
 (Encoder.encode(chain=True)) the calls continue their streams; on a tree whose encoder has no chains the same calls are all I
 pictures -- that is the figure to hold against.  Its figures go to the bench (or, without chains, bench_unchained) section of
 profiles/enc_chain_notes.md.
+A seventh step, `scale`: renditions -- 64 streams of 1080p, one picture per stream per call, 24 calls, scaled to 640x360 and to
+1280x720 by Encoder.encode_scaled (chained, with --gop and --search, q = 8): the scale's "convert" time and the call's total,
+against the route through RGB in the same run (Batch.tensor(size=..., dtype=uint8), then encode_tensor: k_tensor + k_enc_rgb) and
+against a plain device copy of the bytes the scale moves.  Its figures go to the bench section of profiles/enc_scale_notes.md.
 
 Every GPU step is a child process of this tool under its own `timeout`; the steps are chained and the tool stops at the first
 one that fails.  The figures go into the bench section of profiles/enc_notes.md (nothing is written for a step that did not
@@ -20,7 +24,8 @@ run).
     python tools/encode_bench.py [--steps pool64,pool7680,tensor] [--reps 8]
     python tools/encode_bench.py --steps gop --gop 12 --search 7
     python tools/encode_bench.py --steps rate --gop 12 --search 7 --rate 40000
-    python tools/encode_bench.py --steps chain --gop 12 --search 7 --rate 40000 --reps 3"""
+    python tools/encode_bench.py --steps chain --gop 12 --search 7 --rate 40000 --reps 3
+    python tools/encode_bench.py --steps scale --gop 12 --search 7 --reps 3"""
 import argparse
 import json
 import os
@@ -35,7 +40,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 W, H = 1920, 1080
-STEPS = {"pool64": 300, "pool7680": 420, "tensor": 120, "gop": 300, "rate": 420, "chain": 420}          # seconds each step may take
+STEPS = {"pool64": 300, "pool7680": 420, "tensor": 120, "gop": 300, "rate": 420, "chain": 420, "scale": 420}          # seconds each step may take
 
 
 def median(v):
@@ -276,6 +281,69 @@ def step_chain(gop, search, target, reps):
         return dict(step="chain", chained=chained, gop=gop, search=search, target=target, streams=64, calls=CHAIN_CALLS, reps=reps, ways=ways)
 
 
+SCALE_SIZES = ((640, 360), (1280, 720))
+
+
+def step_scale(gop, search, reps):
+    """64 streams x 24 pictures of 1080p from a batch's pool, a picture per stream per call, chained, q = 8, into encoders of
+    640x360 and 1280x720: through encode_scaled, and through Batch.tensor(uint8) + encode_tensor (one round to warm up, `reps`
+    measured)"""
+    import torch
+    import bench
+    from jsmpeg_amd import batch as jb
+    from jsmpeg_amd import build, encode
+    usage = build.check_kernel_resources()
+    kernel = {n: v[n] for name, v in usage.items() if "k_enc_scale" in name for n in ("VGPRs", "LDS Size", "Occupancy", "ScratchSize")}
+    streams = [g[0] for g in bench.generate_streams(0, 64, CHAIN_CALLS)]
+    total = sum(len(s) for s in streams)
+    n = 64 * CHAIN_CALLS
+    with jb.Batch(W, H, 64, n + 8, total + 64 * 64 + 4096, device=0) as b:
+        b.upload(streams)
+        assert b.decode() == n
+        by_stream = {}
+        for p, i in enumerate(b.pictures()):
+            if i.decoded:
+                by_stream.setdefault(i.stream, []).append(p)
+        assert sorted(by_stream) == list(range(64)) and all(len(v) == CHAIN_CALLS for v in by_stream.values())
+        calls = [[by_stream[s][t] for s in range(64)] for t in range(CHAIN_CALLS)]
+        sn = list(range(64))
+        rate = copy_rate(b.L, 1 << 30, 8)
+        sizes = []
+        for ow, oh in SCALE_SIZES:
+            ways = []
+            with encode.Encoder(ow, oh, 64, 64, 64 << 20, device=0) as enc:
+                enc.set_gop(gop, search)
+                moved = 64 * (W * H * 3 // 2 + enc.frame_bytes)                # the source planes' display area read once, the coded frames written once
+                for name in ("encode_scaled", "Batch.tensor(uint8) + encode_tensor"):
+                    wall, convert, tensor_ms, dev, size = [], [], [], [], []
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    for r in range(reps + 1):
+                        enc.chain_reset()
+                        for pics in calls:
+                            t0 = time.perf_counter()
+                            if name == "encode_scaled":
+                                enc.encode_scaled([b.frame_pool_ptr + p * b.frame_stride for p in pics], (W, H), streams=sn, qscale=8, end=False, chain=True)
+                            else:
+                                e0.record()
+                                x = b.tensor(pictures=pics, size=(oh, ow), dtype=torch.uint8)
+                                e1.record()
+                                enc.encode_tensor(x, sn, 8, end=False, chain=True)
+                            enc.sync()
+                            if r >= 1:
+                                ms = enc.timings()
+                                wall.append((time.perf_counter() - t0) * 1e3)
+                                tensor_ms.append(e0.elapsed_time(e1) if name != "encode_scaled" else 0.0)
+                                convert.append(ms["convert_ms"] + tensor_ms[-1])
+                                dev.append(ms["total_ms"] + tensor_ms[-1])
+                                if r == 1:
+                                    size.append(sum(v for _, v in enc.picture_ranges()))
+                    ways.append(dict(name=name, calls=len(wall), wall_ms=median(wall), to_planes_ms=median(convert), to_planes_ms_min=round(min(convert), 3),
+                                     to_planes_ms_max=round(max(convert), 3), k_tensor_ms=median(tensor_ms), total_ms=median(dev),
+                                     bytes_per_picture=round(sum(size) / n)))
+            sizes.append(dict(width=ow, height=oh, moved_bytes=moved, copy_bound_ms=round(moved / (rate * 1e9) * 1e3, 3), ways=ways))
+        return dict(step="scale", gop=gop, search=search, streams=64, calls=CHAIN_CALLS, reps=reps, copy_GBps=round(rate, 1), sizes=sizes, kernel=kernel)
+
+
 def step_tensor():
     import torch
     import enc_inputs as ei
@@ -300,7 +368,24 @@ def step_tensor():
 def notes(results):
     lines = ["## Cost on the MI355X (measured by tools/encode_bench.py)", ""]
     for r in results:
-        if r["step"] == "chain":
+        if r["step"] == "scale":
+            lines = ["## Renditions: %d streams of 1080p, one picture per stream per call, %d chained calls, gop %d, search range %d, q = 8 (measured on an MI355X by tools/encode_bench.py)"
+                     % (r["streams"], r["calls"], r["gop"], r["search"]), ""]
+            for z in r["sizes"]:
+                lines += ["**To %dx%d.**  The scale reads and writes %d bytes per call; a plain device copy ran at %.1f GB/s in the same process and would move them in %.3f ms."
+                          % (z["width"], z["height"], z["moved_bytes"], r["copy_GBps"], z["copy_bound_ms"]), "",
+                          "| | planes ready (convert), median (min .. max), ms per call | of that k_tensor, ms | call total on the device, ms | call + sync, host clock, ms | bytes per picture |",
+                          "|---|---|---|---|---|---|"]
+                for w in z["ways"]:
+                    lines.append("| %s | %.3f (%.3f .. %.3f) | %s | %.3f | %.3f | %d |" % (
+                        w["name"], w["to_planes_ms"], w["to_planes_ms_min"], w["to_planes_ms_max"], "%.3f" % w["k_tensor_ms"] if w["k_tensor_ms"] else "-",
+                        w["total_ms"], w["wall_ms"], w["bytes_per_picture"]))
+                a, c = z["ways"][0], z["ways"][1]
+                lines += ["", "The fused scale takes %.2f times the copy's time and %.2f times the RGB route's (k_tensor + k_enc_rgb)."
+                          % (a["to_planes_ms"] / z["copy_bound_ms"], a["to_planes_ms"] / c["to_planes_ms"]), ""]
+            lines += ["Medians over %d measured calls each (%d rounds of %d behind one round to warm up).  k_enc_scale: %d VGPRs, %d bytes of LDS, occupancy %d, scratch %d."
+                      % (r["sizes"][0]["ways"][0]["calls"], r["reps"], r["calls"], r["kernel"]["VGPRs"], r["kernel"]["LDS Size"], r["kernel"]["Occupancy"], r["kernel"]["ScratchSize"]), ""]
+        elif r["step"] == "chain":
             lines = ["## %s: %d streams of 1080p, one picture per stream per call, %d calls, gop %d, search range %d, target %d bytes per picture (measured on an MI355X by tools/encode_bench.py)"
                      % ("Chained calls" if r["chained"] else "The same calls WITHOUT chains (every picture an I picture)", r["streams"], r["calls"], r["gop"], r["search"], r["target"]), "",
                      "| | bytes per picture | of I pictures | of P pictures | call + sync, host clock, ms | device, median (min .. max), ms per call | calls with I pictures, ms | calls with P pictures, ms |",
@@ -362,7 +447,7 @@ def main():
     ap.add_argument("--child")
     a = ap.parse_args()
     if a.child:
-        r = step_chain(a.gop, a.search, a.rate, a.reps) if a.child == "chain" else step_rate(a.gop, a.search, a.rate, a.reps) if a.child == "rate" else step_gop(a.gop, a.search, a.reps) if a.child == "gop" else step_tensor() if a.child == "tensor" else step_pool(a.child == "pool7680", a.reps)
+        r = step_scale(a.gop, a.search, a.reps) if a.child == "scale" else step_chain(a.gop, a.search, a.rate, a.reps) if a.child == "chain" else step_rate(a.gop, a.search, a.rate, a.reps) if a.child == "rate" else step_gop(a.gop, a.search, a.reps) if a.child == "gop" else step_tensor() if a.child == "tensor" else step_pool(a.child == "pool7680", a.reps)
         print("RESULT " + json.dumps(r), flush=True)
         return 0
     results = []
@@ -384,7 +469,9 @@ def main():
         replace_section(os.path.join(ROOT, "profiles", "enc_rate_notes.md"), "bench", notes([r]))
     for r in [r for r in results if r["step"] == "chain"]:
         replace_section(os.path.join(ROOT, "profiles", "enc_chain_notes.md"), "bench" if r["chained"] else "bench_unchained", notes([r]))
-    results = [r for r in results if r["step"] not in ("gop", "rate", "chain")]
+    for r in [r for r in results if r["step"] == "scale"]:
+        replace_section(os.path.join(ROOT, "profiles", "enc_scale_notes.md"), "bench", notes([r]))
+    results = [r for r in results if r["step"] not in ("gop", "rate", "chain", "scale")]
     if results:
         replace_section(NOTES, "bench", notes(results))
     return 0 if done == len(a.steps.split(",")) else 1
