@@ -1,7 +1,8 @@
 /*
- * MPEG-1 INTRA ENCODER, the per-macroblock device functions (include/jsmpeg_hip.h part 8): what the kernels of encode.hip
- * and the CPU simulator (tests/sim/sim_encode.cpp) share.  Host + device; on the CPU an atomic OR is a plain OR and a lane's
- * slot of LDS is a local array, nothing else differs.  tests/enc_ref.py restates every formula below in numpy.
+ * MPEG-1 INTRA ENCODER, the per-macroblock device functions (include/jsmpeg_hip.h part 8): what the lane bodies of enc_pass.h --
+ * and through them the kernels of encode.hip and the CPU simulator (tests/sim/sim_encode_pass.cpp) -- share.  Host + device; on
+ * the CPU an atomic OR is a plain OR and a lane's slot of LDS is a local array, nothing else differs. tests/enc_ref.py restates
+ * every formula below in numpy.
  *
  * I pictures here, one quantiser scale per picture, the default intra matrix, one slice per macroblock row; P pictures and the
  * closed loop they need (the encoder's reference must be the decoder's reconstruction) are enc_motion.h's, built on what is

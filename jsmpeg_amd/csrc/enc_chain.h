@@ -1,8 +1,9 @@
 /*
  * MPEG-1 ENCODER, P CHAINS AND GOP BUDGETS ACROSS CALLS (include/jsmpeg_hip.h part 8, JSMPEG_HIP_ENC_CHAIN): which ordinal,
  * which reference and which reconstruction store a picture of a call has, stated once, host + device -- what the host side of
- * encode.hip and the CPU simulator (tests/sim/sim_encode_chain.cpp) share.  Nothing here reads the device: a pass stays a pure
- * enqueue.
+ * encode.hip and the CPU simulator's chained calls (tests/sim/sim_encode_pass.cpp, sim_chain_encode) share: the plan of a whole
+ * call (jm_encc_plan_call), its pictures by level (jm_encc_levels), a frame number's address (jm_encc_frame) and the `spent`
+ * row a pick reads (jm_encc_spent_row).  Nothing here reads the device: a pass stays a pure enqueue.
  *
  * CHAIN.  A handle keeps a JmEncChain per stream number s < max_streams: `have` (the stream has chain state), `n` (the pictures
  *    coded so far = the ordinal of the next one), `parity` (which of the stream's two CARRY FRAMES holds its last
@@ -95,3 +96,42 @@ JM_HD void jm_encc_advance(JmEncChain &c, const JmEncPlan &last, bool rate, bool
 	if (end) { jm_encc_reset(c); return; }
 	c.have = 1; c.n = jm_encc_next(last.ordinal, gop); c.parity = (c.parity & 1u) ^ 1u; c.rated = rate ? 1u : 0u;
 }
+
+/* THE CALL'S PLAN, stream by stream: ordinals, GOP sizes and where the reconstructions lie for the `count` pictures of a call
+ * whose stream numbers ascend (stream == NULL: all stream 0), and the records advanced behind it.  chain: the handle's records,
+ * [max_streams]; an unchained call reads and writes none. */
+inline void jm_encc_plan_call(const uint32_t *stream, uint32_t count, JmEncChain *chain, bool rate, uint32_t gop, bool chained, bool end, JmEncPlan *plan) {
+	for (uint32_t k0 = 0; k0 < count;) {
+		const uint32_t s = stream ? stream[k0] : 0;
+		uint32_t n = 1;
+		while (k0 + n < count && (!stream || stream[k0 + n] == s)) n++;
+		jm_encc_plan(chained ? &chain[s] : nullptr, s, rate, gop, k0, n, &plan[k0]);
+		if (chained) jm_encc_advance(chain[s], plan[k0 + n - 1], rate, end, gop);
+		k0 += n;
+	}
+}
+
+/* The call's pictures by level = ordinal mod gop, a counting sort: list[begin[l] .. begin[l + 1]) are the pictures of level l in
+ * the call's order.  list: [count], begin: [gop + 1].  Returns the number of levels the call has. */
+inline uint32_t jm_encc_levels(const JmEncPlan *plan, uint32_t count, uint32_t gop, uint32_t *list, uint32_t *begin) {
+	uint32_t levels = 0;
+	for (uint32_t l = 0; l <= gop; l++) begin[l] = 0;
+	for (uint32_t k = 0; k < count; k++) {
+		const uint32_t l = plan[k].ordinal % gop;
+		begin[l + 1]++;
+		if (l + 1 > levels) levels = l + 1;
+	}
+	for (uint32_t l = 0; l < levels; l++) begin[l + 1] += begin[l];
+	for (uint32_t k = 0; k < count; k++) list[begin[plan[k].ordinal % gop]++] = k;      /* begin[l] is now where level l ends */
+	for (uint32_t l = levels; l > 0; l--) begin[l] = begin[l - 1];
+	begin[0] = 0;
+	return levels;
+}
+
+/* where frame number `frame` of a JmEncPlan lies: store: the call's frames, carry: the streams' carry frames */
+JM_HD uint8_t *jm_encc_frame(uint32_t frame, uint8_t *store, uint8_t *carry, size_t frame_bytes) {
+	return (frame & JM_ENCC_SLOT) ? carry + (size_t)(frame & ~JM_ENCC_SLOT) * frame_bytes : store + (size_t)frame * frame_bytes;
+}
+
+/* spent[2][max_streams]: the row a pick with `carry` reads (JM_ENCC_READ); the one it leaves (JM_ENCC_WRITE) is the other, row ^ 1 */
+JM_HD uint32_t jm_encc_spent_row(uint32_t carry) { return (carry & JM_ENCC_ODD) ? 1u : 0u; }

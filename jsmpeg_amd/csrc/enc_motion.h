@@ -1,6 +1,7 @@
 /*
  * MPEG-1 ENCODER, P PICTURES (include/jsmpeg_hip.h part 8, jsmpeg_hip_encoder_set_gop): the rules of the closed loop, stated
- * once, host + device -- what the kernels of encode.hip and the CPU simulator (tests/sim/sim_encode_p.cpp) share.
+ * once, host + device -- what the lane bodies of enc_pass.h, k_enc_motion of encode.hip and the CPU simulator
+ * (tests/sim/sim_encode_pass.cpp) share.
  * tests/enc_p_ref.py restates every rule below in numpy.  enc_block.h stays what the gop-1 pass compiles.
  *
  * 1. MOTION SEARCH, on luma, against the encoder's own reconstruction of the stream's previous picture.  Candidates: the

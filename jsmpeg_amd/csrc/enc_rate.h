@@ -1,7 +1,8 @@
 /*
  * MPEG-1 ENCODER, RATE CONTROL (include/jsmpeg_hip.h part 8, jsmpeg_hip_encoder_set_rate): the quantiser scale of a picture
- * chosen on the device from a budget in bytes, stated once, host + device -- what the kernels of encode.hip and the CPU
- * simulator (tests/sim/sim_encode_rate.cpp) share.  tests/enc_rate_ref.py restates the rule in numpy by brute force.
+ * chosen on the device from a budget in bytes, stated once, host + device -- what the lane bodies of enc_pass.h, k_enc_rate_pick
+ * of encode.hip and the CPU simulator's pick (tests/sim/sim_encode_pass.cpp) share.  tests/enc_rate_ref.py restates the rule in
+ * numpy by brute force.
  * enc_motion.h's rules 1 .. 5 stand as they are: this one only says which scale they run at.
  *
  * RATE.  The handle carries T, the target bytes per picture (0: off), a range q_min <= q_max within 1 .. 31 and W, the weight of
@@ -46,6 +47,8 @@ JM_HD uint64_t jm_encr_budget(uint64_t T, uint32_t m, uint32_t l, uint32_t W, ui
 	return left * w / S;
 }
 JM_HD uint32_t jm_encr_saturate(uint64_t v) { return v > 0xffffffffull ? 0xffffffffu : (uint32_t)v; }
+/* what a picture at level l of its GOP has in bytes before its slices: the headers */
+JM_HD uint32_t jm_encr_head_bytes(uint32_t l) { return l ? JM_ENC_P_HEAD_BYTES : JM_ENC_PIC_HEAD_BYTES; }
 
 /* block b of a macroblock at every q of [q_min, q_min + nq): acc[qi * as] += its pairs' bits | its pattern bit << 16 */
 template <bool INTER>

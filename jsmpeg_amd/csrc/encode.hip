@@ -1,8 +1,9 @@
 /*
- * MPEG-1 intra encoder on the device (include/jsmpeg_hip.h part 8): frames in HBM, or RGB tensors, to elementary streams
- * that a jsmpeg player, the reference decoder and this library's own batch / live front ends read.  The per-macroblock work
- * is enc_block.h's (shared with tests/sim/sim_encode.cpp); here are the kernels, the pass as a pure enqueue, and the host-side
- * TS mux.
+ * MPEG-1 encoder on the device (include/jsmpeg_hip.h part 8): frames in HBM, or RGB tensors, to elementary streams of I and P
+ * pictures that a jsmpeg player, the reference decoder and this library's own batch / live front ends read.  The arithmetic is
+ * enc_block.h's, enc_motion.h's, enc_rate.h's and enc_chain.h's, what a lane of a kernel does around it is enc_pass.h's -- all
+ * shared with the CPU simulator (tests/sim/sim_encode_pass.cpp); here are the kernels (those whose lanes work alone: their LDS,
+ * their guards and one call of their body), the pass as a pure enqueue, and the host-side TS mux.
  *
  * A pass on the caller's stream, every size and offset worked out on the device:
  *   k_enc_rgb            tensor input only: RGB -> Y | Cr | Cb of the coded size in the encoder's frame store
@@ -42,44 +43,11 @@
  * MEMORY, allocated by the first chained call that runs the level loop: two frames and 16 bytes per stream of max_streams.
  */
 #include "engine_internal.h"
-#include "enc_block.h"
-#include "enc_motion.h"
-#include "enc_rate.h"
-#include "enc_chain.h"
+#include "enc_pass.h"
 #include "enc_scale.h"
 
 #define JM_ENC_LANES 64
 #define JM_ENC_MOTION_WAVES 4    /* macroblocks (one wavefront each) of a k_enc_motion workgroup */
-
-struct JmEncPic {
-	const uint8_t *frame;    /* Y | Cr | Cb of the coded size */
-	const uint8_t *ref;      /* a P picture's reference: the reconstruction of the picture before (enc_chain.h, WHERE); level loop only */
-	uint8_t *recon;          /* where the picture is reconstructed; level loop only */
-	uint32_t stream, ordinal, q;
-	uint32_t last;           /* the last picture of its stream in this call */
-	uint32_t m;              /* the pictures its GOP is budgeted for (rate control) */
-	uint32_t before;         /* pictures of its GOP in front of it in this call (rate control) */
-	uint32_t carry;          /* JM_ENCC_READ | JM_ENCC_WRITE | JM_ENCC_ODD (rate control across calls) */
-};
-
-struct JmEncArgs {
-	uint32_t width, height, cw, ch, mbw, mbh, count, frame_rate_code, end;
-	uint64_t cap;
-	const JmEncPic *pics;
-	const JmEncTables *tables;
-	JmEncMb *mb;             /* [count][mbh][mbw] */
-	uint32_t *slice;         /* [count][mbh]: bytes, then offset in the picture */
-	uint64_t *result;        /* total | status | stream_begin[max_streams] | stream_end[max_streams] | pic_off[max_pictures] | pic_bytes (u32) */
-	uint32_t max_streams, max_pictures;
-	uint32_t *words;         /* the output */
-};
-JM_HD uint64_t *enc_stream_begin(const JmEncArgs &a) { return a.result + 2; }
-JM_HD uint64_t *enc_stream_end(const JmEncArgs &a) { return a.result + 2 + a.max_streams; }
-JM_HD uint64_t *enc_pic_off(const JmEncArgs &a) { return a.result + 2 + 2 * (size_t)a.max_streams; }
-JM_HD uint32_t *enc_pic_bytes(const JmEncArgs &a) { return (uint32_t *)(a.result + 2 + 2 * (size_t)a.max_streams + a.max_pictures); }
-static size_t enc_result_bytes(uint32_t max_streams, uint32_t max_pictures) {
-	return 8 * (2 + 2 * (size_t)max_streams + max_pictures) + 4 * (size_t)max_pictures;
-}
 
 /* ------------------------------------------------------------------ kernels */
 
@@ -199,42 +167,23 @@ __global__ void __launch_bounds__(256) k_enc_scale(JmEncArgs a, JmEncScaleArgs s
 	}
 }
 
-/* the macroblock of lane g: picture, row, column and the three plane pointers */
-struct EncLane { uint32_t k, row, col; const uint8_t *y, *cr, *cb; };
-static __device__ __forceinline__ EncLane enc_lane(const JmEncArgs &a, uint64_t g) {
-	EncLane l;
-	const uint32_t mbs = a.mbw * a.mbh, m = (uint32_t)(g % mbs);
-	l.k = (uint32_t)(g / mbs); l.row = m / a.mbw; l.col = m % a.mbw;
-	const uint8_t *f = a.pics[l.k].frame;
-	const size_t luma = (size_t)a.cw * a.ch, coff = (size_t)l.row * 8u * (a.cw >> 1) + (size_t)l.col * 8u;
-	l.y = f + (size_t)l.row * 16u * a.cw + (size_t)l.col * 16u;
-	l.cr = f + luma + coff;
-	l.cb = f + luma + (luma >> 2) + coff;
-	return l;
-}
-
 __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_measure(JmEncArgs a) {
 	__shared__ int16_t zz[64 * JM_ENC_LANES];
 	const uint64_t g = (uint64_t)blockIdx.x * JM_ENC_LANES + threadIdx.x;
 	if (g >= (uint64_t)a.count * a.mbw * a.mbh) return;
-	const EncLane l = enc_lane(a, g);
-	JmEncMb rec;
-	uint64_t dcs;
-	rec.bits = jm_enc_measure(l.y, l.cr, l.cb, a.cw, a.pics[l.k].q, a.tables, zz + threadIdx.x, JM_ENC_LANES, &dcs);
-	rec.dc[0] = (uint32_t)dcs; rec.dc[1] = (uint32_t)(dcs >> 32);
-	a.mb[g] = rec;
+	jm_pass_measure(a, g, zz + threadIdx.x, JM_ENC_LANES);
 }
 
 __global__ void __launch_bounds__(64) k_enc_scan_slices(JmEncArgs a) {
 	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
 	if (s >= a.count * a.mbh) return;
-	a.slice[s] = jm_enc_scan_slice(a.mb + (size_t)s * a.mbw, a.mbw, a.tables);
+	jm_pass_scan_slice(a, s);
 }
 
 __global__ void __launch_bounds__(64) k_enc_scan_pictures(JmEncArgs a) {
 	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
 	if (k >= a.count) return;
-	enc_pic_bytes(a)[k] = jm_enc_scan_picture(a.slice + (size_t)k * a.mbh, a.mbh);
+	jm_pass_scan_picture(a, k);
 }
 
 /* one workgroup: 256 pictures at a time through LDS, lane 0 walks them */
@@ -282,34 +231,10 @@ __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_write(JmEncArgs a) {
 	if (a.result[1]) return;
 	const uint64_t g = (uint64_t)blockIdx.x * JM_ENC_LANES + threadIdx.x;
 	if (g >= (uint64_t)a.count * a.mbw * a.mbh) return;
-	const EncLane l = enc_lane(a, g);
-	const JmEncPic pic = a.pics[l.k];
-	const uint64_t pic_at = enc_pic_off(a)[l.k], slice_at = pic_at + a.slice[(size_t)l.k * a.mbh + l.row];
-	if (l.col == 0) {
-		jm_enc_put_slice_header(a.words, slice_at, l.row, pic.q);
-		if (l.row == 0) {
-			jm_enc_put_picture_headers(a.words, pic_at, a.width, a.height, a.frame_rate_code, pic.ordinal);
-			if (pic.last) jm_enc_put_stream_tail(a.words, pic_at + enc_pic_bytes(a)[l.k], a.end != 0);
-			if (l.k == 0)
-				for (uint32_t i = 0; i < JM_ENC_LEAD_GAP / 4; i++) jm_enc_or(a.words + i, 0xffffffffu);
-		}
-	}
-	const uint32_t pred = l.col ? jm_enc_pred_of(jm_enc_mb_dcs(a.mb[g - 1])) : JM_ENC_PRED0;
-	JmEncBits bw = jm_enc_bits_at(a.words, slice_at * 8u + a.mb[g].bits);
-	jm_enc_write(l.y, l.cr, l.cb, a.cw, pic.q, a.tables, zz + threadIdx.x, JM_ENC_LANES, pred, bw);
-	jm_enc_flush(bw);
+	jm_pass_write(a, g, zz + threadIdx.x, JM_ENC_LANES);
 }
 
-/* ------------------------------------------------------------------ kernels of a GOP (gop > 1) */
-
-struct JmEncPArgs {
-	JmEncPMb *pmb;               /* [count][mbh][mbw] */
-	const JmEncPTables *ptables;
-	const uint32_t *list;        /* the call's picture numbers, sorted by level */
-	uint32_t *slice_kinds;       /* [count][mbh][4] */
-	uint32_t *stats;             /* [count][4] */
-	uint32_t gop, search, r_size;
-};
+/* ------------------------------------------------------------------ kernels of the level loop (gop > 1, or rate control) */
 
 static __device__ __forceinline__ uint64_t enc_wave_min(uint64_t v) {
 #pragma unroll
@@ -370,50 +295,15 @@ __global__ void __launch_bounds__(64 * JM_ENC_MOTION_WAVES) k_enc_motion(JmEncAr
 	if (live && lane == 0) p.pmb[(size_t)k * mbs + m].info = jm_encp_decide(sad, activity, mvh, mvv);
 }
 
-/* the macroblock of lane g of the n pictures list[first ..] */
-struct EncPLane { uint32_t k, m, row, col; };
-static __device__ __forceinline__ EncPLane encp_lane(const JmEncArgs &a, const JmEncPArgs &p, uint32_t first, uint64_t g) {
-	EncPLane l;
-	const uint32_t mbs = a.mbw * a.mbh;
-	l.k = p.list[first + (uint32_t)(g / mbs)]; l.m = (uint32_t)(g % mbs); l.row = l.m / a.mbw; l.col = l.m % a.mbw;
-	return l;
-}
-
 __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_measure_p(JmEncArgs a, JmEncPArgs p, uint32_t first, uint32_t n) {
 	__shared__ int16_t zz[64 * JM_ENC_LANES];
 	__shared__ uint32_t pp[16 * JM_ENC_LANES];
 	const uint64_t g = (uint64_t)blockIdx.x * JM_ENC_LANES + threadIdx.x;
 	if (g >= (uint64_t)n * a.mbw * a.mbh) return;
-	const EncPLane l = encp_lane(a, p, first, g);
-	const JmEncPic pic = a.pics[l.k];
-	JmEncPMb *rec = p.pmb + ((size_t)l.k * a.mbw * a.mbh + l.m);
-	JM_GLOBAL uint8_t *recon = (JM_GLOBAL uint8_t *)pic.recon;
-	const uint32_t found = (pic.ordinal % p.gop) ? rec->info : 0u;
-	JmEncPMb out;
-	out.dc[0] = out.dc[1] = 0; out.inh = 0; out.pred = 0;
-	if (found & 1u) {
-		out.bits = jm_encp_measure_inter((JM_GLOBAL const uint8_t *)pic.frame, (JM_GLOBAL const uint8_t *)pic.ref, recon, a.cw, a.ch, a.mbw, l.col, l.row,
-		                                 jm_encp_mvh(found), jm_encp_mvv(found), pic.q, a.tables, p.ptables, zz + threadIdx.x, JM_ENC_LANES,
-		                                 pp + threadIdx.x, JM_ENC_LANES, &out.info);
-	} else {
-		uint64_t dcs;
-		out.bits = jm_encp_measure_intra((JM_GLOBAL const uint8_t *)pic.frame, recon, a.cw, a.ch, l.col, l.row, pic.q, a.tables, zz + threadIdx.x, JM_ENC_LANES, &dcs);
-		out.dc[0] = (uint32_t)dcs; out.dc[1] = (uint32_t)(dcs >> 32);
-		out.info = jm_encp_info(JM_ENCP_INTRA, false, 0, 0, 0);
-	}
-	*rec = out;
+	jm_pass_measure_p(a, p, first, g, zz + threadIdx.x, JM_ENC_LANES, pp + threadIdx.x, JM_ENC_LANES);
 }
 
 /* ------------------------------------------------------------------ kernels of rate control (enc_rate.h) */
-
-struct JmEncRArgs {
-	uint16_t *rec;               /* [count][mbh][mbw][JM_ENCR_MAX_Q]: jm_encr_record */
-	uint32_t *slice;             /* [count][mbh][JM_ENCR_MAX_Q]: a slice's bytes at every scale */
-	uint32_t *out;               /* [count][4]: q, budget (saturated), bytes, 0 */
-	uint64_t *spent;             /* [2][max_streams]: the final bytes of a stream's unfinished GOP, from call to call (enc_chain.h, RATE); chained calls only */
-	uint64_t T;
-	uint32_t q_min, nq, W;
-};
 
 __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_rate_measure(JmEncArgs a, JmEncPArgs p, JmEncRArgs r, uint32_t first, uint32_t n) {
 	__shared__ int16_t zz[64 * JM_ENC_LANES];
@@ -421,7 +311,7 @@ __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_rate_measure(JmEncArgs a, 
 	__shared__ uint32_t acc[JM_ENCR_MAX_Q * JM_ENC_LANES];
 	const uint64_t g = (uint64_t)blockIdx.x * JM_ENC_LANES + threadIdx.x;
 	if (g >= (uint64_t)n * a.mbw * a.mbh) return;
-	const EncPLane l = encp_lane(a, p, first, g);
+	const JmEncLane l = jm_pass_lane<true>(a, p.list, first, g);
 	const JmEncPic pic = a.pics[l.k];
 	const size_t at = (size_t)l.k * a.mbw * a.mbh + l.m;
 	JmEncPMb *rec = p.pmb + at;
@@ -448,7 +338,7 @@ __global__ void __launch_bounds__(64) k_enc_rate_pick(JmEncArgs a, JmEncPArgs p,
 	const uint32_t lane = threadIdx.x, k = p.list[first + blockIdx.x];
 	const JmEncPic pic = a.pics[k];
 	const uint32_t level = pic.ordinal % p.gop;
-	uint32_t bytes = level ? JM_ENC_P_HEAD_BYTES : JM_ENC_PIC_HEAD_BYTES;
+	uint32_t bytes = jm_encr_head_bytes(level);
 	if (lane < r.nq)
 		for (uint32_t row = 0; row < a.mbh; row++) bytes += r.slice[((size_t)k * a.mbh + row) * JM_ENCR_MAX_Q + lane];
 	/* the GOP's pictures at the levels before: the `before` pictures in front of this one (all `level` of them unless the GOP
@@ -457,7 +347,7 @@ __global__ void __launch_bounds__(64) k_enc_rate_pick(JmEncArgs a, JmEncPArgs p,
 	for (uint32_t j = 1 + lane; j <= pic.before; j += 64u) spent += r.out[(size_t)(k - j) * 4 + 2];
 #pragma unroll
 	for (int o = 32; o; o >>= 1) spent += __shfl_xor((unsigned long long)spent, o);
-	const uint32_t odd = (pic.carry & JM_ENCC_ODD) ? 1u : 0u;
+	const uint32_t odd = jm_encc_spent_row(pic.carry);
 	if (pic.carry & JM_ENCC_READ) spent += r.spent[(size_t)odd * a.max_streams + pic.stream];
 	const uint64_t budget = jm_encr_budget(r.T, pic.m, level, r.W, spent);
 	const uint32_t fit = (uint32_t)enc_wave_min(lane < r.nq && bytes <= budget ? lane : r.nq - 1u);
@@ -472,20 +362,13 @@ __global__ void __launch_bounds__(64) k_enc_rate_pick(JmEncArgs a, JmEncPArgs p,
 __global__ void __launch_bounds__(64) k_enc_scan_slices_p(JmEncArgs a, JmEncPArgs p) {
 	const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
 	if (s >= a.count * a.mbh) return;
-	uint32_t kinds[4] = { 0, 0, 0, 0 };
-	a.slice[s] = jm_encp_scan_slice(p.pmb + (size_t)s * a.mbw, a.mbw, (a.pics[s / a.mbh].ordinal % p.gop) != 0, p.r_size, a.tables, p.ptables, kinds);
-	for (int i = 0; i < 4; i++) p.slice_kinds[(size_t)s * 4 + i] = kinds[i];
+	jm_pass_scan_slice_p(a, p, s);
 }
 
 __global__ void __launch_bounds__(64) k_enc_scan_pictures_p(JmEncArgs a, JmEncPArgs p) {
 	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
 	if (k >= a.count) return;
-	enc_pic_bytes(a)[k] = jm_encp_scan_picture(a.slice + (size_t)k * a.mbh, a.mbh, (a.pics[k].ordinal % p.gop) ? JM_ENC_P_HEAD_BYTES : JM_ENC_PIC_HEAD_BYTES);
-	for (int i = 0; i < 4; i++) {
-		uint32_t sum = 0;
-		for (uint32_t r = 0; r < a.mbh; r++) sum += p.slice_kinds[((size_t)k * a.mbh + r) * 4 + i];
-		p.stats[(size_t)k * 4 + i] = sum;
-	}
+	jm_pass_scan_picture_p(a, p, k);
 }
 
 __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_write_p(JmEncArgs a, JmEncPArgs p) {
@@ -494,26 +377,7 @@ __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_write_p(JmEncArgs a, JmEnc
 	if (a.result[1]) return;
 	const uint64_t g = (uint64_t)blockIdx.x * JM_ENC_LANES + threadIdx.x;
 	if (g >= (uint64_t)a.count * a.mbw * a.mbh) return;
-	const uint32_t mbs = a.mbw * a.mbh, k = (uint32_t)(g / mbs), m = (uint32_t)(g % mbs), row = m / a.mbw, col = m % a.mbw;
-	const JmEncPic pic = a.pics[k];
-	const bool p_picture = (pic.ordinal % p.gop) != 0;
-	const uint64_t pic_at = enc_pic_off(a)[k], slice_at = pic_at + a.slice[(size_t)k * a.mbh + row];
-	if (col == 0) {
-		jm_enc_put_slice_header(a.words, slice_at, row, pic.q);
-		if (row == 0) {
-			if (p_picture) jm_encp_put_picture_header(a.words, pic_at, pic.ordinal % p.gop, p.r_size);
-			else jm_enc_put_picture_headers(a.words, pic_at, a.width, a.height, a.frame_rate_code, pic.ordinal);
-			if (pic.last) jm_enc_put_stream_tail(a.words, pic_at + enc_pic_bytes(a)[k], a.end != 0);
-			if (k == 0)
-				for (uint32_t i = 0; i < JM_ENC_LEAD_GAP / 4; i++) jm_enc_or(a.words + i, 0xffffffffu);
-		}
-	}
-	const JmEncPMb rec = p.pmb[g];
-	JmEncBits bw = jm_enc_bits_at(a.words, slice_at * 8u + rec.bits);
-	JM_GLOBAL const uint8_t *ref = (JM_GLOBAL const uint8_t *)pic.ref;
-	jm_encp_write(rec, (JM_GLOBAL const uint8_t *)pic.frame, ref, a.cw, a.ch, col, row, p_picture, p.r_size, pic.q, a.tables, p.ptables, zz + threadIdx.x, JM_ENC_LANES,
-	              pp + threadIdx.x, JM_ENC_LANES, bw);
-	jm_enc_flush(bw);
+	jm_pass_write_p(a, p, g, zz + threadIdx.x, JM_ENC_LANES, pp + threadIdx.x, JM_ENC_LANES);
 }
 
 /* ------------------------------------------------------------------ the handle */
@@ -764,16 +628,8 @@ static int enc_run_gop(jsmpeg_hip_encoder_t *e, const JmEncArgs &a, uint32_t cou
 	p.pmb = e->d_pmb; p.ptables = e->d_ptables; p.list = e->d_list;
 	p.slice_kinds = e->d_slice_kinds; p.stats = e->d_stats;
 	p.gop = e->gop; p.search = e->search; p.r_size = jm_encp_r_size(e->search);
-	/* the pictures by level = ordinal mod gop: a counting sort of what the host already has */
-	uint32_t levels = 0;
-	for (uint32_t k = 0; k < count; k++) levels = std::max(levels, e->h_pics[k].ordinal % e->gop + 1);
-	std::vector<uint32_t> begin(levels + 1, 0);
-	for (uint32_t k = 0; k < count; k++) begin[e->h_pics[k].ordinal % e->gop + 1]++;
-	for (uint32_t l = 0; l < levels; l++) begin[l + 1] += begin[l];
-	{
-		std::vector<uint32_t> at(begin.begin(), begin.end() - 1);
-		for (uint32_t k = 0; k < count; k++) e->h_list[at[e->h_pics[k].ordinal % e->gop]++] = k;
-	}
+	std::vector<uint32_t> begin(e->gop + 1);
+	const uint32_t levels = jm_encc_levels(e->plan.data(), count, e->gop, e->h_list, begin.data());
 	HIP_TRY(hipMemcpyAsync(e->d_list, e->h_list, sizeof(uint32_t) * count, hipMemcpyHostToDevice, st));
 	const uint64_t mbs = (uint64_t)e->mbw * e->mbh;
 	JmEncRArgs r;
@@ -845,26 +701,15 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 	e->pass_chain = chained;
 	if (count == 0) { e->valid = true; e->h_result[0] = 0; e->h_result[1] = 0; return 0; }
 	if (dev_rgb && !e->d_store) HIP_TRY(jm_malloc(&e->d_store, (size_t)e->frame_bytes * e->cfg.max_pictures));
-	for (uint32_t k0 = 0; k0 < count;) {                       /* stream by stream: ordinals, GOP sizes, where the reconstructions lie (enc_chain.h) */
-		const uint32_t s = stream ? stream[k0] : 0;
-		uint32_t n = 1;
-		while (k0 + n < count && (!stream || stream[k0 + n] == s)) n++;
-		jm_encc_plan(chained ? &e->chain[s] : nullptr, s, rate, e->gop, k0, n, &e->plan[k0]);
-		if (chained) jm_encc_advance(e->chain[s], e->plan[k0 + n - 1], rate, end, e->gop);
-		k0 += n;
-	}
+	jm_encc_plan_call(stream, count, e->chain.data(), rate, e->gop, chained, end, e->plan.data());
 	for (uint32_t k = 0; k < count; k++) {
 		const JmEncPlan &pl = e->plan[k];
 		JmEncPic &p = e->h_pics[k];
 		p.frame = frames && !source ? (const uint8_t *)frames[k] : e->d_store + (size_t)k * e->frame_bytes;
 		p.stream = stream ? stream[k] : 0; p.ordinal = pl.ordinal; p.q = qscale ? qscale[k] : quantiser_scale;
 		p.last = pl.last; p.m = pl.m; p.before = pl.before; p.carry = pl.carry;
-		uint8_t *where[2];
-		const uint32_t frame_of[2] = { pl.ref, pl.recon };
-		for (int i = 0; i < 2; i++)
-			where[i] = !level_loop ? nullptr : (frame_of[i] & JM_ENCC_SLOT) ? e->d_carry + (size_t)(frame_of[i] & ~JM_ENCC_SLOT) * e->frame_bytes
-			                                                                : e->d_recon + (size_t)frame_of[i] * e->frame_bytes;
-		p.ref = where[0]; p.recon = where[1];
+		p.ref = level_loop ? jm_encc_frame(pl.ref, e->d_recon, e->d_carry, e->frame_bytes) : nullptr;
+		p.recon = level_loop ? jm_encc_frame(pl.recon, e->d_recon, e->d_carry, e->frame_bytes) : nullptr;
 	}
 	JmEncArgs a;
 	a.width = (uint32_t)e->cfg.width; a.height = (uint32_t)e->cfg.height; a.cw = e->cw; a.ch = e->ch; a.mbw = e->mbw; a.mbh = e->mbh;

@@ -1,11 +1,8 @@
 """TEST INFRASTRUCTURE ONLY -- what the tests of the encoder's chains across calls (JSMPEG_HIP_ENC_CHAIN) share, beside
 tests/enc_p_inputs.py and tests/enc_rate_inputs.py: the CPU simulator of a handle that is called again and again
-(tests/sim/sim_encode_chain.cpp, built on demand), the ways of cutting n pictures into calls, and the ledger that gathers what
+(sim_chain_* of tests/sim/sim_encode_pass.cpp, built on demand), the ways of cutting n pictures into calls, and the ledger that gathers what
 the calls leave per stream, segment by segment, to be held against ONE unchained call over the segment's pictures."""
 import ctypes
-import glob
-import os
-import subprocess
 
 import numpy as np
 
@@ -15,24 +12,19 @@ import enc_rate_inputs as er
 import enc_ref
 
 ROOT = ei.ROOT
-SIM_DIR = os.path.join(ROOT, "tests", "sim")
-SIM_SRC = os.path.join(SIM_DIR, "sim_encode_chain.cpp")
-CXXFLAGS = ["-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-I", ei.CSRC, "-I", os.path.join(ROOT, "include")]
+SIM_DIR, SIM_SRC, CXXFLAGS = ei.SIM_DIR, ei.PASS_SRC, ei.CXXFLAGS      # what the stand-alone sanitizer build of the tests uses
 ALL = 0xffffffff
 _sim = None
 
 
 def sim_deps():
-    return [SIM_SRC, os.path.join(SIM_DIR, "sim_encode_rate.cpp"), os.path.join(SIM_DIR, "sim_encode_p.cpp")] + glob.glob(os.path.join(ei.CSRC, "*.h"))
+    return ei.sim_deps(SIM_SRC)
 
 
 def sim():
     global _sim
     if _sim is None:
-        so = os.path.join(SIM_DIR, "libjsmpeg_sim_encode_chain.so")
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in sim_deps()):
-            subprocess.check_call(["g++", "-O2", "-fPIC", "-shared"] + CXXFLAGS + ["-o", so, SIM_SRC])
-        lib = ctypes.CDLL(so)
+        lib = ei.pass_sim()
         vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
         lib.sim_chain_create.restype = vp
         lib.sim_chain_create.argtypes = [u32, u32, u32, u32]

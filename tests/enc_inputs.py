@@ -1,5 +1,6 @@
-"""TEST INFRASTRUCTURE ONLY -- what the encoder's tests and tools share: the CPU simulator of the encoder's kernels
-(tests/sim/sim_encode.cpp, built on demand), the input pictures, and small stream helpers."""
+"""TEST INFRASTRUCTURE ONLY -- what the encoder's tests and tools share: the builder of the CPU simulators (build_sim), the
+simulator of the encoder's pass (tests/sim/sim_encode_pass.cpp, built on demand; its intra entry points are bound here, the
+others in enc_p_inputs, enc_rate_inputs and enc_chain_inputs), the input pictures, and small stream helpers."""
 import ctypes
 import glob
 import os
@@ -15,19 +16,38 @@ import enc_ref  # noqa: E402
 import mpeg1_enc  # noqa: E402
 
 CSRC = os.path.join(ROOT, "jsmpeg_amd", "csrc")
+SIM_DIR = os.path.join(ROOT, "tests", "sim")
+PASS_SRC = os.path.join(SIM_DIR, "sim_encode_pass.cpp")
+CXXFLAGS = ["-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-I", CSRC, "-I", os.path.join(ROOT, "include")]
+_libs = {}
 _sim = None
+
+
+def sim_deps(source, deps=()):
+    """what a simulator is built from: its source, the headers it may include, and `deps`"""
+    return [source] + list(deps) + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(ROOT, "include", "jsmpeg_hip.h")]
+
+
+def build_sim(source, name, deps=()):
+    """tests/sim/lib<name>.so from `source`, rebuilt when anything of sim_deps is newer; the library, one object per name"""
+    if name not in _libs:
+        so = os.path.join(SIM_DIR, "lib%s.so" % name)
+        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in sim_deps(source, deps)):
+            subprocess.check_call(["g++", "-O2", "-fPIC", "-shared"] + CXXFLAGS + ["-o", so, source])
+        _libs[name] = ctypes.CDLL(so)
+    return _libs[name]
+
+
+def pass_sim():
+    """the simulator of the encoder's pass: one library behind the sim() of this module, enc_p_inputs, enc_rate_inputs and
+    enc_chain_inputs, each of which binds its own entry points"""
+    return build_sim(PASS_SRC, "jsmpeg_sim_encode_pass")
 
 
 def sim():
     global _sim
     if _sim is None:
-        so = os.path.join(ROOT, "tests", "sim", "libjsmpeg_sim_encode.so")
-        src = os.path.join(ROOT, "tests", "sim", "sim_encode.cpp")
-        deps = [src] + glob.glob(os.path.join(CSRC, "*.h"))
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-I", CSRC,
-                                   "-I", os.path.join(ROOT, "include"), "-o", so, src])
-        lib = ctypes.CDLL(so)
+        lib = pass_sim()
         vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
         lib.sim_encode.restype = ctypes.c_int64
         lib.sim_encode.argtypes = [vp, u32, u32, u32, vp, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp]

@@ -1,10 +1,7 @@
 """TEST INFRASTRUCTURE ONLY -- what the tests and tools of the encoder's GOP pass (I + P pictures) share, beside
-tests/enc_inputs.py: the CPU simulator of its kernels (tests/sim/sim_encode_p.cpp, built on demand), the inputs of the issue's
-list, and the oracle as judge of a stream."""
+tests/enc_inputs.py: the CPU simulator of its kernels (sim_encode_p of tests/sim/sim_encode_pass.cpp, built on demand), the
+inputs of the issue's list, and the oracle as judge of a stream."""
 import ctypes
-import glob
-import os
-import subprocess
 
 import numpy as np
 
@@ -21,13 +18,7 @@ _sim = None
 def sim():
     global _sim
     if _sim is None:
-        so = os.path.join(ROOT, "tests", "sim", "libjsmpeg_sim_encode_p.so")
-        src = os.path.join(ROOT, "tests", "sim", "sim_encode_p.cpp")
-        deps = [src] + glob.glob(os.path.join(ei.CSRC, "*.h"))
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function",
-                                   "-I", ei.CSRC, "-I", os.path.join(ROOT, "include"), "-o", so, src])
-        lib = ctypes.CDLL(so)
+        lib = ei.pass_sim()
         vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
         lib.sim_encode_p.restype = ctypes.c_int64
         lib.sim_encode_p.argtypes = [vp, u32, u32, u32, vp, vp, u32, u32, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp]

@@ -1,9 +1,7 @@
 """TEST INFRASTRUCTURE ONLY -- what the tests of the encoder's scaled input share: the CPU simulator
 (tests/sim/sim_encode_scale.cpp, built on demand), the named cases, their content and the seeded sweep of geometries."""
 import ctypes
-import glob
 import os
-import subprocess
 
 import numpy as np
 
@@ -25,13 +23,7 @@ def source(width, height, crop=None, aa=1):
 def sim():
     global _sim
     if _sim is None:
-        so = os.path.join(ROOT, "tests", "sim", "libjsmpeg_sim_encode_scale.so")
-        src = os.path.join(ROOT, "tests", "sim", "sim_encode_scale.cpp")
-        deps = [src] + glob.glob(os.path.join(ei.CSRC, "*.h")) + [os.path.join(ROOT, "include", "jsmpeg_hip.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-I", ei.CSRC,
-                                   "-I", os.path.join(ROOT, "include"), "-o", so, src])
-        lib = ctypes.CDLL(so)
+        lib = ei.build_sim(os.path.join(ei.SIM_DIR, "sim_encode_scale.cpp"), "jsmpeg_sim_encode_scale")
         vp, u32 = ctypes.c_void_p, ctypes.c_uint32
         lib.sim_es_check.restype = ctypes.c_char_p
         lib.sim_es_check.argtypes = [ctypes.POINTER(Source)]

@@ -1,5 +1,5 @@
 """The encoder's chains across calls (JSMPEG_HIP_ENC_CHAIN; the rule: jsmpeg_amd/csrc/enc_chain.h) without a GPU: the simulator of
-a handle that is called again and again (tests/sim/sim_encode_chain.cpp) against the yardstick -- the one-call encoder as it
+a handle that is called again and again (sim_chain_* of tests/sim/sim_encode_pass.cpp) against the yardstick -- the one-call encoder as it
 was (ep.sim_encode_p, er.sim_encode_rate) on the same pictures: the pieces concatenated, every picture's reconstruction, kinds,
 bytes and rate choice.  Where a chain is ended the segments between the ends are the units."""
 import ctypes

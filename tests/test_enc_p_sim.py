@@ -1,5 +1,5 @@
 """The encoder's GOP pass (I + P pictures, jsmpeg_amd/csrc/enc_motion.h) without a GPU: the CPU simulator of its kernels
-(tests/sim/sim_encode_p.cpp) against the independent restatement (tests/enc_p_ref.py), and the oracle as judge of every stream:
+(sim_encode_p of tests/sim/sim_encode_pass.cpp) against the independent restatement (tests/enc_p_ref.py), and the oracle as judge of every stream:
 it decodes each one to the encoder's own reconstruction, bit for bit -- the closed loop."""
 import json
 import os

@@ -1,5 +1,5 @@
 """The encoder's rate control (rule RATE, jsmpeg_amd/csrc/enc_rate.h) without a GPU: the CPU simulator of its kernels
-(tests/sim/sim_encode_rate.cpp) against the brute-force restatement (tests/enc_rate_ref.py) in chosen scale, budget, bytes,
+(sim_encode_rate of tests/sim/sim_encode_pass.cpp) against the brute-force restatement (tests/enc_rate_ref.py) in chosen scale, budget, bytes,
 buffer, ranges and reconstructions; the properties of the rule on every picture; the fixed-scale simulator (sim_encode_p,
 unchanged) given the chosen scales; and the oracle as judge of every stream."""
 import numpy as np

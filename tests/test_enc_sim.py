@@ -1,4 +1,4 @@
-"""The intra encoder (C ABI part 8) without a GPU: enc_block.h's device functions compiled by g++ (tests/sim/sim_encode.cpp)
+"""The intra encoder (C ABI part 8) without a GPU: enc_block.h's device functions compiled by g++ (tests/sim/sim_encode_pass.cpp)
 and driven in the kernels' two-pass order.  Every stream is read by the reference's decoder (its restatement, and its own C
 where present) and by tests/sim's decoder, equals tests/enc_ref.py's independent restatement byte for byte, and its
 quantiser is held against a float64 transform with bounds measured by tools/enc_quality.py (profiles/enc_bounds.json)."""

@@ -1,5 +1,5 @@
 """The intra encoder on the device (C ABI part 8, jsmpeg_amd/encode.py): the GPU's bytes equal the CPU simulator's
-(tests/sim/sim_encode.cpp) and the independent restatement's (tests/enc_ref.py); round trips through Batch and Live on the
+(tests/sim/sim_encode_pass.cpp) and the independent restatement's (tests/enc_ref.py); round trips through Batch and Live on the
 device; tensor input; the pass as a pure enqueue; overflow and refusals.  Bytes and work done are asserted, never times."""
 import ctypes
 import os

@@ -1,5 +1,5 @@
 """The encoder's chains across calls on the device (JSMPEG_HIP_ENC_CHAIN; Encoder.encode(chain=True)): every call's buffer,
-ranges, kinds and reconstructions equal the chain simulator's call (tests/sim/sim_encode_chain.cpp, which tests/test_enc_chain_sim.py
+ranges, kinds and reconstructions equal the chain simulator's call (sim_chain_* of tests/sim/sim_encode_pass.cpp, which tests/test_enc_chain_sim.py
 ties to the one-call simulators and the oracle), and every stream's pieces, concatenated, equal ONE unchained call over the same
 pictures on the same handle.  Bytes are asserted, never times."""
 import ctypes

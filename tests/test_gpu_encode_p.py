@@ -1,5 +1,5 @@
 """The encoder's GOP pass on the device (jsmpeg_hip_encoder_set_gop; jsmpeg_amd/encode.py Encoder.set_gop): the GPU's bytes,
-ranges, kinds and reconstructions equal the CPU simulator's (tests/sim/sim_encode_p.cpp) and the independent restatement's
+ranges, kinds and reconstructions equal the CPU simulator's (sim_encode_p of tests/sim/sim_encode_pass.cpp) and the independent restatement's
 (tests/enc_p_ref.py); the round trip through Batch on the device; tensor input; the pass as a pure enqueue; overflow and
 refusals.  Bytes and work done are asserted, never times."""
 import ctypes

@@ -1,5 +1,5 @@
 """The encoder's rate control on the device (jsmpeg_hip_encoder_set_rate; jsmpeg_amd/encode.py Encoder.set_rate): the GPU's
-bytes, ranges, kinds, reconstructions and chosen scales equal the CPU simulator's (tests/sim/sim_encode_rate.cpp) and, on the
+bytes, ranges, kinds, reconstructions and chosen scales equal the CPU simulator's (sim_encode_rate of tests/sim/sim_encode_pass.cpp) and, on the
 small inputs, the brute-force restatement's (tests/enc_rate_ref.py); one handle across calls with the rule changed in between;
 the round trip through Batch on the device; tensor input; the pass as a pure enqueue; overflow and refusals.  Bytes and work
 done are asserted, never times."""

@@ -1,4 +1,4 @@
-"""Measures the encoder's I + P streams on the CPU build (the simulator of tests/sim/sim_encode_p.cpp, gop 12, search range 7)
+"""Measures the encoder's I + P streams on the CPU build (the simulator of tests/sim/sim_encode_pass.cpp, gop 12, search range 7)
 against the project's intra encoder at the same quantiser scale -- the yardstick: what the library could do before -- and writes
 profiles/enc_p_bounds.json (tests/test_enc_p_sim.py holds a fresh run to it) and the quality section of profiles/enc_p_notes.md.
 Luma PSNR of the oracle's decode against the source, over the display area.  No GPU.

@@ -1,5 +1,5 @@
 """Measures the intra encoder's integer transform against a float64 one on the CPU build (the simulator of
-tests/sim/sim_encode.cpp against tests/enc_ref.py with scipy's dctn), over the inputs of tests/enc_inputs.py, and writes
+tests/sim/sim_encode_pass.cpp against tests/enc_ref.py with scipy's dctn), over the inputs of tests/enc_inputs.py, and writes
 the figures: profiles/enc_bounds.json (tests/test_enc_sim.py reads its bounds from it) and the quality section of
 profiles/enc_notes.md.  No GPU.
 

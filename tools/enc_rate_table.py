@@ -1,5 +1,5 @@
 """What rate control (jsmpeg_amd/csrc/enc_rate.h) does on the test cases, CPU build: per case of tests/enc_rate_inputs.py the
-chosen scales and the total bytes against n * T, from the simulator of the kernels (tests/sim/sim_encode_rate.cpp).  Writes the
+chosen scales and the total bytes against n * T, from the simulator of the kernels (tests/sim/sim_encode_pass.cpp).  Writes the
 `cases` section of profiles/enc_rate_notes.md.  No device.
     python tools/enc_rate_table.py"""
 import os
