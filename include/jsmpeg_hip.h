@@ -922,10 +922,61 @@ int jsmpeg_hip_encoder_picture_rate(jsmpeg_hip_encoder_t *enc, uint32_t k, uint3
 /* Host-side TS mux (plain C, no device; a jsmpeg player takes TS): one PES per unit (a picture's range in `es`) with its PTS,
  * the payload in 184-byte pieces, the unit's last packet padded by adaptation-field stuffing -- what the reference's demuxer
  * (ts.js:127-147, jsmpeg_hip_ts_demux_host) ends a video PES by.  *continuity (in / out, may be NULL: 0) is the PID's counter,
- * carried across calls.  Returns the bytes written, a multiple of 188, or < 0; ts == NULL: the bytes needed. */
+ * carried across calls.  The rule, stated so that no packet depends on the packets before it: jsmpeg_amd/csrc/enc_ts.h -- the
+ * same bytes as the mux on the device below.  Returns the bytes written, a multiple of 188, or < 0; ts == NULL: the bytes needed. */
 int64_t jsmpeg_hip_ts_mux_host(const uint8_t *es, const uint64_t *offset, const uint32_t *bytes, const uint64_t *pts_90k,
                                uint32_t n_units, uint32_t stream_id, uint32_t pid, uint8_t *continuity /* in/out */,
                                uint8_t *ts, uint64_t ts_cap);
+
+/* MPEG-TS ON THE DEVICE (a jsmpeg player takes TS): with jsmpeg_hip_encoder_set_ts the encode calls end in ready-to-send packets
+ * per stream -- one PES per PICTURE, jsmpeg_hip_ts_mux_host's bytes -- muxed behind the write in the SAME ENQUEUE, and read back
+ * in one copy (jsmpeg_hip_encoder_read_ts with UINT32_MAX).  Unit k is picture k's range as jsmpeg_hip_encoder_picture_range
+ * reports it (an I picture with its sequence and GOP header, a P picture from its picture start code); a stream's last picture
+ * of a call with JSMPEG_HIP_ENC_END runs on over the end code, so a stream's TS carries every byte of the stream.  In the TS
+ * buffer the first stream of the call begins at 0, each next one at the end before it rounded up to 16; the bytes between
+ * streams are unspecified.  CONTINUITY: a counter per stream number, kept on the device, where the packet counts are known; a
+ * property of the PID, not of the chain: jsmpeg_hip_encoder_chain_reset and jsmpeg_hip_encoder_set_gop leave the counters
+ * alone, only jsmpeg_hip_encoder_set_ts zeroes them, and a call that overflowed -- in the ES or in the TS -- leaves them where
+ * it found them.  A TS OVERFLOW IS AN OVERFLOW OF THE CALL: jsmpeg_hip_encoder_sync fails with a message that names
+ * max_ts_bytes, nothing of the call is valid, chained streams are reset as after an ES overflow; after an ES overflow there
+ * is no TS.  jsmpeg_hip_encoder_timings' "write" covers the mux.  The ES buffer and all its readers are what they are
+ * without TS; a handle that never calls jsmpeg_hip_encoder_set_ts is byte for byte what it was and allocates nothing new.
+ * OUT OF SCOPE: PAT / PMT / PCR (jsmpeg's demuxer needs none; other players do); audio or a second PID in the same buffer
+ * (packets are self-contained, so a host may interleave); Node bindings of the encoder; kernel stores straight into pinned
+ * host memory.
+ * jsmpeg_hip_encoder_set_ts: max_ts_bytes 0 switches TS off (the default); otherwise the TS buffer, the unit table (56 bytes
+ * per picture of max_pictures) and max_streams counter words are allocated and ALL counters set to 0.  Refused while a pass is
+ * in flight, for pid > 0x1fff, stream_id > 0xff.  jsmpeg_hip_ts_bound gives a safe max_ts_bytes for es_bytes of payload in
+ * `units` units over `streams` streams. */
+int jsmpeg_hip_encoder_set_ts(jsmpeg_hip_encoder_t *enc, uint32_t stream_id, uint32_t pid, uint64_t max_ts_bytes);
+/* the PTS values (90 kHz, the low 33 bits go out) of the NEXT encode call, one per picture; consumed by that call: a count that
+ * differs from the call's is refused BY THAT CALL, nothing is launched, and the call after it is not bound.  Without it picture
+ * k's PTS is floor(ordinal * 90000 * den / num) in 64 bits, masked to 33 bits: ordinal the picture's ordinal in its stream (in a
+ * chained call the chain's), num / den the pictures per second of frame_rate_code (24000/1001, 24, 25, 30000/1001, 30, 50,
+ * 60000/1001, 60).  The host computes the values either way and uploads them on hip_stream: the pass stays a pure enqueue. */
+int jsmpeg_hip_encoder_ts_pts(jsmpeg_hip_encoder_t *enc, const uint64_t *pts_90k, uint32_t count);
+/* THE READERS settle the pass like every other reader and refuse a handle with TS off or one whose last call overflowed.
+ * device buffer of the last call's TS and its total bytes */
+void *jsmpeg_hip_encoder_ts(jsmpeg_hip_encoder_t *enc, uint64_t *total_bytes);
+/* a stream's range in the TS buffer and the stream's counter behind the call (what its next packet will carry) */
+int jsmpeg_hip_encoder_ts_range(jsmpeg_hip_encoder_t *enc, uint32_t stream, uint64_t *begin, uint64_t *end, uint32_t *continuity_next);
+/* picture k's packets: offset in the TS buffer and bytes, a multiple of 188; a viewer that joins starts at an I picture's */
+int jsmpeg_hip_encoder_ts_picture_range(jsmpeg_hip_encoder_t *enc, uint32_t k, uint64_t *offset, uint32_t *bytes);
+/* a stream's TS to the host (at most cap; host NULL: none); stream UINT32_MAX: the whole buffer, every stream, in ONE copy
+ * (jsmpeg_hip_encoder_ts_range tells the streams apart); returns the length or < 0 */
+int64_t jsmpeg_hip_encoder_read_ts(jsmpeg_hip_encoder_t *enc, uint32_t stream, void *host, uint64_t cap);
+uint64_t jsmpeg_hip_ts_bound(uint64_t es_bytes, uint32_t units, uint32_t streams);
+/* The same two kernels over ANY device bytes and a host-given unit list, for stored ES on the device: unit i is bytes[i] bytes at
+ * dev_es + offset[i] of stream number stream[i] (NULL: all 0) -- a stream's units contiguous, streams ascending and below
+ * n_streams.  Synchronous, on the null stream (the producer of dev_es must have finished), with scratch of its own for the
+ * call.  continuity: one in / out counter per stream number [n_streams] (NULL: 0, nothing handed back); stream_begin /
+ * stream_end: host out arrays [n_streams] (0, 0 for a stream without units), laid out as above; dev_ts: 4-byte aligned,
+ * ts_cap bytes writable.  Returns the total bytes, or < 0 (a ts_cap too small: nothing is written, the
+ * counters stay).  No CPU fallback: without a device < 0. */
+int64_t jsmpeg_hip_ts_mux_device(const void *dev_es, const uint64_t *offset, const uint32_t *bytes, const uint32_t *stream,
+                                 const uint64_t *pts_90k, uint32_t n_units, uint32_t stream_id, uint32_t pid,
+                                 uint8_t *continuity /* in/out */, uint32_t n_streams,
+                                 void *dev_ts, uint64_t ts_cap, uint64_t *stream_begin, uint64_t *stream_end);
 
 /* Last error of the calling thread ("" if none). */
 const char *jsmpeg_hip_last_error(void);

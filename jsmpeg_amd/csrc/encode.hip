@@ -3,7 +3,8 @@
  * pictures that a jsmpeg player, the reference decoder and this library's own batch / live front ends read.  The arithmetic is
  * enc_block.h's, enc_motion.h's, enc_rate.h's and enc_chain.h's, what a lane of a kernel does around it is enc_pass.h's -- all
  * shared with the CPU simulator (tests/sim/sim_encode_pass.cpp); here are the kernels (those whose lanes work alone: their LDS,
- * their guards and one call of their body), the pass as a pure enqueue, and the host-side TS mux.
+ * their guards and one call of their body), the pass as a pure enqueue, and the TS mux: on the device behind the pass
+ * (jsmpeg_hip_encoder_set_ts), over any device bytes (jsmpeg_hip_ts_mux_device) and on the host -- one rule, enc_ts.h.
  *
  * A pass on the caller's stream, every size and offset worked out on the device:
  *   k_enc_rgb            tensor input only: RGB -> Y | Cr | Cb of the coded size in the encoder's frame store
@@ -15,6 +16,17 @@
  *   k_enc_clear          zeroes the total (the write ORs into it), 0xff behind it
  *   k_enc_write          a macroblock per lane again: transform, quantise, write bits; the headers by the lanes that begin them
  * The host waits in jsmpeg_hip_encoder_sync and the readers only.
+ *
+ * With TS on (jsmpeg_hip_encoder_set_ts; the rule: enc_ts.h) three more kernels follow the write, in the same enqueue:
+ *   k_ts_units           a picture per lane: the unit table -- unit k is picture k's range, a stream's last picture of a call with
+ *                        JSMPEG_HIP_ENC_END runs on over the end code -- with the PTS values the host uploaded
+ *   k_ts_plan            one workgroup, shaped like k_enc_place: per unit its packets, TS offset and first continuity counter, per
+ *                        stream its range, the total, the overflow flag; the streams' counter words, read and -- unless the call
+ *                        overflowed -- written back
+ *   k_ts_write           a fixed grid over (packets) x 47 dwords: the unit by binary search, the dword by jm_ts_dword, the source
+ *                        bytes from aligned dwords and v_alignbyte; plain stores, one owner per dword
+ * EXTRA DEVICE MEMORY, allocated by jsmpeg_hip_encoder_set_ts: max_ts_bytes, 56 bytes per picture of max_pictures and 28 bytes
+ * per stream of max_streams.
  *
  * With a GOP (jsmpeg_hip_encoder_set_gop, gop > 1; the rules: enc_motion.h) the measure step becomes a loop over LEVELS,
  * level = a picture's ordinal in its stream mod gop: all pictures of a level, of every stream, in one launch each of
@@ -45,6 +57,7 @@
 #include "engine_internal.h"
 #include "enc_pass.h"
 #include "enc_scale.h"
+#include "enc_ts.h"
 
 #define JM_ENC_LANES 64
 #define JM_ENC_MOTION_WAVES 4    /* macroblocks (one wavefront each) of a k_enc_motion workgroup */
@@ -380,6 +393,86 @@ __global__ void __launch_bounds__(JM_ENC_LANES) k_enc_write_p(JmEncArgs a, JmEnc
 	jm_pass_write_p(a, p, g, zz + threadIdx.x, JM_ENC_LANES, pp + threadIdx.x, JM_ENC_LANES);
 }
 
+/* ------------------------------------------------------------------ kernels of the TS mux (enc_ts.h) */
+
+struct JmTsArgs {
+	const uint8_t *src;          /* the bytes the units' offsets count from */
+	const JmTsUnit *units;       /* [n] */
+	JmTsPlaced *placed;          /* [n] */
+	uint32_t n, n_streams, stream_id, pid;
+	uint32_t *cc;                /* [n_streams]: the streams' continuity counters, from call to call */
+	uint64_t *result;            /* total | status (1: above cap, 2: no ES) | packets | 0 | stream_begin[n_streams] | stream_end[n_streams] | cc_next, cc_after (u32 [n_streams] each) */
+	uint64_t cap;
+	uint32_t *out;
+	const uint64_t *es_result;   /* the encoder's total | status, NULL without an encoder */
+};
+JM_HD uint64_t *ts_stream_begin(const JmTsArgs &t) { return t.result + 4; }
+JM_HD uint64_t *ts_stream_end(const JmTsArgs &t) { return t.result + 4 + t.n_streams; }
+JM_HD uint32_t *ts_cc_next(const JmTsArgs &t) { return (uint32_t *)(t.result + 4 + 2 * (size_t)t.n_streams); }
+JM_HD uint32_t *ts_cc_after(const JmTsArgs &t) { return ts_cc_next(t) + t.n_streams; }
+JM_HD size_t ts_result_bytes(uint32_t n_streams) { return 8 * (4 + 3 * (size_t)n_streams); }
+
+__global__ void __launch_bounds__(256) k_ts_units(JmEncArgs a, JmTsUnit *units, const uint64_t *pts) {
+	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+	if (k >= a.count) return;
+	JmTsUnit u;
+	u.off = enc_pic_off(a)[k];
+	u.bytes = enc_pic_bytes(a)[k] + ((a.end && a.pics[k].last) ? 4u : 0u);
+	u.stream = a.pics[k].stream;
+	u.pts = pts[k];
+	units[k] = u;
+}
+
+/* one workgroup: 256 units at a time through LDS, lane 0 walks them */
+__global__ void __launch_bounds__(256) k_ts_plan(JmTsArgs t) {
+	__shared__ uint32_t s_bytes[256], s_stream[256];
+	__shared__ JmTsPlaced s_out[256];
+	__shared__ JmTsPlan plan;
+	__shared__ uint32_t s_status;
+	uint64_t *sb = ts_stream_begin(t), *se = ts_stream_end(t);
+	uint32_t *cn = ts_cc_next(t), *ca = ts_cc_after(t);
+	const bool no_es = t.es_result && t.es_result[1];              /* after an ES overflow there is no TS */
+	for (uint32_t i = threadIdx.x; i < t.n_streams; i += 256) { sb[i] = 0; se[i] = 0; cn[i] = 0; }
+	if (threadIdx.x == 0) plan = jm_ts_plan_begin();
+	__syncthreads();
+	for (uint32_t base = 0; base < t.n && !no_es; base += 256) {
+		const uint32_t k = base + threadIdx.x, n = min(256u, t.n - base);
+		if (k < t.n) { s_bytes[threadIdx.x] = t.units[k].bytes; s_stream[threadIdx.x] = t.units[k].stream; }
+		__syncthreads();
+		if (threadIdx.x == 0) {
+			JmTsPlan p = plan;
+			for (uint32_t i = 0; i < n; i++) s_out[i] = jm_ts_plan_unit(p, s_stream[i], s_bytes[i], t.cc, sb, se, cn);
+			plan = p;
+		}
+		__syncthreads();
+		if (k < t.n) t.placed[k] = s_out[threadIdx.x];
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) {
+		JmTsPlan p = plan;
+		jm_ts_plan_close(p, t.cap, se, cn, t.result);
+		if (no_es) t.result[1] = 2u;
+		t.result[3] = 0;
+		s_status = (uint32_t)t.result[1];
+	}
+	__syncthreads();
+	for (uint32_t i = threadIdx.x; i < t.n_streams; i += 256) {
+		if (s_status == 0) jm_ts_plan_commit(i, sb, se, cn, t.cc);
+		ca[i] = t.cc[i];
+	}
+}
+
+__global__ void __launch_bounds__(256) k_ts_write(JmTsArgs t) {
+	if (t.result[1]) return;
+	const uint64_t dwords = t.result[2] * JM_TS_DWORDS;
+	for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < dwords; g += (uint64_t)gridDim.x * blockDim.x) {
+		uint64_t where;
+		const uint32_t v = jm_ts_output_dword<JmTsFetchAligned>(t.units, t.placed, t.n, g, t.stream_id, t.pid, t.src, &where);
+		t.out[where] = v;
+	}
+}
+#define JM_TS_WRITE_GRID 1024u
+
 /* ------------------------------------------------------------------ the handle */
 
 struct jsmpeg_hip_encoder_t {
@@ -425,10 +518,24 @@ struct jsmpeg_hip_encoder_t {
 	uint8_t *d_carry;                /* two frames per stream number, allocated by the first chained call that runs the level loop */
 	uint64_t *d_spent;               /* [2][max_streams], with d_carry */
 	bool pass_chain;                 /* the last call was chained: an overflow resets its streams */
+	/* TS on the device (jsmpeg_hip_encoder_set_ts; the rule: enc_ts.h); everything allocated by set_ts */
+	uint64_t max_ts_bytes;           /* 0: off */
+	uint32_t ts_stream_id, ts_pid;
+	uint8_t *d_ts;
+	JmTsUnit *d_ts_units;
+	JmTsPlaced *d_ts_placed;         /* behind d_ts_result, in one allocation: one copy brings both back */
+	uint32_t *d_ts_cc;               /* [max_streams]: a property of the PID, not of the chain */
+	uint64_t *d_ts_result, *h_ts_result;   /* h_: pinned */
+	uint64_t *d_ts_pts, *h_ts_pts;   /* [max_pictures]; h_: pinned */
+	std::vector<uint64_t> ts_pts;    /* jsmpeg_hip_encoder_ts_pts: for the next call */
+	bool ts_pts_set;
+	bool pass_ts;                    /* the last call ran with TS on */
+	bool ts_overflowed;              /* ... and its TS did not fit */
 };
 
 static void enc_free_gop(jsmpeg_hip_encoder_t *e);
 static void enc_free_rate(jsmpeg_hip_encoder_t *e);
+static void enc_free_ts(jsmpeg_hip_encoder_t *e);
 static void enc_free(jsmpeg_hip_encoder_t *e) {
 	if (!e) return;
 	hipSetDevice(e->device);
@@ -436,6 +543,7 @@ static void enc_free(jsmpeg_hip_encoder_t *e) {
 	hipFree(e->d_tables); hipFree(e->d_pics); hipFree(e->d_mb); hipFree(e->d_slice); hipFree(e->d_result); hipFree(e->d_es); hipFree(e->d_store);
 	enc_free_gop(e);
 	enc_free_rate(e);
+	enc_free_ts(e);
 	hipFree(e->d_carry); hipFree(e->d_spent);
 	if (e->h_pics) hipHostFree(e->h_pics);
 	if (e->h_result) hipHostFree(e->h_result);
@@ -512,6 +620,14 @@ static int enc_settle(jsmpeg_hip_encoder_t *e) {
 			for (uint32_t k = 0; k < e->count; k++) jm_encc_reset(e->chain[e->h_pics[k].stream]);
 		return fail("encoder: the call's streams need %llu bytes, max_es_bytes is %llu: nothing of the call is valid",
 		            (unsigned long long)e->h_result[0], (unsigned long long)e->cfg.max_es_bytes);
+	}
+	if (e->pass_ts && e->count && e->h_ts_result[1] == 1) {        /* a TS overflow is an overflow of the call; the counters stayed */
+		e->valid = false;
+		e->ts_overflowed = true;
+		if (e->pass_chain)
+			for (uint32_t k = 0; k < e->count; k++) jm_encc_reset(e->chain[e->h_pics[k].stream]);
+		return fail("encoder: the call's TS needs %llu bytes, max_ts_bytes is %llu: nothing of the call is valid",
+		            (unsigned long long)e->h_ts_result[0], (unsigned long long)e->max_ts_bytes);
 	}
 	e->valid = true;
 	return 0;
@@ -612,6 +728,75 @@ extern "C" int jsmpeg_hip_encoder_set_rate(jsmpeg_hip_encoder_t *e, uint32_t byt
 	return 0;
 }
 
+static void enc_free_ts(jsmpeg_hip_encoder_t *e) {
+	hipFree(e->d_ts); hipFree(e->d_ts_units); hipFree(e->d_ts_cc); hipFree(e->d_ts_result); hipFree(e->d_ts_pts);
+	if (e->h_ts_result) hipHostFree(e->h_ts_result);
+	if (e->h_ts_pts) hipHostFree(e->h_ts_pts);
+	e->d_ts = nullptr; e->d_ts_units = nullptr; e->d_ts_placed = nullptr; e->d_ts_cc = nullptr; e->d_ts_result = nullptr; e->d_ts_pts = nullptr;
+	e->h_ts_result = nullptr; e->h_ts_pts = nullptr;
+	e->max_ts_bytes = 0;
+}
+
+static size_t enc_ts_result_bytes(const jsmpeg_hip_encoder_t *e) { return ts_result_bytes(e->cfg.max_streams) + sizeof(JmTsPlaced) * e->cfg.max_pictures; }
+
+/* the TS buffer, the unit table, the counters (all 0); the caller frees what a failure leaves behind (enc_free_ts) */
+static int enc_alloc_ts(jsmpeg_hip_encoder_t *e, uint64_t max_ts_bytes) {
+	const size_t np = e->cfg.max_pictures, ns = e->cfg.max_streams, rb = enc_ts_result_bytes(e);
+	HIP_TRY(hipSetDevice(e->device));
+	HIP_TRY(jm_malloc(&e->d_ts, jm_ts_align16(max_ts_bytes) + 16));
+	HIP_TRY(jm_malloc(&e->d_ts_units, sizeof(JmTsUnit) * np));
+	HIP_TRY(jm_malloc(&e->d_ts_cc, sizeof(uint32_t) * ns));
+	HIP_TRY(jm_malloc(&e->d_ts_result, rb));
+	HIP_TRY(jm_malloc(&e->d_ts_pts, sizeof(uint64_t) * np));
+	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_ts_result), rb, hipHostMallocDefault));
+	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_ts_pts), sizeof(uint64_t) * np, hipHostMallocDefault));
+	memset(e->h_ts_result, 0, rb);
+	e->d_ts_placed = reinterpret_cast<JmTsPlaced *>(reinterpret_cast<uint8_t *>(e->d_ts_result) + ts_result_bytes(e->cfg.max_streams));
+	HIP_TRY(hipMemset(e->d_ts_cc, 0, sizeof(uint32_t) * ns));
+	HIP_TRY(hipStreamSynchronize(nullptr));                    /* the caller's stream may not wait for the null stream */
+	e->max_ts_bytes = max_ts_bytes;
+	return 0;
+}
+
+extern "C" int jsmpeg_hip_encoder_set_ts(jsmpeg_hip_encoder_t *e, uint32_t stream_id, uint32_t pid, uint64_t max_ts_bytes) {
+	g_err[0] = 0;
+	if (!e) return fail("encoder: NULL handle");
+	if (e->pending) return fail("encoder: an encode is in flight: jsmpeg_hip_encoder_sync (or a reader) settles it first");
+	if (pid > 0x1fff || stream_id > 0xff) return fail("encoder: pid %u / stream id %u out of range (0x1fff, 0xff)", pid, stream_id);
+	if (max_ts_bytes > 0xffffffffull * 4) return fail("encoder: max_ts_bytes above 16 GiB");
+	enc_free_ts(e);                                            /* off; the last call's TS is gone either way */
+	e->pass_ts = false; e->ts_overflowed = false; e->ts_pts_set = false;
+	if (max_ts_bytes && enc_alloc_ts(e, max_ts_bytes) != 0) { enc_free_ts(e); return -1; }
+	e->ts_stream_id = stream_id; e->ts_pid = pid;
+	return 0;
+}
+
+extern "C" int jsmpeg_hip_encoder_ts_pts(jsmpeg_hip_encoder_t *e, const uint64_t *pts_90k, uint32_t count) {
+	g_err[0] = 0;
+	if (!e) return fail("encoder: NULL handle");
+	if (e->pending) return fail("encoder: an encode is in flight: jsmpeg_hip_encoder_sync (or a reader) settles it first");
+	if (!e->max_ts_bytes) return fail("encoder: TS is off (jsmpeg_hip_encoder_set_ts)");
+	if (count && !pts_90k) return fail("encoder: NULL pts_90k");
+	e->ts_pts.assign(pts_90k, pts_90k + count);
+	e->ts_pts_set = true;
+	return 0;
+}
+
+/* the mux behind the write, in the same enqueue; `a` is the pass's */
+static int enc_run_ts(jsmpeg_hip_encoder_t *e, const JmEncArgs &a, uint32_t count, bool have_pts, hipStream_t st) {
+	for (uint32_t k = 0; k < count; k++) e->h_ts_pts[k] = have_pts ? e->ts_pts[k] : jm_ts_default_pts(e->plan[k].ordinal, e->cfg.frame_rate_code);
+	HIP_TRY(hipMemcpyAsync(e->d_ts_pts, e->h_ts_pts, sizeof(uint64_t) * count, hipMemcpyHostToDevice, st));
+	JmTsArgs t;
+	t.src = e->d_es; t.units = e->d_ts_units; t.placed = e->d_ts_placed; t.n = count; t.n_streams = e->cfg.max_streams;
+	t.stream_id = e->ts_stream_id; t.pid = e->ts_pid; t.cc = e->d_ts_cc; t.result = e->d_ts_result; t.cap = e->max_ts_bytes;
+	t.out = reinterpret_cast<uint32_t *>(e->d_ts); t.es_result = e->d_result;
+	k_ts_units<<<dim3((count + 255) / 256), dim3(256), 0, st>>>(a, e->d_ts_units, e->d_ts_pts);
+	k_ts_plan<<<dim3(1), dim3(256), 0, st>>>(t);
+	k_ts_write<<<dim3(JM_TS_WRITE_GRID), dim3(256), 0, st>>>(t);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
 /* the stores of the scaled input, and the plan and table of `source` (kept while the geometry stays) */
 static int enc_alloc_scale(jsmpeg_hip_encoder_t *e) {
 	const size_t words = jm_es_table_bound((uint32_t)e->cfg.width, (uint32_t)e->cfg.height), np = e->cfg.max_pictures;
@@ -663,6 +848,9 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 	g_err[0] = 0;
 	if (!e) return fail("encoder: NULL handle");
 	if (e->pending) return fail("encoder: an encode is in flight: jsmpeg_hip_encoder_sync (or a reader) settles it first");
+	const bool have_pts = e->ts_pts_set;                       /* jsmpeg_hip_encoder_ts_pts binds this call only, refused or not */
+	e->ts_pts_set = false;
+	if (have_pts && e->ts_pts.size() != count) return fail("encoder: %u pts values for a call of %u pictures", (unsigned)e->ts_pts.size(), count);
 	if (count > e->cfg.max_pictures) return fail("encoder: %u pictures > max_pictures %u", count, e->cfg.max_pictures);
 	if (flags & ~(JSMPEG_HIP_ENC_END | JSMPEG_HIP_ENC_CHAIN)) return fail("encoder: unknown flags 0x%x", flags);
 	if (count && !frames && !dev_rgb) return fail("encoder: NULL frames");
@@ -699,7 +887,13 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 	e->count = count;
 	e->have_pass = true;
 	e->pass_chain = chained;
-	if (count == 0) { e->valid = true; e->h_result[0] = 0; e->h_result[1] = 0; return 0; }
+	e->pass_ts = e->max_ts_bytes != 0;
+	e->ts_overflowed = false;
+	if (count == 0) {
+		e->valid = true; e->h_result[0] = 0; e->h_result[1] = 0;
+		if (e->pass_ts) e->h_ts_result[0] = e->h_ts_result[1] = e->h_ts_result[2] = 0;
+		return 0;
+	}
 	if (dev_rgb && !e->d_store) HIP_TRY(jm_malloc(&e->d_store, (size_t)e->frame_bytes * e->cfg.max_pictures));
 	jm_encc_plan_call(stream, count, e->chain.data(), rate, e->gop, chained, end, e->plan.data());
 	for (uint32_t k = 0; k < count; k++) {
@@ -756,8 +950,10 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 		k_enc_write<<<dim3(mb_grid), dim3(JM_ENC_LANES), 0, st>>>(a);
 		HIP_TRY(hipGetLastError());
 	}
+	if (e->pass_ts && enc_run_ts(e, a, count, have_pts, st) != 0) return -1;
 	HIP_TRY(hipEventRecord(e->ev[3], st));
 	HIP_TRY(hipMemcpyAsync(e->h_result, e->d_result, enc_result_bytes(e->cfg.max_streams, e->cfg.max_pictures), hipMemcpyDeviceToHost, st));
+	if (e->pass_ts) HIP_TRY(hipMemcpyAsync(e->h_ts_result, e->d_ts_result, ts_result_bytes(e->cfg.max_streams) + sizeof(JmTsPlaced) * count, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipEventRecord(e->ev_done, st));
 	e->pending = true;
 	return 0;
@@ -806,6 +1002,7 @@ static int enc_ready(jsmpeg_hip_encoder_t *e) {
 	if (!e) return fail("encoder: NULL handle");
 	if (enc_settle(e) < 0) return -1;
 	if (!e->have_pass) return fail("encoder: nothing was encoded yet");
+	if (!e->valid && e->ts_overflowed) return fail("encoder: the last call overflowed max_ts_bytes (%llu): nothing of it is valid", (unsigned long long)e->max_ts_bytes);
 	if (!e->valid) return fail("encoder: the last call overflowed max_es_bytes (%llu): nothing of it is valid", (unsigned long long)e->cfg.max_es_bytes);
 	return 0;
 }
@@ -898,56 +1095,136 @@ extern "C" int jsmpeg_hip_encoder_timings(jsmpeg_hip_encoder_t *e, float out_ms[
 	return 0;
 }
 
-/* ------------------------------------------------------------------ TS mux (host, no device)
- * One PES per unit: 00 00 01 stream_id, PES_packet_length (0 when the unit does not fit 16 bits), '10' flags, PTS only, the
- * payload in 184-byte pieces.  The reference's demuxer (ts.js:127-147) ends a PES by its length or -- length 0 -- by a
- * LATER packet of it that carries an adaptation field, so: the unit's last packet is stuffed to its size by an adaptation
- * field, no packet between the first and the last has one, and a unit of unknown length whose last packet would come out full
- * gets one stuffing byte in its FIRST packet (an adaptation field there ends nothing: ts.js:143). */
+/* ------------------------------------------------------------------ the TS readers */
+
+static int enc_ts_ready(jsmpeg_hip_encoder_t *e) {
+	if (enc_ready(e) < 0) return -1;
+	if (!e->pass_ts) return fail(e->max_ts_bytes ? "encoder: TS was switched on after the last call: nothing of it is muxed" : "encoder: TS is off (jsmpeg_hip_encoder_set_ts)");
+	return 0;
+}
+
+extern "C" void *jsmpeg_hip_encoder_ts(jsmpeg_hip_encoder_t *e, uint64_t *total_bytes) {
+	if (enc_ts_ready(e) < 0) return nullptr;
+	if (total_bytes) *total_bytes = e->h_ts_result[0];
+	return e->d_ts;
+}
+
+extern "C" int jsmpeg_hip_encoder_ts_range(jsmpeg_hip_encoder_t *e, uint32_t stream, uint64_t *begin, uint64_t *end, uint32_t *continuity_next) {
+	if (enc_ts_ready(e) < 0) return -1;
+	if (stream >= e->cfg.max_streams) return fail("encoder: stream %u >= max_streams %u", stream, e->cfg.max_streams);
+	const uint32_t ns = e->cfg.max_streams;
+	const bool any = e->count != 0;
+	if (begin) *begin = any ? e->h_ts_result[4 + stream] : 0;
+	if (end) *end = any ? e->h_ts_result[4 + ns + stream] : 0;
+	if (continuity_next) *continuity_next = reinterpret_cast<const uint32_t *>(e->h_ts_result + 4 + 2 * (size_t)ns)[ns + stream];   /* cc_after: kept over a call of no pictures */
+	return 0;
+}
+
+extern "C" int jsmpeg_hip_encoder_ts_picture_range(jsmpeg_hip_encoder_t *e, uint32_t k, uint64_t *offset, uint32_t *bytes) {
+	if (enc_ts_ready(e) < 0) return -1;
+	if (k >= e->count) return fail("encoder: picture %u of %u", k, e->count);
+	const JmTsPlaced &u = reinterpret_cast<const JmTsPlaced *>(reinterpret_cast<const uint8_t *>(e->h_ts_result) + ts_result_bytes(e->cfg.max_streams))[k];
+	if (offset) *offset = u.at;
+	if (bytes) *bytes = u.packets * JM_TS_PACKET;
+	return 0;
+}
+
+extern "C" int64_t jsmpeg_hip_encoder_read_ts(jsmpeg_hip_encoder_t *e, uint32_t stream, void *host, uint64_t cap) {
+	uint64_t b = 0, n = 0;
+	if (stream == UINT32_MAX) {
+		if (enc_ts_ready(e) < 0) return -1;
+		n = e->h_ts_result[0];
+	} else {
+		if (jsmpeg_hip_encoder_ts_range(e, stream, &b, &n, nullptr) < 0) return -1;
+		n -= b;
+	}
+	const uint64_t k = std::min(n, cap);
+	if (k && host) {
+		HIP_TRY(hipSetDevice(e->device));
+		HIP_TRY(hipMemcpy(host, e->d_ts + b, k, hipMemcpyDeviceToHost));
+	}
+	return (int64_t)n;
+}
+
+extern "C" uint64_t jsmpeg_hip_ts_bound(uint64_t es_bytes, uint32_t units, uint32_t streams) { return jm_ts_bound(es_bytes, units, streams); }
+
+/* ------------------------------------------------------------------ TS mux on the host (no device) and over any device bytes
+ * The rule, the PES and the stuffing: enc_ts.h.  The host walks units, packets and dwords in order; nothing depends on it. */
 extern "C" int64_t jsmpeg_hip_ts_mux_host(const uint8_t *es, const uint64_t *offset, const uint32_t *bytes, const uint64_t *pts_90k,
                                           uint32_t n_units, uint32_t stream_id, uint32_t pid, uint8_t *continuity, uint8_t *ts, uint64_t ts_cap) {
 	g_err[0] = 0;
 	if (n_units && (!offset || !bytes || !pts_90k || (ts && !es))) return fail("ts_mux: NULL argument");
 	if (pid > 0x1fff || stream_id > 0xff) return fail("ts_mux: pid %u / stream id %u out of range", pid, stream_id);
-	uint8_t cc = continuity ? (uint8_t)(*continuity & 15u) : 0;
+	uint32_t cc = continuity ? (uint32_t)(*continuity & 15u) : 0u;
 	uint64_t at = 0;
-	for (uint32_t u = 0; u < n_units; u++) {
-		const uint64_t total = 14 + (uint64_t)bytes[u];               /* PES header + payload */
-		const bool sized = (uint64_t)bytes[u] + 8 <= 0xffff;
-		uint64_t lead = (!sized && total % 184 == 0) ? 1 : 0;          /* stuffing bytes (adaptation field) in the first packet */
-		const uint64_t packets = (total + lead + 183) / 184;
-		if (!ts) { at += packets * 188; continue; }
-		if (at + packets * 188 > ts_cap) return fail("ts_mux: %llu bytes do not fit ts_cap %llu", (unsigned long long)(at + packets * 188), (unsigned long long)ts_cap);
-		uint8_t head[14];
-		const uint32_t plen = sized ? bytes[u] + 8 : 0;
-		const uint64_t p = pts_90k[u] & 0x1ffffffffull;
-		head[0] = 0; head[1] = 0; head[2] = 1; head[3] = (uint8_t)stream_id;
-		head[4] = (uint8_t)(plen >> 8); head[5] = (uint8_t)plen;
-		head[6] = 0x80; head[7] = 0x80; head[8] = 5;
-		head[9] = (uint8_t)(0x21 | ((p >> 29) & 0x0e));
-		head[10] = (uint8_t)(p >> 22); head[11] = (uint8_t)(0x01 | ((p >> 14) & 0xfe));
-		head[12] = (uint8_t)(p >> 7); head[13] = (uint8_t)(0x01 | ((p << 1) & 0xfe));
-		uint64_t done = 0;                                             /* bytes of header + payload emitted */
-		for (uint64_t k = 0; k < packets; k++) {
-			uint8_t *pk = ts + at;
-			const uint64_t left = total - done;
-			uint64_t stuff = k == 0 ? lead : 0;                        /* bytes of adaptation field, its length byte included */
-			if (left + stuff < 184) stuff = 184 - left;                /* the last packet: padded to size */
-			const uint64_t n = 184 - stuff;
-			pk[0] = 0x47;
-			pk[1] = (uint8_t)((k == 0 ? 0x40 : 0) | (pid >> 8));
-			pk[2] = (uint8_t)pid;
-			pk[3] = (uint8_t)((stuff ? 0x30 : 0x10) | cc);
-			cc = (cc + 1) & 15u;
-			uint8_t *w = pk + 4;
-			if (stuff) {
-				*w++ = (uint8_t)(stuff - 1);
-				if (stuff > 1) { *w++ = 0; memset(w, 0xff, stuff - 2); w += stuff - 2; }
+	for (uint32_t i = 0; i < n_units; i++) {
+		const uint32_t packets = jm_ts_packets(bytes[i]);
+		if (!ts) { at += (uint64_t)packets * JM_TS_PACKET; continue; }
+		if (at + (uint64_t)packets * JM_TS_PACKET > ts_cap) return fail("ts_mux: %llu bytes do not fit ts_cap %llu", (unsigned long long)(at + (uint64_t)packets * JM_TS_PACKET), (unsigned long long)ts_cap);
+		JmTsUnit u;
+		u.off = offset[i]; u.bytes = bytes[i]; u.stream = 0; u.pts = pts_90k[i];
+		JmTsFetchBytes f;
+		f.base = es + u.off;
+		for (uint32_t k = 0; k < packets; k++, at += JM_TS_PACKET)
+			for (uint32_t w = 0; w < JM_TS_DWORDS; w++) {
+				const uint32_t v = jm_ts_dword(u, cc, stream_id, pid, k, w, f);
+				memcpy(ts + at + 4u * w, &v, 4);
 			}
-			for (uint64_t i = 0; i < n; i++, done++) w[i] = done < 14 ? head[done] : es[offset[u] + done - 14];
-			at += 188;
-		}
+		cc = (cc + packets) & 15u;
 	}
-	if (ts && continuity) *continuity = cc;
+	if (ts && continuity) *continuity = (uint8_t)cc;
 	return (int64_t)at;
+}
+
+/* The two kernels over any device bytes and a host-given unit list; synchronous, on the null stream, with scratch of its own
+ * for the call: for stored ES on the device.  The units of a stream are contiguous, the streams ascend and stay below
+ * n_streams; continuity: one in / out counter per stream number. */
+extern "C" int64_t jsmpeg_hip_ts_mux_device(const void *dev_es, const uint64_t *offset, const uint32_t *bytes, const uint32_t *stream,
+                                            const uint64_t *pts_90k, uint32_t n_units, uint32_t stream_id, uint32_t pid,
+                                            uint8_t *continuity, uint32_t n_streams,
+                                            void *dev_ts, uint64_t ts_cap, uint64_t *stream_begin, uint64_t *stream_end) {
+	g_err[0] = 0;
+	if (jsmpeg_hip_device_count() <= 0) return fail("no HIP device available: jsmpeg_hip_ts_mux_device has no CPU fallback (jsmpeg_hip_ts_mux_host)");
+	if (n_units && (!dev_es || !offset || !bytes || !pts_90k || !dev_ts)) return fail("ts_mux: NULL argument");
+	if (n_streams < 1) return fail("ts_mux: n_streams 0");
+	if (pid > 0x1fff || stream_id > 0xff) return fail("ts_mux: pid %u / stream id %u out of range", pid, stream_id);
+	if ((uintptr_t)dev_ts & 3u) return fail("ts_mux: dev_ts is not 4-byte aligned");
+	if (ts_cap > 0xffffffffull * 4) return fail("ts_mux: ts_cap above 16 GiB");
+	std::vector<JmTsUnit> units(n_units);
+	for (uint32_t i = 0; i < n_units; i++) {
+		JmTsUnit &u = units[i];
+		u.off = offset[i]; u.bytes = bytes[i]; u.stream = stream ? stream[i] : 0u; u.pts = pts_90k[i];
+		if (u.stream >= n_streams) return fail("ts_mux: stream[%u] = %u >= n_streams %u", i, u.stream, n_streams);
+		if (i && u.stream < units[i - 1].stream) return fail("ts_mux: stream[] must ascend (stream[%u] = %u after %u)", i, u.stream, units[i - 1].stream);
+	}
+	std::vector<uint32_t> cc(n_streams, 0u);
+	for (uint32_t s = 0; continuity && s < n_streams; s++) cc[s] = continuity[s] & 15u;
+	const size_t rb = ts_result_bytes(n_streams);
+	std::vector<uint64_t> result(rb / 8, 0);
+	uint8_t *scratch = nullptr;                                /* units | placed | result | cc */
+	const size_t o_placed = sizeof(JmTsUnit) * n_units, o_result = o_placed + sizeof(JmTsPlaced) * n_units, o_cc = o_result + rb;
+	HIP_TRY(jm_malloc(&scratch, o_cc + sizeof(uint32_t) * n_streams));
+	JmTsArgs t;
+	t.src = (const uint8_t *)dev_es; t.units = reinterpret_cast<JmTsUnit *>(scratch); t.placed = reinterpret_cast<JmTsPlaced *>(scratch + o_placed);
+	t.n = n_units; t.n_streams = n_streams; t.stream_id = stream_id; t.pid = pid;
+	t.cc = reinterpret_cast<uint32_t *>(scratch + o_cc); t.result = reinterpret_cast<uint64_t *>(scratch + o_result);
+	t.cap = ts_cap; t.out = reinterpret_cast<uint32_t *>(dev_ts); t.es_result = nullptr;
+	hipError_t r = n_units ? hipMemcpy(scratch, units.data(), o_placed, hipMemcpyHostToDevice) : hipSuccess;
+	if (r == hipSuccess) r = hipMemcpy(t.cc, cc.data(), sizeof(uint32_t) * n_streams, hipMemcpyHostToDevice);
+	if (r == hipSuccess) {
+		k_ts_plan<<<dim3(1), dim3(256), 0, nullptr>>>(t);
+		k_ts_write<<<dim3(JM_TS_WRITE_GRID), dim3(256), 0, nullptr>>>(t);
+		r = hipGetLastError();
+	}
+	if (r == hipSuccess) r = hipMemcpy(result.data(), t.result, rb, hipMemcpyDeviceToHost);      /* waits for both kernels */
+	hipFree(scratch);
+	if (r != hipSuccess) return fail("ts_mux: %s", hipGetErrorString(r));
+	if (result[1]) return fail("ts_mux: %llu bytes do not fit ts_cap %llu", (unsigned long long)result[0], (unsigned long long)ts_cap);
+	const uint32_t *after = reinterpret_cast<const uint32_t *>(result.data() + 4 + 2 * (size_t)n_streams) + n_streams;
+	for (uint32_t s = 0; s < n_streams; s++) {
+		if (continuity) continuity[s] = (uint8_t)after[s];
+		if (stream_begin) stream_begin[s] = result[4 + s];
+		if (stream_end) stream_end[s] = result[4 + n_streams + s];
+	}
+	return (int64_t)result[0];
 }

@@ -1,5 +1,5 @@
 """The MPEG-1 encoder on the device (I pictures, or I + P with a GOP): the Python side of C ABI part 8 (include/jsmpeg_hip.h, jsmpeg_hip_encoder_*) and
-the host-side TS mux.  Frames in HBM (a Batch's pool, a Live tick's pictures, any device pointers) or uint8 RGB torch tensors
+the TS mux: on the device behind the pass (Encoder.set_ts), over any device bytes (ts_mux_device) and on the host (ts_mux).  Frames in HBM (a Batch's pool, a Live tick's pictures, any device pointers) or uint8 RGB torch tensors
 -> elementary streams in a device buffer that Batch.attach_device takes as it is.  I pictures, or -- Encoder.set_gop -- I + P
 with motion search on the device and a closed loop; one quantiser scale per picture, the caller's or -- Encoder.set_rate --
 chosen on the device for a budget in bytes.  Frames of another size than the encoder's are cropped and scaled on the device,
@@ -18,7 +18,9 @@ SYMBOLS = ("jsmpeg_hip_encoder_create", "jsmpeg_hip_encoder_destroy", "jsmpeg_hi
            "jsmpeg_hip_encoder_picture_range", "jsmpeg_hip_encoder_read_es", "jsmpeg_hip_encoder_timings", "jsmpeg_hip_ts_mux_host",
            "jsmpeg_hip_encoder_set_gop", "jsmpeg_hip_encoder_recon", "jsmpeg_hip_encoder_picture_stats",
            "jsmpeg_hip_encoder_set_rate", "jsmpeg_hip_encoder_picture_rate", "jsmpeg_hip_encoder_chain_reset", "jsmpeg_hip_encoder_chain_info",
-           "jsmpeg_hip_encoder_encode_scaled", "jsmpeg_hip_encoder_source")
+           "jsmpeg_hip_encoder_encode_scaled", "jsmpeg_hip_encoder_source",
+           "jsmpeg_hip_encoder_set_ts", "jsmpeg_hip_encoder_ts_pts", "jsmpeg_hip_encoder_ts", "jsmpeg_hip_encoder_ts_range",
+           "jsmpeg_hip_encoder_ts_picture_range", "jsmpeg_hip_encoder_read_ts", "jsmpeg_hip_ts_bound", "jsmpeg_hip_ts_mux_device")
 
 FRAME_RATES = {1: (24000, 1001), 2: (24, 1), 3: (25, 1), 4: (30000, 1001), 5: (30, 1), 6: (50, 1), 7: (60000, 1001), 8: (60, 1)}
 
@@ -92,8 +94,61 @@ def lib():
         L.jsmpeg_hip_encoder_source.argtypes = [vp, u32]
         L.jsmpeg_hip_ts_mux_host.restype = ctypes.c_int64
         L.jsmpeg_hip_ts_mux_host.argtypes = [vp, vp, vp, vp, u32, u32, u32, ctypes.POINTER(ctypes.c_uint8), vp, u64]
+        L.jsmpeg_hip_encoder_set_ts.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_set_ts.argtypes = [vp, u32, u32, u64]
+        L.jsmpeg_hip_encoder_ts_pts.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_ts_pts.argtypes = [vp, vp, u32]
+        L.jsmpeg_hip_encoder_ts.restype = vp
+        L.jsmpeg_hip_encoder_ts.argtypes = [vp, ctypes.POINTER(u64)]
+        L.jsmpeg_hip_encoder_ts_range.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_ts_range.argtypes = [vp, u32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u32)]
+        L.jsmpeg_hip_encoder_ts_picture_range.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_ts_picture_range.argtypes = [vp, u32, ctypes.POINTER(u64), ctypes.POINTER(u32)]
+        L.jsmpeg_hip_encoder_read_ts.restype = ctypes.c_int64
+        L.jsmpeg_hip_encoder_read_ts.argtypes = [vp, u32, vp, u64]
+        L.jsmpeg_hip_ts_bound.restype = u64
+        L.jsmpeg_hip_ts_bound.argtypes = [u64, u32, u32]
+        L.jsmpeg_hip_ts_mux_device.restype = ctypes.c_int64
+        L.jsmpeg_hip_ts_mux_device.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, vp, u32, vp, u64, vp, vp]
         _bound = L
     return _bound
+
+
+def pts_90k(pts):
+    """seconds -> 90 kHz ticks, rounded as ts_mux() rounds"""
+    return np.ascontiguousarray([int(round(float(t) * 90000.0)) for t in pts], dtype=np.uint64)
+
+
+def ts_bound(es_bytes, units, streams=1):
+    """a safe max_ts_bytes / ts_cap for es_bytes of payload in `units` units over `streams` streams"""
+    return int(lib().jsmpeg_hip_ts_bound(int(es_bytes), int(units), int(streams)))
+
+
+def ts_mux_device(dev_es, ranges, pts, dev_ts, ts_cap, streams=None, n_streams=None, stream_id=0xE0, pid=0x100, continuity=None):
+    """The mux on the device over ANY device bytes (jsmpeg_hip_ts_mux_device): dev_es / dev_ts device addresses, ranges =
+    [(offset, bytes)] -- one PES per range -- pts = seconds per range, streams = a stream number per range (ascending; None: all
+    0), continuity = a counter per stream number (None: 0).  Synchronous.  Returns (total bytes, {stream: (begin, end)} of the
+    streams that have units, [the counters to hand to the next call])."""
+    L = lib()
+    n = len(ranges)
+    if len(pts) != n:
+        raise ValueError("ts_mux_device: one pts per range")
+    st = np.zeros(n, np.uint32) if streams is None else np.ascontiguousarray(streams, dtype=np.uint32)
+    if st.shape != (n,):
+        raise ValueError("ts_mux_device: one stream number per range")
+    ns = int(n_streams) if n_streams is not None else (int(st.max()) + 1 if n else 1)
+    off = np.ascontiguousarray([r[0] for r in ranges], dtype=np.uint64)
+    ln = np.ascontiguousarray([r[1] for r in ranges], dtype=np.uint32)
+    p90 = pts_90k(pts)
+    cc = np.zeros(ns, np.uint8)
+    if continuity is not None:
+        cc[:] = np.asarray(continuity, dtype=np.int64) & 15
+    sb, se = np.zeros(ns, np.uint64), np.zeros(ns, np.uint64)
+    total = L.jsmpeg_hip_ts_mux_device(dev_es, off.ctypes.data, ln.ctypes.data, st.ctypes.data, p90.ctypes.data, n, stream_id, pid,
+                                       cc.ctypes.data, ns, dev_ts, int(ts_cap), sb.ctypes.data, se.ctypes.data)
+    if total < 0:
+        raise RuntimeError(_batch.last_error())
+    return int(total), {int(s): (int(sb[s]), int(se[s])) for s in sorted(set(int(v) for v in st))}, [int(c) for c in cc]
 
 
 def ts_mux(es, ranges, pts, stream_id=0xE0, pid=0x100, continuity=0):
@@ -108,7 +163,7 @@ def ts_mux(es, ranges, pts, stream_id=0xE0, pid=0x100, continuity=0):
     ln = np.ascontiguousarray([r[1] for r in ranges], dtype=np.uint32)
     if n and int((off + ln).max()) > es.size:
         raise ValueError("ts_mux: a range ends behind the bytes")
-    p90 = np.ascontiguousarray([int(round(float(t) * 90000.0)) for t in pts], dtype=np.uint64)
+    p90 = pts_90k(pts)
     cc = ctypes.c_uint8(continuity & 15)
     need = L.jsmpeg_hip_ts_mux_host(es.ctypes.data, off.ctypes.data, ln.ctypes.data, p90.ctypes.data, n, stream_id, pid, ctypes.byref(cc), None, 0)
     if need < 0:
@@ -173,20 +228,28 @@ class Encoder:
     def _flags(end, chain):
         return (END if end else 0) | (CHAIN if chain else 0)
 
-    def encode(self, frame_ptrs, streams=None, qscale=8, end=True, stream=None, chain=False):
+    def _pts(self, pts):
+        """pts: seconds per picture of the next call, rounded as ts_mux() rounds (None: the default rule of the frame rate)"""
+        if pts is not None:
+            p = pts_90k(pts)
+            self._ok(self.L.jsmpeg_hip_encoder_ts_pts(self.h, p.ctypes.data, len(p)))
+
+    def encode(self, frame_ptrs, streams=None, qscale=8, end=True, stream=None, chain=False, pts=None):
         """frame_ptrs: device addresses of Y | Cr | Cb planes of the coded size, one per picture; streams: ascending stream
         numbers (None: all stream 0); qscale: 1 .. 31, or one per picture; end: close every stream with a sequence end
         code; stream: the HIP stream to enqueue on -- the one the frames were produced on (ordering is the caller's); chain:
-        continue the streams (end=True then closes them AND ends their chains)."""
+        continue the streams (end=True then closes them AND ends their chains); pts: with set_ts, seconds per picture for the
+        PES headers (None: ordinal / frame rate)."""
         ptrs = [int(p) if p else 0 for p in frame_ptrs]
         n = len(ptrs)
         arr = (ctypes.c_void_p * max(1, n))(*ptrs)
         s, q, qs = self._lists(n, streams, qscale)
+        self._pts(pts)
         self._ok(self.L.jsmpeg_hip_encoder_encode(self.h, arr, None if s is None else s.ctypes.data, None if q is None else q.ctypes.data,
                                                   n, qs, self._flags(end, chain), stream))
         self.count = n
 
-    def encode_scaled(self, frame_ptrs, source_size, crop=None, antialias=True, streams=None, qscale=8, end=True, stream=None, chain=False):
+    def encode_scaled(self, frame_ptrs, source_size, crop=None, antialias=True, streams=None, qscale=8, end=True, stream=None, chain=False, pts=None):
         """encode() from frames of ANOTHER size: frame_ptrs are Y | Cr | Cb planes of the coded size of source_size = (width,
         height), e.g. pool slots of a Batch or Live of that size; crop = (x, y, width, height) in display pixels, x / y even
         (None: the whole picture).  The planes are cropped and scaled on the device into the encoder's own frame store --
@@ -197,18 +260,19 @@ class Encoder:
         arr = (ctypes.c_void_p * max(1, n))(*ptrs)
         s, q, qs = self._lists(n, streams, qscale)
         src = EncSource(int(source_size[0]), int(source_size[1]), *([int(v) for v in crop] if crop is not None else [0, 0, 0, 0]), 1 if antialias else 0)
+        self._pts(pts)
         self._ok(self.L.jsmpeg_hip_encoder_encode_scaled(self.h, arr, ctypes.byref(src), None if s is None else s.ctypes.data,
                                                          None if q is None else q.ctypes.data, n, qs, self._flags(end, chain), stream))
         self.count = n
 
-    def _encode_from(self, ptrs, size, crop, antialias, streams, qscale, end, stream, chain):
+    def _encode_from(self, ptrs, size, crop, antialias, streams, qscale, end, stream, chain, pts=None):
         """planes of `size`: straight in when that is the encoder's size and nothing is cropped, scaled otherwise"""
         if crop is None and tuple(size) == (self.width, self.height):
-            self.encode(ptrs, streams, qscale, end, stream, chain)
+            self.encode(ptrs, streams, qscale, end, stream, chain, pts)
         else:
-            self.encode_scaled(ptrs, size, crop, antialias, streams, qscale, end, stream, chain)
+            self.encode_scaled(ptrs, size, crop, antialias, streams, qscale, end, stream, chain, pts)
 
-    def encode_batch(self, batch, pictures, streams=None, qscale=8, end=True, stream=None, chain=False, crop=None, antialias=True):
+    def encode_batch(self, batch, pictures, streams=None, qscale=8, end=True, stream=None, chain=False, crop=None, antialias=True, pts=None):
         """pictures of a Batch's last decode, straight from its frame pool (the batch is synchronised first; a picture that was
         not decoded is refused).  streams None: each picture's own stream number, which must then ascend.  A batch of another
         size than the encoder's, or a crop, goes through encode_scaled."""
@@ -221,14 +285,15 @@ class Encoder:
             streams = [info.stream for info in infos]
         base = batch.frame_pool_ptr
         self._encode_from([base + int(p) * batch.frame_stride for p in pictures], (batch.width, batch.height), crop, antialias,
-                          streams, qscale, end, stream, chain)
+                          streams, qscale, end, stream, chain, pts)
 
-    def encode_live(self, live, pictures=None, streams=None, qscale=8, end=True, stream=None, chain=False, crop=None, antialias=True):
+    def encode_live(self, live, pictures=None, streams=None, qscale=8, end=True, stream=None, chain=False, crop=None, antialias=True, pts=None):
         """pictures of a Live's last tick (None: all of them, in tick order), from their device_frame pointers.  streams
         None: the pictures are sorted by their live stream id (stable) and numbered 0, 1, .. in that order -- or, with
         chain=True, each picture's live stream id IS its stream number (an id at or above max_streams is refused), so that a
         stream keeps its identity when others join or leave.  A live of another size than the encoder's, or a crop, goes
-        through encode_scaled: a rendition.  Returns the pictures in the order they were encoded in."""
+        through encode_scaled: a rendition.  pts: per picture IN THE ORDER ENCODED (the sorted one).  Returns the pictures in
+        the order they were encoded in."""
         pics = live.pictures()
         if pictures is not None:
             pics = [pics[int(i)] for i in pictures]
@@ -243,10 +308,10 @@ class Encoder:
             else:
                 ids = sorted({p.stream for p in pics})
                 streams = [ids.index(p.stream) for p in pics]
-        self._encode_from([p.device_frame for p in pics], (live.width, live.height), crop, antialias, streams, qscale, end, stream, chain)
+        self._encode_from([p.device_frame for p in pics], (live.width, live.height), crop, antialias, streams, qscale, end, stream, chain, pts)
         return pics
 
-    def encode_tensor(self, x, streams=None, qscale=8, end=True, order="rgb", chain=False):
+    def encode_tensor(self, x, streams=None, qscale=8, end=True, order="rgb", chain=False, pts=None):
         """x: a contiguous torch uint8 CUDA tensor [N, 3, H, W] or [N, H, W, 3] of the display size; runs on torch's current
         stream of the tensor's device"""
         import torch
@@ -263,6 +328,7 @@ class Encoder:
         n = int(x.shape[0])
         s, q, qs = self._lists(n, streams, qscale)
         st = torch.cuda.current_stream(x.device).cuda_stream
+        self._pts(pts)
         self._ok(self.L.jsmpeg_hip_encoder_encode_rgb(self.h, x.data_ptr() if n else None, layout, 1 if str(order).lower() == "bgr" else 0,
                                                       None if s is None else s.ctypes.data, None if q is None else q.ctypes.data,
                                                       n, qs, self._flags(end, chain), st))
@@ -380,6 +446,56 @@ class Encoder:
         ms = (ctypes.c_float * 4)()
         self._ok(self.L.jsmpeg_hip_encoder_timings(self.h, ms))
         return dict(convert_ms=ms[0], measure_ms=ms[1], write_ms=ms[2], total_ms=ms[3])
+
+    def set_ts(self, max_ts_bytes, stream_id=0xE0, pid=0x100):
+        """MPEG-TS on the device: 0 switches it off (the default).  Otherwise every later encode* call also leaves each stream
+        as ready-to-send TS packets, one PES per picture, in a device buffer of max_ts_bytes (ts_bound gives a safe size) --
+        the bytes ts_mux() writes over the call's picture ranges, muxed in the same enqueue.  A continuity counter per stream
+        number lives on the device and goes on from call to call; chain_reset and set_gop leave it alone, set_ts zeroes all."""
+        self._ok(self.L.jsmpeg_hip_encoder_set_ts(self.h, stream_id, pid, int(max_ts_bytes)))
+
+    def device_ts(self):
+        """(device address, total bytes) of the last call's TS buffer: 16-byte aligned stream begins"""
+        total = ctypes.c_uint64()
+        p = self.L.jsmpeg_hip_encoder_ts(self.h, ctypes.byref(total))
+        if not p:
+            raise RuntimeError(_batch.last_error())
+        return p, int(total.value)
+
+    def ts_range(self, stream):
+        """(begin, end) of the stream in the TS buffer and the continuity counter its next packet will carry"""
+        b, e, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
+        self._ok(self.L.jsmpeg_hip_encoder_ts_range(self.h, stream, ctypes.byref(b), ctypes.byref(e), ctypes.byref(c)))
+        return int(b.value), int(e.value), int(c.value)
+
+    def ts_picture_ranges(self):
+        """[(offset in the TS buffer, bytes)] of each picture's packets; a viewer that joins starts at an I picture's"""
+        out = []
+        for k in range(self.count):
+            o, b = ctypes.c_uint64(), ctypes.c_uint32()
+            self._ok(self.L.jsmpeg_hip_encoder_ts_picture_range(self.h, k, ctypes.byref(o), ctypes.byref(b)))
+            out.append((int(o.value), int(b.value)))
+        return out
+
+    def ts(self, stream=0):
+        """the stream's TS packets of the last call, copied to the host"""
+        n = self._ok(self.L.jsmpeg_hip_encoder_read_ts(self.h, stream, None, 0))
+        out = np.empty(max(1, n), dtype=np.uint8)
+        self._ok(self.L.jsmpeg_hip_encoder_read_ts(self.h, stream, out.ctypes.data, n))
+        return out[:n].tobytes()
+
+    def ts_all(self, streams=None):
+        """every stream's TS in ONE copy: (the whole buffer as a uint8 array, {stream: (begin, end)}) -- of `streams`, or of
+        every stream number that has packets"""
+        n = self._ok(self.L.jsmpeg_hip_encoder_read_ts(self.h, 0xffffffff, None, 0))
+        out = np.empty(max(1, n), dtype=np.uint8)
+        self._ok(self.L.jsmpeg_hip_encoder_read_ts(self.h, 0xffffffff, out.ctypes.data, n))
+        ranges = {}
+        for s in (range(self.max_streams) if streams is None else streams):
+            b, e, _ = self.ts_range(s)
+            if e > b or streams is not None:
+                ranges[int(s)] = (b, e)
+        return out[:n], ranges
 
     def ts_mux(self, es, ranges, pts, stream_id=0xE0, pid=0x100):
         """ts_mux() with the continuity counter carried from call to call on this object"""

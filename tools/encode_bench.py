@@ -17,6 +17,10 @@ A seventh step, `scale`: renditions -- 64 streams of 1080p, one picture per stre
 1280x720 by Encoder.encode_scaled (chained, with --gop and --search, q = 8): the scale's "convert" time and the call's total,
 against the route through RGB in the same run (Batch.tensor(size=..., dtype=uint8), then encode_tensor: k_tensor + k_enc_rgb) and
 against a plain device copy of the bytes the scale moves.  Its figures go to the bench section of profiles/enc_scale_notes.md.
+An eighth step, `ts`: what the relay's last step costs -- 64 streams of 1080p, one picture per stream per chained call, with
+--gop and --search at q = 8: host time from the call to every stream's TS bytes on the host, (a) with TS on the device
+(Encoder.set_ts) and ONE read_ts of the whole buffer, (b) with TS off, read_es per stream and jsmpeg_hip_ts_mux_host per stream;
+and timings() with TS on and off, alternating, in one process.  Its figures go to the bench section of profiles/enc_ts_notes.md.
 
 Every GPU step is a child process of this tool under its own `timeout`; the steps are chained and the tool stops at the first
 one that fails.  The figures go into the bench section of profiles/enc_notes.md (nothing is written for a step that did not
@@ -25,7 +29,8 @@ run).
     python tools/encode_bench.py --steps gop --gop 12 --search 7
     python tools/encode_bench.py --steps rate --gop 12 --search 7 --rate 40000
     python tools/encode_bench.py --steps chain --gop 12 --search 7 --rate 40000 --reps 3
-    python tools/encode_bench.py --steps scale --gop 12 --search 7 --reps 3"""
+    python tools/encode_bench.py --steps scale --gop 12 --search 7 --reps 3
+    python tools/encode_bench.py --steps ts --gop 12 --search 7 --reps 3"""
 import argparse
 import json
 import os
@@ -40,7 +45,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 W, H = 1920, 1080
-STEPS = {"pool64": 300, "pool7680": 420, "tensor": 120, "gop": 300, "rate": 420, "chain": 420, "scale": 420}          # seconds each step may take
+STEPS = {"pool64": 300, "pool7680": 420, "tensor": 120, "gop": 300, "rate": 420, "chain": 420, "scale": 420, "ts": 420}          # seconds each step may take
 
 
 def median(v):
@@ -344,6 +349,95 @@ def step_scale(gop, search, reps):
         return dict(step="scale", gop=gop, search=search, streams=64, calls=CHAIN_CALLS, reps=reps, copy_GBps=round(rate, 1), sizes=sizes, kernel=kernel)
 
 
+def step_ts(gop, search, reps):
+    """64 streams x 24 pictures of 1080p from a batch's pool, a picture per stream per chained call, q = 8 (one round to warm
+    up, `reps` measured): from the call to all streams' TS bytes on the host, with the mux on the device and with the host's"""
+    import ctypes
+    import bench
+    from jsmpeg_amd import batch as jb
+    from jsmpeg_amd import encode
+    streams = [g[0] for g in bench.generate_streams(0, 64, CHAIN_CALLS)]
+    total = sum(len(s) for s in streams)
+    n = 64 * CHAIN_CALLS
+    es_cap = 128 << 20
+    ts_cap = encode.ts_bound(es_cap, 64, 64)
+    with jb.Batch(W, H, 64, n + 8, total + 64 * 64 + 4096, device=0) as b:
+        b.upload(streams)
+        assert b.decode() == n
+        by_stream = {}
+        for p, i in enumerate(b.pictures()):
+            if i.decoded:
+                by_stream.setdefault(i.stream, []).append(p)
+        assert sorted(by_stream) == list(range(64)) and all(len(v) == CHAIN_CALLS for v in by_stream.values())
+        calls = [[b.frame_pool_ptr + by_stream[s][t] * b.frame_stride for s in range(64)] for t in range(CHAIN_CALLS)]
+        sn = list(range(64))
+        L = encode.lib()
+        host_ts, host_es = np.empty(ts_cap, np.uint8), np.empty(es_cap, np.uint8)
+        zero64, ln32, p64 = np.zeros(1, np.uint64), np.zeros(1, np.uint32), np.zeros(1, np.uint64)
+        with encode.Encoder(W, H, 64, 64, es_cap, device=0) as on, encode.Encoder(W, H, 64, 64, es_cap, device=0) as off:
+            on.set_ts(ts_cap)
+            for e in (on, off):
+                e.set_gop(gop, search)
+            a_ms, b_ms, b_read_ms, b_mux_ms, es_bytes, ts_bytes = [], [], [], [], [], []
+            t_on, t_off, first = [], [], []
+            cc = [ctypes.c_uint8(0) for _ in sn]
+            for r in range(reps + 1):
+                for e in (on, off):
+                    e.chain_reset()
+                for t, ptrs in enumerate(calls):
+                    # (a) the mux on the device, one copy
+                    t0 = time.perf_counter()
+                    on.encode(ptrs, sn, 8, end=False, chain=True)
+                    got = L.jsmpeg_hip_encoder_read_ts(on.h, 0xffffffff, host_ts.ctypes.data, ts_cap)
+                    ranges = [on.ts_range(s)[:2] for s in sn]
+                    t1 = time.perf_counter()
+                    assert got > 0 and ranges[-1][1] == got
+                    # (b) what the parent offers: sync, a copy per stream, the host mux per stream
+                    t2 = time.perf_counter()
+                    off.encode(ptrs, sn, 8, end=False, chain=True)
+                    off.sync()
+                    at, sizes = 0, []
+                    for s in sn:
+                        k = L.jsmpeg_hip_encoder_read_es(off.h, s, host_es.ctypes.data + at, es_cap - at)
+                        sizes.append(k)
+                        at += k
+                    t3 = time.perf_counter()
+                    at = out = 0
+                    for s in sn:
+                        ln32[0], p64[0] = sizes[s], 3000 * (r * CHAIN_CALLS + t)
+                        out += L.jsmpeg_hip_ts_mux_host(host_es.ctypes.data + at, zero64.ctypes.data, ln32.ctypes.data, p64.ctypes.data, 1, 0xE0, 0x100,
+                                                        ctypes.byref(cc[s]), host_ts.ctypes.data + out, ts_cap - out)
+                        at += sizes[s]
+                    t4 = time.perf_counter()
+                    if r >= 1:
+                        a_ms.append((t1 - t0) * 1e3)
+                        b_ms.append((t4 - t2) * 1e3)
+                        b_read_ms.append((t3 - t2) * 1e3)
+                        b_mux_ms.append((t4 - t3) * 1e3)
+                        es_bytes.append(at)
+                        ts_bytes.append(got)
+                        t_on.append(on.timings())
+                        t_off.append(off.timings())
+                        first.append(t % gop == 0)
+        med = lambda v, k: median([x[k] for x in v])
+        kinds = []
+        for name, flag in (("calls of I pictures", True), ("calls of P pictures", False)):
+            pick = lambda v: [x for x, f in zip(v, first) if f == flag]
+            if pick(a_ms):
+                kinds.append(dict(name=name, calls=len(pick(a_ms)), device_mux_one_copy_ms=median(pick(a_ms)), host_mux_ms=median(pick(b_ms)),
+                                  host_read_es_ms=median(pick(b_read_ms)), host_mux_only_ms=median(pick(b_mux_ms)),
+                                  es_bytes=round(float(np.median(pick(es_bytes)))), ts_bytes=round(float(np.median(pick(ts_bytes)))),
+                                  write_ms_ts_on=median([x["write_ms"] for x in pick(t_on)]), write_ms_ts_off=median([x["write_ms"] for x in pick(t_off)]),
+                                  total_ms_ts_on=median([x["total_ms"] for x in pick(t_on)]), total_ms_ts_off=median([x["total_ms"] for x in pick(t_off)])))
+        return dict(step="ts", gop=gop, search=search, streams=64, calls=CHAIN_CALLS, reps=reps, measured=len(a_ms),
+                    device_mux_one_copy_ms=median(a_ms), device_mux_min_ms=round(min(a_ms), 3), device_mux_max_ms=round(max(a_ms), 3),
+                    host_mux_ms=median(b_ms), host_mux_min_ms=round(min(b_ms), 3), host_mux_max_ms=round(max(b_ms), 3),
+                    host_read_es_ms=median(b_read_ms), host_mux_only_ms=median(b_mux_ms),
+                    es_bytes_per_call=round(float(np.mean(es_bytes))), ts_bytes_per_call=round(float(np.mean(ts_bytes))),
+                    write_ms_ts_on=med(t_on, "write_ms"), write_ms_ts_off=med(t_off, "write_ms"),
+                    total_ms_ts_on=med(t_on, "total_ms"), total_ms_ts_off=med(t_off, "total_ms"), kinds=kinds)
+
+
 def step_tensor():
     import torch
     import enc_inputs as ei
@@ -385,6 +479,27 @@ def notes(results):
                           % (a["to_planes_ms"] / z["copy_bound_ms"], a["to_planes_ms"] / c["to_planes_ms"]), ""]
             lines += ["Medians over %d measured calls each (%d rounds of %d behind one round to warm up).  k_enc_scale: %d VGPRs, %d bytes of LDS, occupancy %d, scratch %d."
                       % (r["sizes"][0]["ways"][0]["calls"], r["reps"], r["calls"], r["kernel"]["VGPRs"], r["kernel"]["LDS Size"], r["kernel"]["Occupancy"], r["kernel"]["ScratchSize"]), ""]
+        elif r["step"] == "ts":
+            lines = ["## TS for a relay tick: %d streams of 1080p, one picture per stream per chained call, %d calls, gop %d, search range %d, q = 8 (measured on an MI355X by tools/encode_bench.py)"
+                     % (r["streams"], r["calls"], r["gop"], r["search"]), "",
+                     "Host clock from the encode call to every stream's TS bytes on the host, median (min .. max) over %d calls (%d rounds of %d behind one round to warm up):"
+                     % (r["measured"], r["reps"], r["calls"]), "",
+                     "| way | ms per call |", "|---|---|",
+                     "| (a) TS on the device, one `read_ts` of the whole buffer, 64 `ts_range` | %.3f (%.3f .. %.3f) |" % (r["device_mux_one_copy_ms"], r["device_mux_min_ms"], r["device_mux_max_ms"]),
+                     "| (b) TS off: `sync`, 64 `read_es`, 64 `jsmpeg_hip_ts_mux_host` | %.3f (%.3f .. %.3f) |" % (r["host_mux_ms"], r["host_mux_min_ms"], r["host_mux_max_ms"]),
+                     "| of (b): the call, `sync` and the 64 copies | %.3f |" % r["host_read_es_ms"],
+                     "| of (b): the 64 host mux calls | %.3f |" % r["host_mux_only_ms"], "",
+                     "A call's streams are %d bytes of ES and %d bytes of TS (%.4f times)." % (r["es_bytes_per_call"], r["ts_bytes_per_call"], r["ts_bytes_per_call"] / max(1, r["es_bytes_per_call"])), "",
+                     "`timings()` of the same calls on two handles in one process, alternating, medians:", "",
+                     "| | write, ms | total, ms |", "|---|---|---|",
+                     "| TS on (write covers k_ts_units, k_ts_plan, k_ts_write) | %.3f | %.3f |" % (r["write_ms_ts_on"], r["total_ms_ts_on"]),
+                     "| TS off | %.3f | %.3f |" % (r["write_ms_ts_off"], r["total_ms_ts_off"]), "",
+                     "The same by the kind of call (the bytes above are a mean over all calls, the times medians), medians:", "",
+                     "| | calls | ES bytes | TS bytes | (a), ms | (b), ms | of (b): call, sync, copies | of (b): host mux | write, TS on / off, ms | total, TS on / off, ms |",
+                     "|---|---|---|---|---|---|---|---|---|---|"]
+            lines += ["| %s | %d | %d | %d | %.3f | %.3f | %.3f | %.3f | %.3f / %.3f | %.3f / %.3f |" % (
+                k["name"], k["calls"], k["es_bytes"], k["ts_bytes"], k["device_mux_one_copy_ms"], k["host_mux_ms"], k["host_read_es_ms"], k["host_mux_only_ms"],
+                k["write_ms_ts_on"], k["write_ms_ts_off"], k["total_ms_ts_on"], k["total_ms_ts_off"]) for k in r["kinds"]] + [""]
         elif r["step"] == "chain":
             lines = ["## %s: %d streams of 1080p, one picture per stream per call, %d calls, gop %d, search range %d, target %d bytes per picture (measured on an MI355X by tools/encode_bench.py)"
                      % ("Chained calls" if r["chained"] else "The same calls WITHOUT chains (every picture an I picture)", r["streams"], r["calls"], r["gop"], r["search"], r["target"]), "",
@@ -447,7 +562,7 @@ def main():
     ap.add_argument("--child")
     a = ap.parse_args()
     if a.child:
-        r = step_scale(a.gop, a.search, a.reps) if a.child == "scale" else step_chain(a.gop, a.search, a.rate, a.reps) if a.child == "chain" else step_rate(a.gop, a.search, a.rate, a.reps) if a.child == "rate" else step_gop(a.gop, a.search, a.reps) if a.child == "gop" else step_tensor() if a.child == "tensor" else step_pool(a.child == "pool7680", a.reps)
+        r = step_ts(a.gop, a.search, a.reps) if a.child == "ts" else step_scale(a.gop, a.search, a.reps) if a.child == "scale" else step_chain(a.gop, a.search, a.rate, a.reps) if a.child == "chain" else step_rate(a.gop, a.search, a.rate, a.reps) if a.child == "rate" else step_gop(a.gop, a.search, a.reps) if a.child == "gop" else step_tensor() if a.child == "tensor" else step_pool(a.child == "pool7680", a.reps)
         print("RESULT " + json.dumps(r), flush=True)
         return 0
     results = []
@@ -471,7 +586,9 @@ def main():
         replace_section(os.path.join(ROOT, "profiles", "enc_chain_notes.md"), "bench" if r["chained"] else "bench_unchained", notes([r]))
     for r in [r for r in results if r["step"] == "scale"]:
         replace_section(os.path.join(ROOT, "profiles", "enc_scale_notes.md"), "bench", notes([r]))
-    results = [r for r in results if r["step"] not in ("gop", "rate", "chain", "scale")]
+    for r in [r for r in results if r["step"] == "ts"]:
+        replace_section(os.path.join(ROOT, "profiles", "enc_ts_notes.md"), "bench", notes([r]))
+    results = [r for r in results if r["step"] not in ("gop", "rate", "chain", "scale", "ts")]
     if results:
         replace_section(NOTES, "bench", notes(results))
     return 0 if done == len(a.steps.split(",")) else 1
