@@ -180,7 +180,8 @@ int jsmpeg_hip_ts_packet_runs(const uint8_t *ts, uint64_t ts_bytes, const uint64
                               uint64_t *leftover_at);
 /* The destination.write calls of stream `stream` of the last upload_ts: pts in
  * seconds, byte range inside that stream's elementary stream.  Returns their
- * number (fills at most `cap` entries; any array may be NULL) or < 0. */
+ * number (fills at most `cap` entries; any array may be NULL) or < 0.  An
+ * upload_ts that was refused leaves no list: < 0 until the next one succeeds. */
 int jsmpeg_hip_batch_ts_writes(jsmpeg_hip_batch_t *b, uint32_t stream, double *pts, uint32_t *offset,
                                uint32_t *length, uint32_t cap);
 /* Device-to-host copy of one stream's resident elementary stream; returns its
@@ -391,7 +392,8 @@ int jsmpeg_hip_mp2_batch_upload_device(jsmpeg_hip_mp2_batch_t *b, const void *de
 int jsmpeg_hip_mp2_batch_upload_ts(jsmpeg_hip_mp2_batch_t *b, uint32_t n_streams, const uint8_t *const *ts,
                                    const uint64_t *ts_bytes, uint32_t stream_id);
 /* The destination.write calls of stream `stream` of the last upload_ts: pts in seconds, byte range inside that
- * stream's MP2 bytes.  Returns their number (fills at most `cap` entries; any array may be NULL) or < 0. */
+ * stream's MP2 bytes.  Returns their number (fills at most `cap` entries; any array may be NULL) or < 0.  An upload_ts
+ * that was refused leaves no list: < 0 until the next one succeeds. */
 int jsmpeg_hip_mp2_batch_ts_writes(jsmpeg_hip_mp2_batch_t *b, uint32_t stream, double *pts, uint32_t *offset,
                                    uint32_t *length, uint32_t cap);
 /* Device-to-host copy of one stream's resident MP2 bytes; returns their number (copies at most `cap`) or < 0. */

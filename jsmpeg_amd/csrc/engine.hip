@@ -18,9 +18,6 @@ int fail(const char *fmt, ...) {
 	return -1;
 }
 extern "C" const char *jsmpeg_hip_last_error(void) { return g_err; }
-/* for the other translation units of the library (mp2_stage.hip): same thread-local message */
-int jm_set_error(const char *msg) { return fail("%s", msg); }
-void jm_clear_error(void) { g_err[0] = 0; }
 extern "C" int jsmpeg_hip_device_count(void) {
 	int n = 0;
 	if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -63,7 +60,7 @@ void batch_free(jsmpeg_hip_batch_t *b) {
 	hipFree(b->d_done); hipFree(b->d_rstatus); hipFree(b->d_plan); hipFree(b->d_plan_u32); hipFree(b->d_sel); hipFree(b->d_before_last);
 	if (b->h_rstatus) hipHostFree(b->h_rstatus);
 	hipFree(b->d_pool_alloc); hipFree(b->d_hashes); hipFree(b->d_dbg); hipFree(b->d_rgba);
-	hipFree(b->d_ts); hipFree(b->d_ts_rec); hipFree(b->d_ts_es_off); hipFree(b->d_ts_cand); hipFree(b->d_ts_writes); hipFree(b->d_ts_begin); hipFree(b->d_ts_len); hipFree(b->d_ts_small);
+	jm_ts_ingest_free(b->ts);
 	if (b->h_counters) hipHostFree(b->h_counters);
 	if (b->h_covered) hipHostFree(b->h_covered);
 	if (b->h_pics) hipHostFree(b->h_pics);
@@ -301,93 +298,15 @@ static int upload_ts_impl(jsmpeg_hip_batch_t *b, uint32_t n_streams, const uint8
 	if (!b || (n_streams && (!ts || !ts_bytes))) return fail("null argument");
 	if (b->enq_pending) return fail("upload_ts: %s", k_in_flight);
 	if (n_streams > b->cfg.max_streams) return fail("%u streams > max_streams %u", n_streams, b->cfg.max_streams);
-	if (stream_id == 0 || stream_id > 255) return fail("stream id %u out of range", stream_id);
 	HIP_TRY(hipSetDevice(b->device));
-	/* the packets of every stream (host pre-pass), then the layout of the TS scratch: the packets of a stream back to
-	 * back from a 16-byte aligned start, 16 readable bytes behind each stream */
-	std::vector<std::vector<JmTsRun>> runs(n_streams);
-	std::vector<uint64_t> begin(n_streams), len(n_streams);
-	std::vector<JmTsWriteEnd> ends;
-	b->ts_pkt_first.assign(n_streams + 1, 0);
-	uint64_t off = 0;
-	uint32_t max_packets = 0;
-	const uint64_t *wb = write_bytes;
-	for (uint32_t i = 0; i < n_streams; i++) {
-		const uint32_t nw = n_writes ? n_writes[i] : 0;
-		/* with a write table, zero writes deliver nothing (bytes beyond the writes are never written); without one the
-		 * whole buffer is one write */
-		const uint64_t pk = n_writes && nw == 0 ? 0 : jm_ts_sync_runs(ts[i], ts_bytes[i], nw ? wb : nullptr, nw, runs[i], nullptr, &ends);
-		if (n_writes) wb += nw;
-		/* the kernels parse framed packets: refuse the input for which that is not what ts.js parses (ts_sync.h) */
-		const int64_t bad = pk ? jm_ts_header_spill_differs(ts[i], runs[i], ends) : -1;
-		if (bad >= 0) return fail("stream %u: TS packet %lld: a payload start reads past the packet's end, and what follows it in the written bytes is not the next packet", i, (long long)bad);
-		begin[i] = off; len[i] = pk * 188;
-		off += (len[i] + 16 + 15) & ~15ull;
-		if (b->ts_pkt_first[i] + pk > 0x3fffffffull) return fail("too many TS packets in one batch");
-		b->ts_pkt_first[i + 1] = b->ts_pkt_first[i] + (uint32_t)pk;
-		max_packets = std::max(max_packets, (uint32_t)pk);
-	}
-	const uint32_t n_packets = b->ts_pkt_first[n_streams];
-	if (off > b->ts_cap) {
-		hipFree(b->d_ts); b->d_ts = nullptr; b->ts_cap = 0;
-		HIP_TRY(jm_malloc(&b->d_ts, off));
-		b->ts_cap = off;
-	}
-	if (n_packets > b->ts_pkt_cap) {
-		hipFree(b->d_ts_rec); hipFree(b->d_ts_es_off); hipFree(b->d_ts_cand); hipFree(b->d_ts_writes);
-		b->d_ts_rec = nullptr; b->d_ts_es_off = nullptr; b->d_ts_cand = nullptr; b->d_ts_writes = nullptr; b->ts_pkt_cap = 0;
-		HIP_TRY(jm_malloc(&b->d_ts_rec, sizeof(JmTsRec) * (size_t)n_packets));
-		HIP_TRY(jm_malloc(&b->d_ts_es_off, sizeof(uint32_t) * (size_t)n_packets));
-		HIP_TRY(jm_malloc(&b->d_ts_cand, sizeof(JmTsCand) * (size_t)n_packets));
-		HIP_TRY(jm_malloc(&b->d_ts_writes, sizeof(JmTsWrite) * 2 * (size_t)n_packets));
-		b->ts_pkt_cap = n_packets;
-	}
-	const uint32_t ms = std::max(1u, b->cfg.max_streams);
-	if (!b->d_ts_begin) {
-		HIP_TRY(jm_malloc(&b->d_ts_begin, sizeof(uint64_t) * ms));
-		HIP_TRY(jm_malloc(&b->d_ts_len, sizeof(uint64_t) * ms));
-		HIP_TRY(jm_malloc(&b->d_ts_small, sizeof(uint32_t) * (6 * (size_t)ms + 1)));
-	}
-	uint32_t *d_pkt_first = b->d_ts_small, *d_n_writes = d_pkt_first + ms + 1, *d_es_total = d_n_writes + ms,
-	         *d_es_given = d_es_total + ms, *d_status = d_es_given + ms, *d_es_begin = d_status + ms;
-	if (n_streams == 0) { b->ts_n_writes.clear(); return batch_layout(b, 0, nullptr); }
-	hipStream_t st = nullptr;
-	for (uint32_t i = 0; i < n_streams; i++) {
-		uint64_t at = begin[i];
-		for (const JmTsRun &r : runs[i]) {                      /* in sync from the first byte: one run, one copy */
-			HIP_TRY(hipMemcpy(b->d_ts + at, ts[i] + r.src, 188ull * r.packets, hipMemcpyHostToDevice));
-			at += 188ull * r.packets;
-		}
-	}
-	HIP_TRY(hipMemcpy(b->d_ts_begin, begin.data(), sizeof(uint64_t) * n_streams, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(b->d_ts_len, len.data(), sizeof(uint64_t) * n_streams, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(d_pkt_first, b->ts_pkt_first.data(), sizeof(uint32_t) * (n_streams + 1), hipMemcpyHostToDevice));
-	HIP_TRY(hipDeviceSynchronize());
-	JmTsBufs tb;
-	tb.ts = b->d_ts; tb.ts_begin = b->d_ts_begin; tb.ts_len = b->d_ts_len; tb.pkt_first = d_pkt_first;
-	tb.n_streams = n_streams; tb.stream_id = stream_id;
-	tb.rec = b->d_ts_rec; tb.es_off = b->d_ts_es_off; tb.cand = b->d_ts_cand; tb.writes = b->d_ts_writes;
-	tb.n_writes = d_n_writes; tb.es_total = d_es_total; tb.es_given = d_es_given; tb.status = d_status;
-	tb.es = b->d_es; tb.es_begin = d_es_begin;
-	HIP_TRY(jm_launch_ts_parse_walk(tb, max_packets, st));
-	std::vector<uint32_t> small(4 * (size_t)ms);
-	HIP_TRY(hipMemcpy(small.data(), d_n_writes, sizeof(uint32_t) * 4 * (size_t)ms, hipMemcpyDeviceToHost));
-	const uint32_t *h_n_writes = small.data(), *h_es_given = small.data() + 2 * ms, *h_status = small.data() + 3 * ms;
-	std::vector<uint64_t> es_len(n_streams);
-	for (uint32_t i = 0; i < n_streams; i++) {
-		if (h_status[i] == 1) return fail("internal: stream %u: a framed TS packet does not start with the sync byte", i);
-		if (h_status[i] == 3) return fail("stream %u: a PES / adaptation-field header runs past the end of its TS packet", i);
-		if (h_status[i]) return fail("stream %u: more than 16 PIDs carry PES headers", i);
-		es_len[i] = h_es_given[i];     /* what the destination received; a PES still open at the end of the input stays pending, like in ts.js */
-	}
+	std::vector<uint64_t> es_len;
+	if (jm_ts_ingest_parse(b->ts, std::max(1u, b->cfg.max_streams), n_streams, ts, ts_bytes, n_writes, write_bytes, stream_id, es_len) != 0) return -1;
 	if (batch_layout(b, n_streams, es_len.data()) != 0) return -1;
-	b->ts_n_writes.assign(h_n_writes, h_n_writes + n_streams);
+	if (n_streams == 0) return 0;                /* an empty upload: no write list, nothing laid out */
 	std::vector<uint32_t> es_begin(n_streams);
 	for (uint32_t i = 0; i < n_streams; i++) es_begin[i] = b->h_streams[i].es_begin;
 	HIP_TRY(hipMemset(b->d_es, 0xff, (size_t)b->es_bytes + JM_ES_PAD));
-	HIP_TRY(hipMemcpy(d_es_begin, es_begin.data(), sizeof(uint32_t) * n_streams, hipMemcpyHostToDevice));
-	HIP_TRY(hipDeviceSynchronize());
-	HIP_TRY(jm_launch_ts_gather(tb, max_packets, st));
+	if (jm_ts_ingest_gather(b->ts, b->d_es, es_begin.data(), n_streams) != 0) return -1;
 	HIP_TRY(hipMemcpy(b->d_streams, b->h_streams.data(), sizeof(JmStream) * n_streams, hipMemcpyHostToDevice));
 	HIP_TRY(hipDeviceSynchronize());
 	return 0;
@@ -399,17 +318,9 @@ static int upload_ts_impl(jsmpeg_hip_batch_t *b, uint32_t n_streams, const uint8
 extern "C" int jsmpeg_hip_batch_ts_writes(jsmpeg_hip_batch_t *b, uint32_t stream, double *pts, uint32_t *offset,
                                           uint32_t *length, uint32_t cap) {
 	g_err[0] = 0;
-	if (!b || stream >= b->ts_n_writes.size()) return fail("no TS upload for stream %u", stream);
+	if (!b) return fail("no TS upload for stream %u", stream);
 	HIP_TRY(hipSetDevice(b->device));
-	const uint32_t n = b->ts_n_writes[stream], k = std::min(n, cap);
-	std::vector<JmTsWrite> w(k);
-	if (k) HIP_TRY(hipMemcpy(w.data(), b->d_ts_writes + 2 * (size_t)b->ts_pkt_first[stream], sizeof(JmTsWrite) * k, hipMemcpyDeviceToHost));
-	for (uint32_t i = 0; i < k; i++) {
-		if (pts) pts[i] = (double)(((uint64_t)w[i].pts_hi << 32) | w[i].pts_lo) / 90000.0;
-		if (offset) offset[i] = w[i].begin;
-		if (length) length[i] = w[i].length;
-	}
-	return (int)n;
+	return jm_ts_ingest_writes(b->ts, stream, pts, offset, length, cap);
 }
 
 /* Copies stream `stream`'s elementary stream (as resident in the batch) to the host; returns its size in bytes

@@ -1,8 +1,8 @@
 /*
  * What the translation units of the host runtime share (engine.hip: the batch engine; live.hip: live streams, C ABI part 5;
- * decoder.hip: the reference's one-picture-per-call decoder ABI): the error message, the allocation helper, the batch
- * object itself -- the live front end and the decoder's decode-ahead both drive a batch from the inside.  Not installed;
- * nothing outside jsmpeg_amd/csrc includes it.
+ * decoder.hip: the reference's one-picture-per-call decoder ABI): the batch object itself -- the live front end and the
+ * decoder's decode-ahead both drive a batch from the inside.  The error message and the allocation helper come from
+ * host_common.h, the batch's TS ingest from ts_ingest.h.  Not installed; nothing outside jsmpeg_amd/csrc includes it.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,33 +16,13 @@
 #include <deque>
 #include <vector>
 
+#include "host_common.h"
 #include "index_tables.h"
 #include "jsmpeg_hip.h"
 #include "kernels.h"
 #include "recon_plan.h"
+#include "ts_ingest.h"
 #include "ts_sync.h"
-
-/* ------------------------------------------------------------------ errors */
-
-/* the calling thread's last message (jsmpeg_hip_last_error); defined in engine.hip */
-extern thread_local char g_err[512];
-int fail(const char *fmt, ...);
-#define HIP_TRY(expr)                                                                        \
-	do {                                                                                     \
-		hipError_t e_ = (expr);                                                              \
-		if (e_ != hipSuccess) return fail("%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-	} while (0)
-
-/* Every device allocation of the engine goes through here.  JSMPEG_HIP_POISON=<byte> fills fresh allocations with
- * that byte (diagnostics: a kernel that reads memory nobody wrote then misbehaves the same way every time instead
- * of depending on what the allocator hands back). */
-template <class T>
-static hipError_t jm_malloc(T **p, size_t bytes) {
-	hipError_t e = hipMalloc(reinterpret_cast<void **>(p), bytes);
-	static const int poison = [] { const char *v = getenv("JSMPEG_HIP_POISON"); return v ? (int)strtol(v, nullptr, 0) & 255 : -1; }();
-	if (e == hipSuccess && poison >= 0 && bytes) { e = hipMemset(*p, poison, bytes); if (e == hipSuccess) e = hipDeviceSynchronize(); }
-	return e;
-}
 
 /* ------------------------------------------------------------ shared state */
 
@@ -123,11 +103,7 @@ struct jsmpeg_hip_batch_t {
 	JmMbRec *d_mb; uint16_t *d_tokens; uint8_t *d_pool_alloc, *d_pool;
 	uint64_t *d_hashes;
 	uint8_t *d_rgba;             /* one RGBA frame: scratch of jsmpeg_hip_batch_read_rgba */
-	/* ingest side (jsmpeg_hip_batch_upload_ts): scratch sized to the largest upload so far */
-	uint8_t *d_ts; uint64_t ts_cap;
-	JmTsRec *d_ts_rec; uint32_t *d_ts_es_off; JmTsCand *d_ts_cand; JmTsWrite *d_ts_writes; uint32_t ts_pkt_cap;
-	uint64_t *d_ts_begin, *d_ts_len; uint32_t *d_ts_small;   /* [max_streams] each; d_ts_small: pkt_first[n+1] | n_writes | es_total | es_given | status | es_begin */
-	std::vector<uint32_t> ts_pkt_first, ts_n_writes;
+	JmTsIngest ts;                /* ingest side (jsmpeg_hip_batch_upload_ts, _ts_writes): the device TS demux and its last write list */
 	uint32_t *d_dbg;
 	uint8_t epoch;
 

@@ -395,15 +395,8 @@ extern "C" int jsmpeg_hip_live_write_ts(jsmpeg_hip_live_t *l, uint32_t stream, c
 	if (!l || stream >= l->streams.size() || !l->streams[stream].open) return fail("write_ts: stream %u is not open", stream);
 	if (stream_id == 0 || stream_id > 255) return fail("stream id %u out of range", stream_id);
 	if (n && !bytes) return fail("write_ts: null buffer");
-	LiveStream &S = l->streams[stream];
-	if (!S.ts) { S.ts = new LiveTs(); S.ts->cur_len = S.ts->total_len = 0; S.ts->pts = 0; S.ts->writes = 0; }
-	int rc = 0;
-	char first_err[sizeof(g_err)] = "";
-	live_ts_feed(*S.ts, (const uint8_t *)bytes, n, stream_id, [&](double pts, const uint8_t *pes, uint32_t m) {
-		if (jsmpeg_hip_live_write(l, stream, pts, pes, m) < 0 && rc == 0) { rc = -1; memcpy(first_err, g_err, sizeof(g_err)); }
-	});
-	if (rc < 0) memcpy(g_err, first_err, sizeof(g_err));
-	return rc;
+	return live_ts_write(l->streams[stream].ts, (const uint8_t *)bytes, n, stream_id,
+	                     [&](double pts, const uint8_t *pes, uint32_t m) { return jsmpeg_hip_live_write(l, stream, pts, pes, m); });
 }
 
 /* The same demuxer by itself (host code, no device): `ts` handed over in write() calls of write_bytes[0 .. n_writes) bytes
@@ -417,7 +410,6 @@ extern "C" int jsmpeg_hip_ts_demux_host(const uint8_t *ts, uint64_t ts_bytes, co
 	if (!ts && ts_bytes) return fail("null buffer");
 	if (stream_id == 0 || stream_id > 255) return fail("stream id %u out of range", stream_id);
 	LiveTs T;
-	T.cur_len = T.total_len = 0; T.pts = 0; T.writes = 0;
 	uint64_t total = 0, at = 0;
 	uint32_t calls = 0;
 	const uint64_t one = ts_bytes;

@@ -26,26 +26,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
-#include <string>
 #include <vector>
 
+#include "host_common.h"
 #include "jsmpeg_hip.h"
 #include "mp2_internal.h"
 #include "ts_feed.h"
-
-int jm_set_error(const char *msg);      /* engine.hip: thread-local message behind jsmpeg_hip_last_error() */
-void jm_clear_error(void);
-
-static int alive_fail(const char *fmt, const char *a = "", long b = 0) {
-	char buf[400];
-	snprintf(buf, sizeof(buf), fmt, a, b);
-	return jm_set_error(buf);
-}
-#define ALIVE_TRY(expr)                                                                                \
-	do {                                                                                               \
-		hipError_t e_ = (expr);                                                                        \
-		if (e_ != hipSuccess) return alive_fail(#expr ": %s (mp2_live.hip:%ld)", hipGetErrorString(e_), __LINE__); \
-	} while (0)
 
 struct Mp2LiveStamp { uint64_t at; double pts; };
 struct Mp2LiveStream {
@@ -95,17 +81,17 @@ static int alive_reserve_in(jsmpeg_hip_mp2_live_t *a, uint64_t bytes) {
 	uint64_t cap = a->in_cap ? a->in_cap : 64 * 1024;
 	while (cap < bytes) cap *= 2;
 	hipHostFree(a->h_in); hipFree(a->d_in); a->h_in = nullptr; a->d_in = nullptr; a->in_cap = 0;
-	ALIVE_TRY(hipHostMalloc(reinterpret_cast<void **>(&a->h_in), cap, hipHostMallocDefault));
-	ALIVE_TRY(hipMalloc(reinterpret_cast<void **>(&a->d_in), cap));
+	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&a->h_in), cap, hipHostMallocDefault));
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&a->d_in), cap));
 	a->in_cap = cap;
 	return 0;
 }
 
 extern "C" jsmpeg_hip_mp2_live_t *jsmpeg_hip_mp2_live_create(const jsmpeg_hip_mp2_live_config_t *config) {
-	jm_clear_error();
+	g_err[0] = 0;
 	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { alive_fail("no HIP device available: the MP2 decode stage has no CPU fallback"); return nullptr; }
-	if (!config || config->max_streams == 0) { alive_fail("bad live audio configuration"); return nullptr; }
+	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { fail("no HIP device available: the MP2 decode stage has no CPU fallback"); return nullptr; }
+	if (!config || config->max_streams == 0) { fail("bad live audio configuration"); return nullptr; }
 	jsmpeg_hip_mp2_live_t *a = new jsmpeg_hip_mp2_live_t();
 	a->cfg = *config;
 	if (!a->cfg.max_frames_per_tick) a->cfg.max_frames_per_tick = 8;
@@ -117,7 +103,7 @@ extern "C" jsmpeg_hip_mp2_live_t *jsmpeg_hip_mp2_live_create(const jsmpeg_hip_mp
 	const uint32_t ms = a->cfg.max_streams;
 	a->cap = a->cfg.max_frames_per_tick;
 	if ((uint64_t)ms * a->cfg.store_bytes > (1ull << 30) || a->cap > 1024 || (uint64_t)ms * a->cap > (1u << 20)) {
-		alive_fail("live audio config too large: max_streams x store_bytes must stay below 1 GiB, max_frames_per_tick <= 1024, max_streams x max_frames_per_tick below 2^20");
+		fail("live audio config too large: max_streams x store_bytes must stay below 1 GiB, max_frames_per_tick <= 1024, max_streams x max_frames_per_tick below 2^20");
 		delete a;
 		return nullptr;
 	}
@@ -143,7 +129,7 @@ extern "C" jsmpeg_hip_mp2_live_t *jsmpeg_hip_mp2_live_create(const jsmpeg_hip_mp
 		for (uint32_t s = 0; s <= ms; s++) cap_first[s] = s * a->cap;
 	}
 	if (!ok || alive_reserve_in(a, 64 * 1024) != 0) {
-		if (!jsmpeg_hip_last_error()[0]) alive_fail("live audio allocation failed: %s", hipGetErrorString(hipGetLastError()));
+		if (!jsmpeg_hip_last_error()[0]) fail("live audio allocation failed: %s", hipGetErrorString(hipGetLastError()));
 		alive_free(a);
 		return nullptr;
 	}
@@ -153,8 +139,8 @@ extern "C" jsmpeg_hip_mp2_live_t *jsmpeg_hip_mp2_live_create(const jsmpeg_hip_mp
 extern "C" void jsmpeg_hip_mp2_live_destroy(jsmpeg_hip_mp2_live_t *a) { alive_free(a); }
 
 extern "C" int jsmpeg_hip_mp2_live_open(jsmpeg_hip_mp2_live_t *a) {
-	jm_clear_error();
-	if (!a) return alive_fail("null live audio handle");
+	g_err[0] = 0;
+	if (!a) return fail("null live audio handle");
 	for (uint32_t s = 0; s < a->streams.size(); s++) {
 		Mp2LiveStream &S = a->streams[s];
 		if (S.open) continue;
@@ -167,12 +153,12 @@ extern "C" int jsmpeg_hip_mp2_live_open(jsmpeg_hip_mp2_live_t *a) {
 		delete S.ts; S.ts = nullptr;
 		return (int)s;
 	}
-	return alive_fail("open: all %s%ld streams are in use", "", (long)a->streams.size());
+	return fail("open: all %zu streams are in use", a->streams.size());
 }
 
 extern "C" int jsmpeg_hip_mp2_live_close(jsmpeg_hip_mp2_live_t *a, uint32_t stream) {
-	jm_clear_error();
-	if (!a || stream >= a->streams.size() || !a->streams[stream].open) return alive_fail("close: stream %s%ld is not open", "", stream);
+	g_err[0] = 0;
+	if (!a || stream >= a->streams.size() || !a->streams[stream].open) return fail("close: stream %u is not open", stream);
 	Mp2LiveStream &S = a->streams[stream];
 	S.open = false; S.store.clear(); S.store.shrink_to_fit(); S.stamps.clear();
 	delete S.ts; S.ts = nullptr;
@@ -184,12 +170,12 @@ extern "C" int jsmpeg_hip_mp2_live_close(jsmpeg_hip_mp2_live_t *a, uint32_t stre
  * when U + n <= capacity; otherwise "emergency evac" -- the undecoded bytes go, the write starts an empty store. */
 extern "C" int jsmpeg_hip_mp2_live_write_v(jsmpeg_hip_mp2_live_t *a, uint32_t stream, double pts, const void *const *buffers,
                                            const uint32_t *lengths, uint32_t n_buffers) {
-	jm_clear_error();
-	if (!a || stream >= a->streams.size() || !a->streams[stream].open) return alive_fail("write: stream %s%ld is not open", "", stream);
+	g_err[0] = 0;
+	if (!a || stream >= a->streams.size() || !a->streams[stream].open) return fail("write: stream %u is not open", stream);
 	uint64_t total = 0;
-	for (uint32_t i = 0; i < n_buffers; i++) { if (lengths[i] && !buffers[i]) return alive_fail("write: null buffer"); total += lengths[i]; }
+	for (uint32_t i = 0; i < n_buffers; i++) { if (lengths[i] && !buffers[i]) return fail("write: null buffer"); total += lengths[i]; }
 	if (total == 0) return 0;
-	if (total > a->cfg.store_bytes) return alive_fail("write of %s%ld bytes is larger than the stream's store (the reference writes past its allocation there)", "", (long)total);
+	if (total > a->cfg.store_bytes) return fail("write of %llu bytes is larger than the stream's store (the reference writes past its allocation there)", (unsigned long long)total);
 	Mp2LiveStream &S = a->streams[stream];
 	if (S.store.size() + total > a->cfg.store_bytes) {
 		S.consumed += S.store.size(); S.store.clear(); S.stamps.clear();
@@ -209,19 +195,12 @@ extern "C" int jsmpeg_hip_mp2_live_write(jsmpeg_hip_mp2_live_t *a, uint32_t stre
 }
 
 extern "C" int jsmpeg_hip_mp2_live_write_ts(jsmpeg_hip_mp2_live_t *a, uint32_t stream, const void *bytes, uint32_t n, uint32_t stream_id) {
-	jm_clear_error();
-	if (!a || stream >= a->streams.size() || !a->streams[stream].open) return alive_fail("write_ts: stream %s%ld is not open", "", stream);
-	if (stream_id == 0 || stream_id > 255) return alive_fail("stream id %s%ld out of range", "", stream_id);
-	if (n && !bytes) return alive_fail("write_ts: null buffer");
-	Mp2LiveStream &S = a->streams[stream];
-	if (!S.ts) { S.ts = new LiveTs(); S.ts->cur_len = S.ts->total_len = 0; S.ts->pts = 0; S.ts->writes = 0; }
-	int rc = 0;
-	std::string first_err;
-	live_ts_feed(*S.ts, (const uint8_t *)bytes, n, stream_id, [&](double pts, const uint8_t *pes, uint32_t m) {
-		if (jsmpeg_hip_mp2_live_write(a, stream, pts, pes, m) < 0 && rc == 0) { rc = -1; first_err = jsmpeg_hip_last_error(); }
-	});
-	if (rc < 0) jm_set_error(first_err.c_str());
-	return rc;
+	g_err[0] = 0;
+	if (!a || stream >= a->streams.size() || !a->streams[stream].open) return fail("write_ts: stream %u is not open", stream);
+	if (stream_id == 0 || stream_id > 255) return fail("stream id %u out of range", stream_id);
+	if (n && !bytes) return fail("write_ts: null buffer");
+	return live_ts_write(a->streams[stream].ts, (const uint8_t *)bytes, n, stream_id,
+	                     [&](double pts, const uint8_t *pes, uint32_t m) { return jsmpeg_hip_mp2_live_write(a, stream, pts, pes, m); });
 }
 
 static inline double now_ms(void) {
@@ -229,9 +208,9 @@ static inline double now_ms(void) {
 }
 
 extern "C" int jsmpeg_hip_mp2_live_tick(jsmpeg_hip_mp2_live_t *a, void *hip_stream) {
-	jm_clear_error();
-	if (!a) return alive_fail("null live audio handle");
-	ALIVE_TRY(hipSetDevice(a->device));
+	g_err[0] = 0;
+	if (!a) return fail("null live audio handle");
+	HIP_TRY(hipSetDevice(a->device));
 	hipStream_t st = hip_stream ? (hipStream_t)hip_stream : a->own_stream;
 	const double t0 = now_ms();
 	const uint32_t ms = a->cfg.max_streams, cap = a->cap;
@@ -257,15 +236,15 @@ extern "C" int jsmpeg_hip_mp2_live_tick(jsmpeg_hip_mp2_live_t *a, void *hip_stre
 			memset(a->h_in + at + n, 0, next - (at + n));
 			at = next;
 			if (S.clear_ring) {                               /* a stream that joined on an id another one used: its ring reads as zeros */
-				ALIVE_TRY(hipMemsetAsync(a->d_w + (size_t)s * a->ring * MP2_VEC_FLOATS, 0, sizeof(float) * MP2_VEC_FLOATS * (size_t)a->ring, st));
+				HIP_TRY(hipMemsetAsync(a->d_w + (size_t)s * a->ring * MP2_VEC_FLOATS, 0, sizeof(float) * MP2_VEC_FLOATS * (size_t)a->ring, st));
 				S.clear_ring = false;
 			}
 		}
 	}
 	memset(a->h_in + at, 0, MP2_PAD);                         /* readable zeros behind the last stream (mp2_wg_walk_fill, mp2_wg_stage_frame) */
-	ALIVE_TRY(hipEventRecord(a->ev[0], st));
-	ALIVE_TRY(hipMemcpyAsync(a->d_in, a->h_in, at + MP2_PAD, hipMemcpyHostToDevice, st));
-	ALIVE_TRY(hipMemcpyAsync(a->d_up, a->h_up, 4 * (4ull * ms + 1), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipEventRecord(a->ev[0], st));
+	HIP_TRY(hipMemcpyAsync(a->d_in, a->h_in, at + MP2_PAD, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(a->d_up, a->h_up, 4 * (4ull * ms + 1), hipMemcpyHostToDevice, st));
 	Mp2Bufs k;
 	memset(&k, 0, sizeof(k));
 	k.in = a->d_in; k.begin = a->d_up; k.end = a->d_up + ms; k.n_streams = n_streams; k.cap_first = a->d_up + 3ull * ms;
@@ -273,15 +252,15 @@ extern "C" int jsmpeg_hip_mp2_live_tick(jsmpeg_hip_mp2_live_t *a, void *hip_stre
 	k.frame_first = nullptr; k.n_frames = n_streams * cap;
 	k.w = a->d_w; k.w_mask = 0; k.n_abs_base = 0; k.n_abs_ptr = a->d_up + 2ull * ms; k.window = a->d_window; k.pcm = a->d_pcm;
 	k.live_cap = cap; k.live_ring = a->ring;
-	ALIVE_TRY(mp2_launch_walk(k, n_streams, st));
-	ALIVE_TRY(hipEventRecord(a->ev[1], st));
-	ALIVE_TRY(mp2_launch_matrix(k, n_streams * cap, st));
-	ALIVE_TRY(hipEventRecord(a->ev[2], st));
-	ALIVE_TRY(mp2_launch_window(k, n_streams * cap, st));
-	ALIVE_TRY(hipMemcpyAsync(a->h_down, a->d_down, 4 * (size_t)ms * (1 + 2ull * cap), hipMemcpyDeviceToHost, st));
-	ALIVE_TRY(hipEventRecord(a->ev[3], st));
+	HIP_TRY(mp2_launch_walk(k, n_streams, st));
+	HIP_TRY(hipEventRecord(a->ev[1], st));
+	HIP_TRY(mp2_launch_matrix(k, n_streams * cap, st));
+	HIP_TRY(hipEventRecord(a->ev[2], st));
+	HIP_TRY(mp2_launch_window(k, n_streams * cap, st));
+	HIP_TRY(hipMemcpyAsync(a->h_down, a->d_down, 4 * (size_t)ms * (1 + 2ull * cap), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipEventRecord(a->ev[3], st));
 	const double t1 = now_ms();
-	ALIVE_TRY(hipStreamSynchronize(st));
+	HIP_TRY(hipStreamSynchronize(st));
 	const double t2 = now_ms();
 	/* book-keeping: what the walk found, stream by stream */
 	const uint32_t *count = a->h_down, *frame_pos = a->h_down + ms, *frame_hdr = a->h_down + ms + (size_t)ms * cap;
@@ -289,14 +268,14 @@ extern "C" int jsmpeg_hip_mp2_live_tick(jsmpeg_hip_mp2_live_t *a, void *hip_stre
 		Mp2LiveStream &S = a->streams[s];
 		if (!S.open || S.store.empty()) continue;
 		const uint32_t c = count[s];
-		if (c > cap) return alive_fail("internal: stream %s%ld: the frame walk counted more frames than the launch has places for", "", s);
+		if (c > cap) return fail("internal: stream %u: the frame walk counted more frames than the launch has places for", s);
 		uint32_t used = 0;
 		for (uint32_t n = 0; n < c; n++) {
 			Mp2Hdr H;
 			mp2_parse_header_word(frame_hdr[(size_t)s * cap + n], H);
 			const uint32_t off = frame_pos[(size_t)s * cap + n] - begin[s];
 			if (!H.valid || off != used || off + (uint32_t)H.frame_bytes > S.store.size())
-				return alive_fail("internal: stream %s%ld: the frame walk's table does not describe the stream's bytes", "", s);
+				return fail("internal: stream %u: the frame walk's table does not describe the stream's bytes", s);
 			const uint64_t at_stream = S.consumed + off;
 			while (S.stamps.size() > 1 && S.stamps[1].at <= at_stream) S.stamps.pop_front();
 			a->frames.push_back(Mp2LiveFrame{ s, (uint32_t)a->frames.size(), (uint32_t)H.frame_bytes, H.sample_rate, S.stamps.empty() ? 0.0 : S.stamps.front().pts, at_stream });
@@ -322,8 +301,8 @@ extern "C" int jsmpeg_hip_mp2_live_tick(jsmpeg_hip_mp2_live_t *a, void *hip_stre
 extern "C" uint32_t jsmpeg_hip_mp2_live_frame_count(jsmpeg_hip_mp2_live_t *a) { return a ? (uint32_t)a->frames.size() : 0; }
 
 extern "C" int jsmpeg_hip_mp2_live_frame(jsmpeg_hip_mp2_live_t *a, uint32_t i, jsmpeg_hip_mp2_live_frame_t *out) {
-	jm_clear_error();
-	if (!a || !out || i >= a->frames.size()) return alive_fail("no such frame in the last tick");
+	g_err[0] = 0;
+	if (!a || !out || i >= a->frames.size()) return fail("no such frame in the last tick");
 	const Mp2LiveFrame &F = a->frames[i];
 	out->stream = F.stream; out->sample_rate = F.sample_rate; out->pts = F.pts; out->stream_offset = F.at; out->bytes = F.bytes; out->reserved = 0;
 	out->device_pcm = a->d_pcm + (size_t)F.place * 2 * MP2_SAMPLES_PER_FRAME;
@@ -331,21 +310,21 @@ extern "C" int jsmpeg_hip_mp2_live_frame(jsmpeg_hip_mp2_live_t *a, uint32_t i, j
 }
 
 extern "C" int jsmpeg_hip_mp2_live_read_pcm(jsmpeg_hip_mp2_live_t *a, uint32_t first, uint32_t count, float *out) {
-	jm_clear_error();
-	if (!a || (count && !out)) return alive_fail("null live audio argument");
-	if ((uint64_t)first + count > a->frames.size()) return alive_fail("read_pcm: frames %s%ld .. are not in the last tick", "", first);
-	ALIVE_TRY(hipSetDevice(a->device));
+	g_err[0] = 0;
+	if (!a || (count && !out)) return fail("null live audio argument");
+	if ((uint64_t)first + count > a->frames.size()) return fail("read_pcm: frames %u .. are not in the last tick", first);
+	HIP_TRY(hipSetDevice(a->device));
 	const size_t frame_floats = 2 * MP2_SAMPLES_PER_FRAME;           /* (the tick's samples lie packed in tick order: one copy) */
 	if (count) {
-		ALIVE_TRY(hipMemcpyAsync(out, a->d_pcm + (size_t)first * frame_floats, sizeof(float) * frame_floats * count, hipMemcpyDeviceToHost, a->own_stream));
-		ALIVE_TRY(hipStreamSynchronize(a->own_stream));
+		HIP_TRY(hipMemcpyAsync(out, a->d_pcm + (size_t)first * frame_floats, sizeof(float) * frame_floats * count, hipMemcpyDeviceToHost, a->own_stream));
+		HIP_TRY(hipStreamSynchronize(a->own_stream));
 	}
 	return 0;
 }
 
 extern "C" int jsmpeg_hip_mp2_live_stream_info(jsmpeg_hip_mp2_live_t *a, uint32_t stream, jsmpeg_hip_mp2_live_stream_info_t *out) {
-	jm_clear_error();
-	if (!a || !out || stream >= a->streams.size() || !a->streams[stream].open) return alive_fail("stream_info: stream %s%ld is not open", "", stream);
+	g_err[0] = 0;
+	if (!a || !out || stream >= a->streams.size() || !a->streams[stream].open) return fail("stream_info: stream %u is not open", stream);
 	const Mp2LiveStream &S = a->streams[stream];
 	out->sample_rate = S.sample_rate; out->pending_bytes = (uint32_t)S.store.size(); out->bytes_written = S.written; out->frames = S.frames;
 	out->evictions = S.evictions; out->reserved = 0;
@@ -359,8 +338,8 @@ extern "C" int jsmpeg_hip_mp2_live_stream_info(jsmpeg_hip_mp2_live_t *a, uint32_
 }
 
 extern "C" int jsmpeg_hip_mp2_live_timings(jsmpeg_hip_mp2_live_t *a, float out_ms[7]) {
-	jm_clear_error();
-	if (!a || !out_ms) return alive_fail("null live audio argument");
+	g_err[0] = 0;
+	if (!a || !out_ms) return fail("null live audio argument");
 	for (int i = 0; i < 7; i++) out_ms[i] = a->ms[i];
 	return 0;
 }

@@ -23,7 +23,6 @@
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -32,19 +31,8 @@
 #include <numeric>
 #include <vector>
 
+#include "host_common.h"
 #include "jsmpeg_hip.h"
-
-/* engine.hip owns the thread's error string */
-int jm_set_error(const char *msg);
-void jm_clear_error(void);
-static int sfail(const char *fmt, ...) {
-	char buf[256];
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(buf, sizeof buf, fmt, ap);
-	va_end(ap);
-	return jm_set_error(buf);
-}
 
 /* ------------------------------------------------------------------ cutting one elementary stream into closed GOPs
  * Host code: the bytes are in host memory when a stream arrives (TS demux output, a file); one linear scan. */
@@ -63,8 +51,8 @@ static inline const uint8_t *next_start_code(const uint8_t *p, const uint8_t *en
 
 extern "C" int jsmpeg_hip_split_gops(const uint8_t *es, uint64_t es_bytes, jsmpeg_hip_gop_unit_t *units, uint32_t cap,
                                      uint64_t *header_offset, uint64_t *header_bytes) {
-	jm_clear_error();
-	if (!es && es_bytes) return sfail("null elementary stream");
+	g_err[0] = 0;
+	if (!es && es_bytes) return fail("null elementary stream");
 	struct Code { uint64_t pos; uint8_t code; };
 	std::vector<Code> codes;
 	const uint8_t *end = es + es_bytes;
@@ -118,8 +106,8 @@ extern "C" int jsmpeg_hip_split_gops(const uint8_t *es, uint64_t es_bytes, jsmpe
 
 /* Greedy balanced assignment (largest first onto the least loaded rank); unit order is preserved inside a rank. */
 extern "C" int jsmpeg_hip_plan_shards(const uint64_t *weights, uint32_t n, uint32_t world, uint32_t *owner) {
-	jm_clear_error();
-	if (world == 0 || (n && (!weights || !owner))) return sfail("bad shard plan arguments");
+	g_err[0] = 0;
+	if (world == 0 || (n && (!weights || !owner))) return fail("bad shard plan arguments");
 	std::vector<uint32_t> order(n);
 	std::iota(order.begin(), order.end(), 0u);
 	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return weights[a] > weights[b]; });
@@ -136,8 +124,8 @@ extern "C" int jsmpeg_hip_plan_shards(const uint64_t *weights, uint32_t n, uint3
  * stream -- what is left of the cuts that cross ranks is <= world - 1 for the whole job (include/jsmpeg_hip.h part 4:
  * a unit continues its predecessor; across ranks that costs two frames when the unit needs them). */
 extern "C" int jsmpeg_hip_plan_contiguous(const uint64_t *weights, uint32_t n, uint32_t world, uint32_t *owner) {
-	jm_clear_error();
-	if (world == 0 || (n && (!weights || !owner))) return sfail("bad shard plan arguments");
+	g_err[0] = 0;
+	if (world == 0 || (n && (!weights || !owner))) return fail("bad shard plan arguments");
 	long double total = 0;
 	for (uint32_t i = 0; i < n; i++) total += (long double)weights[i];
 	long double before = 0;
@@ -155,11 +143,11 @@ extern "C" int jsmpeg_hip_plan_contiguous(const uint64_t *weights, uint32_t n, u
  * that narrows the gap between the two -- the unit whose weight is closest to half the gap, never more than the gap --
  * so the bytes that travel are about half the imbalance and a balanced job moves nothing. */
 extern "C" int jsmpeg_hip_plan_rebalance(const uint64_t *weights, const uint32_t *home, uint32_t n, uint32_t world, uint32_t *owner) {
-	jm_clear_error();
-	if (world == 0 || (n && (!weights || !home || !owner))) return sfail("bad rebalance arguments");
+	g_err[0] = 0;
+	if (world == 0 || (n && (!weights || !home || !owner))) return fail("bad rebalance arguments");
 	std::vector<uint64_t> load(world, 0);
 	for (uint32_t i = 0; i < n; i++) {
-		if (home[i] >= world) return sfail("unit %u: home rank %u outside the job", i, home[i]);
+		if (home[i] >= world) return fail("unit %u: home rank %u outside the job", i, home[i]);
 		owner[i] = home[i];
 		load[home[i]] += weights[i];
 	}
@@ -204,10 +192,10 @@ static int rccl_load(void) {
 		h = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
 		if (h) break;
 	}
-	if (!h) return sfail("cannot load librccl: %s", dlerror());
+	if (!h) return fail("cannot load librccl: %s", dlerror());
 	RcclApi a;
 	a.lib = h;
-#define JM_SYM(field, name) *(void **)(&a.field) = dlsym(h, name); if (!a.field) return sfail("librccl has no %s", name)
+#define JM_SYM(field, name) *(void **)(&a.field) = dlsym(h, name); if (!a.field) return fail("librccl has no %s", name)
 	JM_SYM(GetUniqueId, "ncclGetUniqueId");
 	JM_SYM(CommInitRank, "ncclCommInitRank");
 	JM_SYM(CommDestroy, "ncclCommDestroy");
@@ -225,21 +213,15 @@ static int rccl_load(void) {
 #define RCCL_TRY(call)                                                        \
 	do {                                                                      \
 		ncclResult_t r_ = (call);                                             \
-		if (r_ != ncclSuccess) return sfail("%s: %s", #call, g_rccl.GetErrorString(r_)); \
+		if (r_ != ncclSuccess) return fail("%s: %s", #call, g_rccl.GetErrorString(r_)); \
 	} while (0)
 /* inside a ncclGroupStart / ncclGroupEnd bracket: a failing call must not leave the group open on this thread (every
  * later RCCL call, on any communicator, would queue into a group that never ends) */
 #define RCCL_TRY_IN_GROUP(call)                                               \
 	do {                                                                      \
 		ncclResult_t r_ = (call);                                             \
-		if (r_ != ncclSuccess) { (void)g_rccl.GroupEnd(); return sfail("%s: %s", #call, g_rccl.GetErrorString(r_)); } \
+		if (r_ != ncclSuccess) { (void)g_rccl.GroupEnd(); return fail("%s: %s", #call, g_rccl.GetErrorString(r_)); } \
 	} while (0)
-#define SHIP_TRY(call)                                                        \
-	do {                                                                      \
-		hipError_t e_ = (call);                                               \
-		if (e_ != hipSuccess) return sfail("%s: %s", #call, hipGetErrorString(e_)); \
-	} while (0)
-
 struct jsmpeg_hip_dist_t {
 	int rank, world, device;
 	ncclComm_t comm;
@@ -250,8 +232,8 @@ struct jsmpeg_hip_dist_t {
 static_assert(JSMPEG_HIP_DIST_ID_BYTES == sizeof(ncclUniqueId), "unique id size");
 
 extern "C" int jsmpeg_hip_dist_unique_id(void *id) {
-	jm_clear_error();
-	if (!id) return sfail("null id");
+	g_err[0] = 0;
+	if (!id) return fail("null id");
 	if (rccl_load() != 0) return -1;
 	ncclUniqueId u;
 	RCCL_TRY(g_rccl.GetUniqueId(&u));
@@ -260,20 +242,20 @@ extern "C" int jsmpeg_hip_dist_unique_id(void *id) {
 }
 
 extern "C" jsmpeg_hip_dist_t *jsmpeg_hip_dist_create(int32_t rank, int32_t world, const void *id, int32_t device) {
-	jm_clear_error();
-	if (!id || world < 1 || rank < 0 || rank >= world) { sfail("bad communicator arguments"); return nullptr; }
+	g_err[0] = 0;
+	if (!id || world < 1 || rank < 0 || rank >= world) { fail("bad communicator arguments"); return nullptr; }
 	if (rccl_load() != 0) return nullptr;
-	if (device >= 0 && hipSetDevice(device) != hipSuccess) { sfail("hipSetDevice(%d) failed", device); return nullptr; }
+	if (device >= 0 && hipSetDevice(device) != hipSuccess) { fail("hipSetDevice(%d) failed", device); return nullptr; }
 	jsmpeg_hip_dist_t *d = new jsmpeg_hip_dist_t();
 	d->rank = rank; d->world = world; d->comm = nullptr; d->check_dev = nullptr;
-	if (hipGetDevice(&d->device) != hipSuccess) { sfail("hipGetDevice failed"); delete d; return nullptr; }
+	if (hipGetDevice(&d->device) != hipSuccess) { fail("hipGetDevice failed"); delete d; return nullptr; }
 	if (hipMalloc((void **)&d->check_dev, (2 * (size_t)world + 2 * (size_t)world * world) * sizeof(uint64_t)) != hipSuccess) {
-		(void)hipGetLastError(); sfail("cannot allocate the communicator's check buffer"); delete d; return nullptr;
+		(void)hipGetLastError(); fail("cannot allocate the communicator's check buffer"); delete d; return nullptr;
 	}
 	ncclUniqueId u;
 	memcpy(&u, id, sizeof u);
 	ncclResult_t r = g_rccl.CommInitRank(&d->comm, world, u, rank);
-	if (r != ncclSuccess) { sfail("ncclCommInitRank: %s", g_rccl.GetErrorString(r)); (void)hipFree(d->check_dev); delete d; return nullptr; }
+	if (r != ncclSuccess) { fail("ncclCommInitRank: %s", g_rccl.GetErrorString(r)); (void)hipFree(d->check_dev); delete d; return nullptr; }
 	return d;
 }
 
@@ -292,14 +274,14 @@ extern "C" int32_t jsmpeg_hip_dist_world(jsmpeg_hip_dist_t *d) { return d ? d->w
  * sends leave in ONE group: the source's xGMI links work in parallel.  Enqueued on `hip_stream`. */
 extern "C" int jsmpeg_hip_dist_scatter(jsmpeg_hip_dist_t *d, int32_t src_rank, const void *src_dev, const uint64_t *offset,
                                        const uint64_t *bytes, void *dst_dev, void *hip_stream) {
-	jm_clear_error();
-	if (!d || !offset || !bytes || src_rank < 0 || src_rank >= d->world) return sfail("bad scatter arguments");
-	SHIP_TRY(hipSetDevice(d->device));
+	g_err[0] = 0;
+	if (!d || !offset || !bytes || src_rank < 0 || src_rank >= d->world) return fail("bad scatter arguments");
+	HIP_TRY(hipSetDevice(d->device));
 	hipStream_t st = (hipStream_t)hip_stream;
 	if (d->rank == src_rank) {
-		if (!src_dev) return sfail("the source rank passes the packed buffer");
+		if (!src_dev) return fail("the source rank passes the packed buffer");
 		if (bytes[d->rank] && dst_dev)
-			SHIP_TRY(hipMemcpyAsync(dst_dev, (const uint8_t *)src_dev + offset[d->rank], bytes[d->rank], hipMemcpyDeviceToDevice, st));
+			HIP_TRY(hipMemcpyAsync(dst_dev, (const uint8_t *)src_dev + offset[d->rank], bytes[d->rank], hipMemcpyDeviceToDevice, st));
 		if (d->world > 1) {
 			RCCL_TRY(g_rccl.GroupStart());
 			for (int r = 0; r < d->world; r++)
@@ -308,7 +290,7 @@ extern "C" int jsmpeg_hip_dist_scatter(jsmpeg_hip_dist_t *d, int32_t src_rank, c
 			RCCL_TRY(g_rccl.GroupEnd());
 		}
 	} else if (bytes[d->rank]) {
-		if (!dst_dev) return sfail("null receive buffer");
+		if (!dst_dev) return fail("null receive buffer");
 		RCCL_TRY(g_rccl.Recv(dst_dev, bytes[d->rank], ncclUint8, src_rank, d->comm, st));
 	}
 	return 0;
@@ -318,14 +300,14 @@ extern "C" int jsmpeg_hip_dist_scatter(jsmpeg_hip_dist_t *d, int32_t src_rank, c
  * every rank's `src_dev` (bytes[rank] bytes) lands at dst_dev + offset[rank] on `dst_rank`. */
 extern "C" int jsmpeg_hip_dist_gather(jsmpeg_hip_dist_t *d, int32_t dst_rank, const void *src_dev, const uint64_t *offset,
                                       const uint64_t *bytes, void *dst_dev, void *hip_stream) {
-	jm_clear_error();
-	if (!d || !offset || !bytes || dst_rank < 0 || dst_rank >= d->world) return sfail("bad gather arguments");
-	SHIP_TRY(hipSetDevice(d->device));
+	g_err[0] = 0;
+	if (!d || !offset || !bytes || dst_rank < 0 || dst_rank >= d->world) return fail("bad gather arguments");
+	HIP_TRY(hipSetDevice(d->device));
 	hipStream_t st = (hipStream_t)hip_stream;
 	if (d->rank == dst_rank) {
-		if (!dst_dev) return sfail("the destination rank passes the collecting buffer");
+		if (!dst_dev) return fail("the destination rank passes the collecting buffer");
 		if (bytes[d->rank] && src_dev)
-			SHIP_TRY(hipMemcpyAsync((uint8_t *)dst_dev + offset[d->rank], src_dev, bytes[d->rank], hipMemcpyDeviceToDevice, st));
+			HIP_TRY(hipMemcpyAsync((uint8_t *)dst_dev + offset[d->rank], src_dev, bytes[d->rank], hipMemcpyDeviceToDevice, st));
 		if (d->world > 1) {
 			RCCL_TRY(g_rccl.GroupStart());
 			for (int r = 0; r < d->world; r++)
@@ -334,7 +316,7 @@ extern "C" int jsmpeg_hip_dist_gather(jsmpeg_hip_dist_t *d, int32_t dst_rank, co
 			RCCL_TRY(g_rccl.GroupEnd());
 		}
 	} else if (bytes[d->rank]) {
-		if (!src_dev) return sfail("null send buffer");
+		if (!src_dev) return fail("null send buffer");
 		RCCL_TRY(g_rccl.Send(src_dev, bytes[d->rank], ncclUint8, dst_rank, d->comm, st));
 	}
 	return 0;
@@ -346,16 +328,16 @@ extern "C" int jsmpeg_hip_dist_gather(jsmpeg_hip_dist_t *d, int32_t dst_rank, co
  * device copy.  One group: every link of every rank works at once.  Enqueued on `hip_stream`. */
 extern "C" int jsmpeg_hip_dist_exchange(jsmpeg_hip_dist_t *d, const void *src_dev, const uint64_t *send_offset, const uint64_t *send_bytes,
                                         void *dst_dev, const uint64_t *recv_offset, const uint64_t *recv_bytes, void *hip_stream) {
-	jm_clear_error();
-	if (!d || !send_offset || !send_bytes || !recv_offset || !recv_bytes) return sfail("bad exchange arguments");
-	SHIP_TRY(hipSetDevice(d->device));
+	g_err[0] = 0;
+	if (!d || !send_offset || !send_bytes || !recv_offset || !recv_bytes) return fail("bad exchange arguments");
+	HIP_TRY(hipSetDevice(d->device));
 	hipStream_t st = (hipStream_t)hip_stream;
 	uint64_t out = 0, in = 0;
 	for (int r = 0; r < d->world; r++) { out += send_bytes[r]; in += recv_bytes[r]; }
-	if ((out && !src_dev) || (in && !dst_dev)) return sfail("null exchange buffer");
-	if (send_bytes[d->rank] != recv_bytes[d->rank]) return sfail("the rank's own entry must be the same on both sides");
+	if ((out && !src_dev) || (in && !dst_dev)) return fail("null exchange buffer");
+	if (send_bytes[d->rank] != recv_bytes[d->rank]) return fail("the rank's own entry must be the same on both sides");
 	if (send_bytes[d->rank])
-		SHIP_TRY(hipMemcpyAsync((uint8_t *)dst_dev + recv_offset[d->rank], (const uint8_t *)src_dev + send_offset[d->rank], send_bytes[d->rank],
+		HIP_TRY(hipMemcpyAsync((uint8_t *)dst_dev + recv_offset[d->rank], (const uint8_t *)src_dev + send_offset[d->rank], send_bytes[d->rank],
 		                        hipMemcpyDeviceToDevice, st));
 	if (d->world > 1) {
 		RCCL_TRY(g_rccl.GroupStart());
@@ -372,8 +354,8 @@ extern "C" int jsmpeg_hip_dist_exchange(jsmpeg_hip_dist_t *d, const void *src_de
 /* Plan-time check of an exchange: every rank's two tables to every rank (one all-gather of 2 x world x 8 bytes per
  * rank), then the whole matrix on the host -- so every rank reaches the same verdict and all refuse together. */
 extern "C" int jsmpeg_hip_dist_check_exchange(jsmpeg_hip_dist_t *d, const uint64_t *send_bytes, const uint64_t *recv_bytes, void *hip_stream) {
-	jm_clear_error();
-	if (!d) return sfail("bad exchange check arguments");
+	g_err[0] = 0;
+	if (!d) return fail("bad exchange check arguments");
 	/* EVERY rank enters the collective, whatever happened to it on the way there (round 5 advisor): a rank that returned
 	 * early would leave the others waiting in the all-gather for ever -- the hang this check exists to prevent.  A rank
 	 * that cannot contribute its tables (null tables, the device refused it) contributes a row of ~0 instead, and every
@@ -389,12 +371,12 @@ extern "C" int jsmpeg_hip_dist_check_exchange(jsmpeg_hip_dist_t *d, const uint64
 		(void)hipMemsetAsync(dev, 0xff, row * sizeof(uint64_t), st);           /* the poisoned row without the host's help */
 	}
 	const ncclResult_t gr = g_rccl.AllGather(dev, dev + row, row * sizeof(uint64_t), ncclUint8, d->comm, st);
-	if (gr != ncclSuccess) return sfail("ncclAllGather: %s", g_rccl.GetErrorString(gr));
+	if (gr != ncclSuccess) return fail("ncclAllGather: %s", g_rccl.GetErrorString(gr));
 	if (hipMemcpyAsync(all.data(), dev + row, row * w * sizeof(uint64_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-	    hipStreamSynchronize(st) != hipSuccess) return sfail("exchange check: copy out failed");
+	    hipStreamSynchronize(st) != hipSuccess) return fail("exchange check: copy out failed");
 	for (size_t a = 0; a < w; a++)
 		if (all[a * row] == ~0ull && all[a * row + row - 1] == ~0ull)
-			return sfail("exchange plan refused: rank %zu could not take part in the check%s", a, (int)a == d->rank && !local_ok ? " (this rank: bad tables or the device refused the copy)" : "");
+			return fail("exchange plan refused: rank %zu could not take part in the check%s", a, (int)a == d->rank && !local_ok ? " (this rank: bad tables or the device refused the copy)" : "");
 	char msg[220];
 	size_t used = 0, bad = 0;
 	msg[0] = 0;
@@ -405,7 +387,7 @@ extern "C" int jsmpeg_hip_dist_check_exchange(jsmpeg_hip_dist_t *d, const uint64
 			if (bad++ < 2) used += (size_t)snprintf(msg + used, sizeof msg - used, "%srank %zu sends %llu bytes to rank %zu, which expects %llu",
 			                                         bad > 1 ? "; " : "", a, (unsigned long long)sent, r, (unsigned long long)expected);
 		}
-	if (bad) return sfail("exchange plan refused (%zu pair%s): %s", bad, bad == 1 ? "" : "s", msg);
+	if (bad) return fail("exchange plan refused (%zu pair%s): %s", bad, bad == 1 ? "" : "s", msg);
 	return 0;
 }
 
@@ -413,9 +395,9 @@ extern "C" int jsmpeg_hip_dist_check_exchange(jsmpeg_hip_dist_t *d, const uint64
  * dst_dev[r * bytes_per_rank ...] = rank r's src_dev. */
 extern "C" int jsmpeg_hip_dist_allgather(jsmpeg_hip_dist_t *d, const void *src_dev, void *dst_dev, uint64_t bytes_per_rank,
                                          void *hip_stream) {
-	jm_clear_error();
-	if (!d || !src_dev || !dst_dev) return sfail("bad all-gather arguments");
-	SHIP_TRY(hipSetDevice(d->device));
+	g_err[0] = 0;
+	if (!d || !src_dev || !dst_dev) return fail("bad all-gather arguments");
+	HIP_TRY(hipSetDevice(d->device));
 	RCCL_TRY(g_rccl.AllGather(src_dev, dst_dev, bytes_per_rank, ncclUint8, d->comm, (hipStream_t)hip_stream));
 	return 0;
 }
@@ -424,42 +406,42 @@ extern "C" int jsmpeg_hip_dist_allgather(jsmpeg_hip_dist_t *d, const void *src_d
  * The exchange steps above move bytes between DEVICE buffers.  A Python host has torch tensors for those; the Node host
  * (jsmpeg_amd/js/shard-hip.js over napi_shard.c) has these: plain allocations and copies, nothing of the decode path. */
 extern "C" void *jsmpeg_hip_device_alloc(uint64_t bytes, int32_t device, int32_t fill) {
-	jm_clear_error();
-	if (device >= 0 && hipSetDevice(device) != hipSuccess) { sfail("hipSetDevice(%d) failed", device); return nullptr; }
+	g_err[0] = 0;
+	if (device >= 0 && hipSetDevice(device) != hipSuccess) { fail("hipSetDevice(%d) failed", device); return nullptr; }
 	void *p = nullptr;
-	if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); sfail("cannot allocate %llu bytes of device memory", (unsigned long long)bytes); return nullptr; }
+	if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); fail("cannot allocate %llu bytes of device memory", (unsigned long long)bytes); return nullptr; }
 	if (fill >= 0 && bytes && (hipMemset(p, fill & 255, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) {
-		(void)hipFree(p); sfail("cannot fill the new device buffer"); return nullptr;
+		(void)hipFree(p); fail("cannot fill the new device buffer"); return nullptr;
 	}
 	return p;
 }
 extern "C" void jsmpeg_hip_device_free(void *p) { if (p) (void)hipFree(p); }
 extern "C" int jsmpeg_hip_device_write(void *dst, const void *host, uint64_t n) {
-	jm_clear_error();
-	if (n && (!dst || !host)) return sfail("null buffer");
-	if (n) SHIP_TRY(hipMemcpy(dst, host, n, hipMemcpyHostToDevice));
+	g_err[0] = 0;
+	if (n && (!dst || !host)) return fail("null buffer");
+	if (n) HIP_TRY(hipMemcpy(dst, host, n, hipMemcpyHostToDevice));
 	return 0;
 }
 extern "C" int jsmpeg_hip_device_read(void *host, const void *src, uint64_t n) {
-	jm_clear_error();
-	if (n && (!src || !host)) return sfail("null buffer");
-	if (n) SHIP_TRY(hipMemcpy(host, src, n, hipMemcpyDeviceToHost));
+	g_err[0] = 0;
+	if (n && (!src || !host)) return fail("null buffer");
+	if (n) HIP_TRY(hipMemcpy(host, src, n, hipMemcpyDeviceToHost));
 	return 0;
 }
 extern "C" int jsmpeg_hip_device_copy(void *dst, const void *src, uint64_t n) {
-	jm_clear_error();
-	if (n && (!dst || !src)) return sfail("null buffer");
-	if (n) SHIP_TRY(hipMemcpy(dst, src, n, hipMemcpyDeviceToDevice));
+	g_err[0] = 0;
+	if (n && (!dst || !src)) return fail("null buffer");
+	if (n) HIP_TRY(hipMemcpy(dst, src, n, hipMemcpyDeviceToDevice));
 	return 0;
 }
 extern "C" int jsmpeg_hip_device_fill(void *dst, int32_t byte, uint64_t n) {
-	jm_clear_error();
-	if (n && !dst) return sfail("null buffer");
-	if (n) { SHIP_TRY(hipMemset(dst, byte & 255, n)); SHIP_TRY(hipDeviceSynchronize()); }
+	g_err[0] = 0;
+	if (n && !dst) return fail("null buffer");
+	if (n) { HIP_TRY(hipMemset(dst, byte & 255, n)); HIP_TRY(hipDeviceSynchronize()); }
 	return 0;
 }
 extern "C" int jsmpeg_hip_device_synchronize(void) {
-	jm_clear_error();
-	SHIP_TRY(hipDeviceSynchronize());
+	g_err[0] = 0;
+	HIP_TRY(hipDeviceSynchronize());
 	return 0;
 }

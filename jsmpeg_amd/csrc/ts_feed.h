@@ -1,25 +1,28 @@
 /*
  * The reference's MPEG-TS demuxer (src/ts.js:25-210) as HOST code in front of a live stream's write(): its state between
- * write() calls and the feed that turns TS bytes into destination.write(pts, payload) calls.  Shared by the live video streams
- * (live.hip: jsmpeg_hip_live_write_ts, jsmpeg_hip_ts_demux_host) and the live audio streams (mp2_live.hip:
- * jsmpeg_hip_mp2_live_write_ts).  Not installed; nothing outside jsmpeg_amd/csrc includes it.
+ * write() calls, the feed that turns TS bytes into destination.write(pts, payload) calls (live_ts_feed), and the body of a live
+ * stream's write_ts around it (live_ts_write).  Shared by the live video streams (live.hip: jsmpeg_hip_live_write_ts,
+ * jsmpeg_hip_ts_demux_host) and the live audio streams (mp2_live.hip: jsmpeg_hip_mp2_live_write_ts).  Not installed; nothing
+ * outside jsmpeg_amd/csrc includes it.
  */
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <utility>
 #include <vector>
 
+#include "host_common.h"
 #include "ts_sync.h"
 
 /* a live stream fed as MPEG-TS (jsmpeg_hip_live_write_ts): the reference demuxer's state between write() calls (ts.js:3-41) */
 struct LiveTs {
 	std::vector<uint8_t> left;                         /* leftoverBytes */
 	std::vector<std::pair<uint16_t, uint8_t>> pids;    /* pidsToStreamIds */
-	int64_t cur_len, total_len;                        /* pesPacketInfo[stream id]: currentLength, totalLength, pts, buffers */
-	double pts;
+	int64_t cur_len = 0, total_len = 0;                /* pesPacketInfo[stream id]: currentLength, totalLength, pts, buffers */
+	double pts = 0;
 	std::vector<uint8_t> pes;
 	std::vector<uint8_t> joined;                       /* scratch: leftover + the new bytes */
-	uint64_t writes;                                   /* destination.write calls made so far */
+	uint64_t writes = 0;                               /* destination.write calls made so far */
 };
 
 /* The stream as MPEG-TS: the reference's demuxer in front of write() (src/ts.js:25-147), with its state between calls --
@@ -88,3 +91,17 @@ static void live_ts_feed(LiveTs &T, const uint8_t *buf, uint64_t len, uint32_t s
 	T.left.assign(buf + rest, buf + len);
 }
 
+/* A live stream's write_ts behind its argument checks: the stream's demuxer state (made here on first use) is fed the bytes, and
+ * every PES goes to `write(pts, bytes, n)`, the stream's own write (< 0: failed, its message in g_err).  All of them are written;
+ * returns 0, or -1 with the FIRST failure's message. */
+template <class W>
+static int live_ts_write(LiveTs *&ts, const uint8_t *bytes, uint32_t n, uint32_t stream_id, W &&write) {
+	if (!ts) ts = new LiveTs();
+	int rc = 0;
+	char first_err[sizeof(g_err)] = "";
+	live_ts_feed(*ts, bytes, n, stream_id, [&](double pts, const uint8_t *pes, uint32_t m) {
+		if (write(pts, pes, m) < 0 && rc == 0) { rc = -1; memcpy(first_err, g_err, sizeof(g_err)); }
+	});
+	if (rc < 0) memcpy(g_err, first_err, sizeof(g_err));
+	return rc;
+}

@@ -15,30 +15,24 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("path", EXCLUDED, ids=EXCLUDED_IDS)
 def test_device_demux_refuses_what_it_cannot_match(path, hip_lib, libs):
-    """upload_ts raises with the stated message -- nothing is silently different from ts.js -- and the handle goes on
-    working: the next upload_ts gives the restatement's result."""
+    """upload_ts raises with the stated message -- nothing is silently different from ts.js --, the write list of the
+    upload before it is gone (its rows lie at another upload's offsets), and the handle goes on working: the next
+    upload_ts gives the restatement's result."""
     from jsmpeg_amd import batch as jb
     fx, ts = load_case(path)
     ws = fx.get("write_sizes")
     good = ts_craft.CASES["negative_total"]()
     want_es, want_w = checkers.oracle_ts_demux(libs["oracle"], good, 0xE0)
     with jb.Batch(176, 144, 2, 64, 1 << 20) as b:
+        b.upload_ts([good, good], 0xE0)
+        assert b.ts_writes(0) == want_w
         with pytest.raises(RuntimeError, match=fx["refused"]):
             b.upload_ts([good, ts], fx["stream_id"], None if ws is None else [[len(good)], ws])
+        with pytest.raises(RuntimeError, match="no TS upload"):
+            b.ts_writes(0)
         b.upload_ts([ts[:188 * 2], good], 0xE0)
         assert b.ts_writes(1) == want_w
         assert np.array_equal(b.read_es(1), want_es[:sum(w[2] for w in want_w)])
-
-
-def test_audio_handle_refuses_the_same(hip_lib):
-    from jsmpeg_amd import mp2
-    with mp2.Mp2Batch(2, 1 << 20) as b:
-        with pytest.raises(RuntimeError, match=ts_craft.REFUSED[("spill_junk", False)]):
-            b.upload_ts([ts_craft.CASES["spill_junk"]()], 0xE0)
-        with pytest.raises(RuntimeError, match=ts_craft.REFUSED[("seventeen_pids", False)]):
-            b.upload_ts([ts_craft.CASES["seventeen_pids"]()], 0xC0)
-        b.upload_ts([ts_craft.CASES["sixteen_pids"]()], 0xC0)
-        assert len(b.ts_writes(0)) > 0
 
 
 def check_batch(libs, handle, read, tss, sizes, sid, tag):
@@ -47,6 +41,22 @@ def check_batch(libs, handle, read, tss, sizes, sid, tag):
         assert handle.ts_writes(s) == want_w, (tag, s)                   # pts with ==: both sides divide the same integer by 90000.0
         got = read(s)
         assert len(got) == sum(w[2] for w in want_w) and np.array_equal(got, want_es[:len(got)]), (tag, s)
+
+
+def test_audio_handle_refuses_the_same(hip_lib, libs):
+    """the three refusals through mp2.Mp2Batch.upload_ts, each after a good upload whose write list it must take along"""
+    from jsmpeg_amd import mp2
+    good = [ts_craft.CASES["sixteen_pids"](), ts_craft.CASES["video_audio_null"]()]
+    with mp2.Mp2Batch(2, 1 << 20) as b:
+        for case, sid in (("spill_junk", 0xE0), ("seventeen_pids", 0xC0), ("header_past_packet", 0xE0)):
+            b.upload_ts(good, 0xC0)
+            assert len(b.ts_writes(0)) > 0
+            with pytest.raises(RuntimeError, match=ts_craft.REFUSED[(case, False)]):
+                b.upload_ts([good[0], ts_craft.CASES[case]()], sid)
+            with pytest.raises(RuntimeError, match="no TS upload"):
+                b.ts_writes(0)
+        b.upload_ts(good, 0xC0)
+        check_batch(libs, b, b.read_bytes, good, None, 0xC0, "after the refusals")
 
 
 def test_random_sweep_matches_the_restatement(hip_lib, libs):
