@@ -88,6 +88,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "enc"))
 import mpeg1_enc  # noqa: E402
 for _name, _kw in mpeg1_enc.CASES.items():
     CASES["" + _name] = ("enc:" + _name, _kw["n_frames"], {})
+# Streams written macroblock by macroblock (tests/craft_es.py), committed the same way: the transform at its stated bounds
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import craft_es  # noqa: E402
+CASES[craft_es.BOUNDS_NAME] = ("enc:" + craft_es.BOUNDS_NAME, 2, {})
+# what a fixture records beside the pictures: name -> () -> dict
+EXTRAS = {craft_es.BOUNDS_NAME: lambda: dict(bounds=craft_es.bounds_figures())}
 
 
 def disagreement_record(name, cfg, n, ov, es, runs, why):
@@ -165,6 +171,7 @@ def main():
         fixture = dict(case=name, config=cfg, n_frames=n, overrides=ov, es_bytes=int(len(es)),
                        es_md5=hashlib.md5(es.tobytes()).hexdigest(), agreed_by=sorted(runs), info=info,
                        bit_index_after_decode=idx, frame_md5=first)
+        fixture.update(EXTRAS.get(name, dict)())
         if abi_list != first:
             fixture["abi_frame_md5"] = abi_list   # one entry per decode() == true, skipped pictures repeat the previous one
         with open(os.path.join(HERE, "frames_%s.json" % name), "w") as fo:
