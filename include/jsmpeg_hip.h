@@ -980,6 +980,67 @@ int64_t jsmpeg_hip_ts_mux_device(const void *dev_es, const uint64_t *offset, con
                                  uint8_t *continuity /* in/out */, uint32_t n_streams,
                                  void *dev_ts, uint64_t ts_cap, uint64_t *stream_begin, uint64_t *stream_end);
 
+/* ------------------------------------------------------------------ part 9
+ * The audio half of the way back: an MPEG-1 Audio LAYER II ENCODER on the device.  PCM in HBM -- float32 [frame][2][1152], the
+ * layout parts 3 and 6 leave it in; a mono handle reads channel 0 -- -> constant-bit-rate Layer II frames in a device buffer
+ * that jsmpeg_hip_mp2_batch_upload_device and jsmpeg_hip_ts_mux_device (stream_id 0xC0) take as it is.  The rule is stated
+ * once, in jsmpeg_amd/csrc/mp2_enc.h: exact integer analysis filterbank, scalefactors without lossy merging, a greedy bit
+ * allocation on a fixed noise measure, and a quantiser that is closed-loop against the decoder's own requantiser.  The streams
+ * carry ISO's level: a full-scale sine has subband samples near 1.  (The decoder of parts 3 and 6 returns, like the reference,
+ * HALF of ISO's level -- its window is ISO's D times 2^15 and its output divides by 2^31 -- so PCM decoded here from these
+ * streams is the input times one half, 481 samples late.)
+ * FRAME LENGTHS ARE CLOSED FORM: N = 144000 kbit/s, b = N / fs, r = N mod fs; frame n of a stream (its ordinal, which goes on
+ * across chained calls) has b + floor((n + 1) r / fs) - floor(n r / fs) bytes and begins n b + floor(n r / fs) bytes behind
+ * ordinal 0.  Streams of a call begin at multiples of 16 with zeros up to the next multiple behind each; the total is a
+ * multiple of 16.  So the host knows every offset at enqueue time: a call is ONE kernel, a workgroup per frame, a PURE ENQUEUE
+ * on hip_stream with an event at its end; jsmpeg_hip_mp2_encoder_sync and the readers of device results settle it, the
+ * ranges are answered without waiting.  One pass at a time per handle: a second encode before the first is settled is
+ * REFUSED, as in part 8.  Ordering against the producer of the PCM is the caller's: pass the stream it ran on.
+ * OUT OF SCOPE: a psychoacoustic model, joint stereo, dual channel, CRC, variable bit rate, lossy scfsi merging, a Node binding.
+ * A bad argument returns < 0 with jsmpeg_hip_last_error and nothing is launched; so does a call whose total is above
+ * max_es_bytes (known on the host), and the handle stays usable.  Without a device create returns NULL (no CPU fallback). */
+typedef struct jsmpeg_hip_mp2_encoder_t jsmpeg_hip_mp2_encoder_t;
+typedef struct jsmpeg_hip_mp2_encoder_config_t {
+	uint32_t sample_rate_index;   /* 0: 44100, 1: 48000, 2: 32000 */
+	uint32_t channels;            /* 1: mode mono, 2: mode stereo */
+	uint32_t bitrate_index;       /* 1..14; not 32 / 48 / 56 / 80 kbit/s with two channels, not 224 .. 384 with one */
+	uint32_t max_streams;         /* per call, and the stream numbers of chained calls lie below it */
+	uint32_t max_frames;          /* per call */
+	uint64_t max_es_bytes;        /* output capacity per call (the zeros behind every stream included) */
+	int32_t device;               /* -1: current */
+} jsmpeg_hip_mp2_encoder_config_t;
+#define JSMPEG_HIP_MP2_ENC_END 1u     /* with CHAIN: the chains of the call's streams end behind it (as jsmpeg_hip_mp2_encoder_chain_reset) */
+/* CONTINUE the call's streams: the handle keeps, per stream number, whether the stream has state, its ordinal and which of
+ * two carries on the device holds its last 480 samples per channel.  The first frame of a stream reads that carry, the last
+ * one writes the other, so the pieces of a stream, concatenated in call order, ARE byte for byte the stream one call over all
+ * its frames writes, padding included.  A stream without frames in a call keeps its state; a call without the flag neither
+ * reads nor writes it. */
+#define JSMPEG_HIP_MP2_ENC_CHAIN 2u
+jsmpeg_hip_mp2_encoder_t *jsmpeg_hip_mp2_encoder_create(const jsmpeg_hip_mp2_encoder_config_t *config);
+void jsmpeg_hip_mp2_encoder_destroy(jsmpeg_hip_mp2_encoder_t *enc);
+/* stream i: frames[i] (0 allowed) contiguous frames at the device address pcm[i] (4-byte aligned; ignored for 0 frames), stream
+ * number stream_numbers[i] (strictly ascending, below max_streams; NULL: i) */
+int jsmpeg_hip_mp2_encoder_encode(jsmpeg_hip_mp2_encoder_t *enc, const void *const *pcm, const uint32_t *frames, const uint32_t *stream_numbers,
+                                  uint32_t n_streams, uint32_t flags, void *hip_stream);
+int jsmpeg_hip_mp2_encoder_sync(jsmpeg_hip_mp2_encoder_t *enc);
+/* 1: no pass in flight, 0: still running; never waits */
+int jsmpeg_hip_mp2_encoder_query(jsmpeg_hip_mp2_encoder_t *enc);
+/* the last call's buffer on the device and its bytes (settles the pass) */
+void *jsmpeg_hip_mp2_encoder_es(jsmpeg_hip_mp2_encoder_t *enc, uint64_t *total_bytes);
+/* [begin, end) of stream NUMBER `stream` in that buffer (0, 0: not in the call) and of frame k of the call: closed form, no wait */
+int jsmpeg_hip_mp2_encoder_stream_range(jsmpeg_hip_mp2_encoder_t *enc, uint32_t stream, uint64_t *begin, uint64_t *end);
+int jsmpeg_hip_mp2_encoder_frame_range(jsmpeg_hip_mp2_encoder_t *enc, uint32_t k, uint64_t *offset, uint32_t *bytes);
+/* a stream's bytes to the host (at most cap; host NULL: none); returns the length or < 0 */
+int64_t jsmpeg_hip_mp2_encoder_read_es(jsmpeg_hip_mp2_encoder_t *enc, uint32_t stream, void *host, uint64_t cap);
+/* frame k: pairs that got bits, bits used, bits left over, the largest allocation code */
+int jsmpeg_hip_mp2_encoder_frame_stats(jsmpeg_hip_mp2_encoder_t *enc, uint32_t k, uint32_t out[4]);
+/* ends the chain of `stream` (UINT32_MAX: of every stream); refused while a pass is in flight */
+int jsmpeg_hip_mp2_encoder_chain_reset(jsmpeg_hip_mp2_encoder_t *enc, uint32_t stream);
+/* out[0]: the stream has chain state; out[1]: frames it has coded = the ordinal of its next chained frame */
+int jsmpeg_hip_mp2_encoder_chain_info(jsmpeg_hip_mp2_encoder_t *enc, uint32_t stream, uint64_t out[2]);
+/* the last pass on the device: the kernel (with the upload of its frame list), the whole enqueue */
+int jsmpeg_hip_mp2_encoder_timings(jsmpeg_hip_mp2_encoder_t *enc, float out_ms[2]);
+
 /* Last error of the calling thread ("" if none). */
 const char *jsmpeg_hip_last_error(void);
 /* Number of visible HIP devices (0 if none / runtime unusable). */
