@@ -944,7 +944,7 @@ int64_t jsmpeg_hip_ts_mux_host(const uint8_t *es, const uint64_t *offset, const 
  * is no TS.  jsmpeg_hip_encoder_timings' "write" covers the mux.  The ES buffer and all its readers are what they are
  * without TS; a handle that never calls jsmpeg_hip_encoder_set_ts is byte for byte what it was and allocates nothing new.
  * OUT OF SCOPE: PAT / PMT / PCR (jsmpeg's demuxer needs none; other players do); audio or a second PID in the same buffer
- * (packets are self-contained, so a host may interleave); Node bindings of the encoder; kernel stores straight into pinned
+ * (packets are self-contained, so a host may interleave) -- both are part 10's, jsmpeg_hip_ts_program_*; Node bindings of the encoder; kernel stores straight into pinned
  * host memory.
  * jsmpeg_hip_encoder_set_ts: max_ts_bytes 0 switches TS off (the default); otherwise the TS buffer, the unit table (56 bytes
  * per picture of max_pictures) and max_streams counter words are allocated and ALL counters set to 0.  Refused while a pass is
@@ -1040,6 +1040,104 @@ int jsmpeg_hip_mp2_encoder_chain_reset(jsmpeg_hip_mp2_encoder_t *enc, uint32_t s
 int jsmpeg_hip_mp2_encoder_chain_info(jsmpeg_hip_mp2_encoder_t *enc, uint32_t stream, uint64_t out[2]);
 /* the last pass on the device: the kernel (with the upload of its frame list), the whole enqueue */
 int jsmpeg_hip_mp2_encoder_timings(jsmpeg_hip_mp2_encoder_t *enc, float out_ms[2]);
+
+/* ------------------------------------------------------------------ part 10
+ * TS PROGRAM MUX ON THE DEVICE: the last step of the way back.  A jsmpeg player is fed ONE transport stream per channel with
+ * video and audio interleaved in it; parts 8 and 9 end in one buffer per kind.  A program handle turns two unit tables --
+ * video units over one device buffer, audio units over another -- into one program per stream number, in ONE enqueue and
+ * read back in ONE copy, and on request with PAT / PMT / PCR, so that players other than jsmpeg open the result too.  The
+ * rule is stated once, in jsmpeg_amd/csrc/ts_prog.h, on top of part 8's (enc_ts.h: the PES header, one PES per unit, the
+ * stuffing); jsmpeg_hip_ts_program_mux_host writes the same bytes without a device.
+ * ORDER: per stream number the two lists are merged by PTS (64-bit 90 kHz values, unwrapped; the low 33 bits go out), video
+ * first at equal PTS; a unit's packets lie back to back.  In each table a stream's units are contiguous, the streams ascend
+ * and stay below max_streams, and the PTS do not decrease within a stream: anything else is REFUSED.  A kind whose PID is
+ * configured as 0x1fff is absent: units of it are refused and the PMT does not list it.  In the output the first stream
+ * begins at 0, each next one at the end before it rounded up to 16; the bytes between streams are unspecified.
+ * JSMPEG_HIP_TSP_PCR: the first packet of every unit of the carrier kind (video if present, else audio) carries a PCR of
+ * (pts - pcr_lead_90k) mod 2^33, extension 0, in an adaptation field of 8 bytes -- the only place where the reference's
+ * demuxer (ts.js:143) lets a video PES carry one.
+ * JSMPEG_HIP_TSP_PSI: one PAT packet (PID 0) and one PMT packet (pmt_pid; stream_type 0x01 video, 0x03 audio, PCR_PID the
+ * carrier's) go in front of a stream's first unit since create / reset and in front of every video unit that begins with a
+ * sequence header (00 00 01 B3: every I picture part 8 writes), once where both hold.
+ * STATE per stream number, on the device: the continuity counters of PAT, PMT, video and audio, and `started`.  A call that
+ * does not fit max_ts_bytes (or the caller's buffer) writes NOTHING and leaves all five words; so does a call behind an ES
+ * overflow of the video encoder (jsmpeg_hip_ts_program_mux_encoders).  jsmpeg_hip_ts_program_sync then fails with a message.
+ * A call is a PURE ENQUEUE on hip_stream with an event at its end; one pass at a time per handle: a second call before the
+ * first is settled (sync, or any reader) is REFUSED, as in parts 8 and 9.  Without a device create returns NULL.
+ * OUT OF SCOPE: packet-level interleave inside a unit; T-STD buffer conformance, constant-rate null-packet padding, more than
+ * one audio PID; several frames per PES beyond what the caller's ranges express; B-picture DTS; Node bindings. */
+typedef struct jsmpeg_hip_ts_program_t jsmpeg_hip_ts_program_t;
+typedef struct jsmpeg_hip_ts_program_config_t {
+	uint32_t max_streams;         /* stream numbers lie below it */
+	uint32_t max_video_units;     /* per call */
+	uint32_t max_audio_units;     /* per call */
+	uint64_t max_ts_bytes;        /* output capacity per call (jsmpeg_hip_ts_program_bound) */
+	uint32_t video_pid;           /* 0x1fff: no video */
+	uint32_t audio_pid;           /* 0x1fff: no audio */
+	uint32_t pmt_pid;
+	uint32_t video_stream_id;     /* 0: 0xE0 */
+	uint32_t audio_stream_id;     /* 0: 0xC0 */
+	uint32_t program_number;
+	uint32_t transport_stream_id;
+	uint32_t flags;               /* JSMPEG_HIP_TSP_* */
+	uint64_t pcr_lead_90k;        /* how far the PCR runs behind the PTS it is written with */
+	int32_t device;               /* -1: current */
+} jsmpeg_hip_ts_program_config_t;
+#define JSMPEG_HIP_TSP_PSI 1u
+#define JSMPEG_HIP_TSP_PCR 2u
+/* refuses PIDs above 0x1fff, equal PIDs, PID 0 for anything but the PAT, both kinds absent, stream ids above 0xff, sizes of 0 */
+jsmpeg_hip_ts_program_t *jsmpeg_hip_ts_program_create(const jsmpeg_hip_ts_program_config_t *config);
+void jsmpeg_hip_ts_program_destroy(jsmpeg_hip_ts_program_t *prog);
+/* the calls write into dev_ts (4-byte aligned, cap bytes writable) instead of the handle's own buffer; NULL: the handle's
+ * again.  Refused while a pass is in flight. */
+int jsmpeg_hip_ts_program_set_output(jsmpeg_hip_ts_program_t *prog, void *dev_ts, uint64_t cap);
+/* HOST tables over two device buffers: video unit i is v_bytes[i] bytes at dev_video + v_offset[i], stream number v_stream[i]
+ * (NULL: all 0), PTS v_pts[i]; the audio units likewise.  Pinned staging, uploads on hip_stream, the two kernels, an event. */
+int jsmpeg_hip_ts_program_mux(jsmpeg_hip_ts_program_t *prog,
+                              const void *dev_video, const uint64_t *v_offset, const uint32_t *v_bytes, const uint32_t *v_stream, const uint64_t *v_pts, uint32_t n_v,
+                              const void *dev_audio, const uint64_t *a_offset, const uint32_t *a_bytes, const uint32_t *a_stream, const uint64_t *a_pts, uint32_t n_a,
+                              void *hip_stream);
+/* THE RELAY FORM: the video units are the last call of `enc` -- unit k = picture k's range, the end code as
+ * jsmpeg_hip_encoder_set_ts does it -- taken from the encoder's picture table ON THE DEVICE: that call may still be in flight
+ * on the same hip_stream, nothing is waited for.  The audio units are the frames of the last call of `mp2enc` (closed-form
+ * ranges).  v_pts / a_pts: one value per picture / frame, or NULL: floor(ordinal * 90000 * den / num) of the picture's chain
+ * ordinal, floor(ordinal * 1152 * 90000 / fs) of the frame's.  Either encoder may be NULL; stream numbers are the encoders' own. */
+int jsmpeg_hip_ts_program_mux_encoders(jsmpeg_hip_ts_program_t *prog, jsmpeg_hip_encoder_t *enc, const uint64_t *v_pts,
+                                       jsmpeg_hip_mp2_encoder_t *mp2enc, const uint64_t *a_pts, void *hip_stream);
+int jsmpeg_hip_ts_program_sync(jsmpeg_hip_ts_program_t *prog);
+/* 1: no pass in flight, 0: still running; never waits */
+int jsmpeg_hip_ts_program_query(jsmpeg_hip_ts_program_t *prog);
+/* THE READERS settle the pass and refuse a handle whose last call failed.  The last call's device buffer and its total bytes */
+void *jsmpeg_hip_ts_program_ts(jsmpeg_hip_ts_program_t *prog, uint64_t *total_bytes);
+/* [begin, end) of stream NUMBER `stream` in that buffer (0, 0: not in the call) */
+int jsmpeg_hip_ts_program_stream_range(jsmpeg_hip_ts_program_t *prog, uint32_t stream, uint64_t *begin, uint64_t *end);
+/* unit k of `kind` (0 video, 1 audio) of the call's table: where its packets begin -- at the PAT if PSI lies in front --
+ * their bytes (the PSI's included), and the PSI's bytes (0 or 376); a viewer that joins starts at a unit with PSI */
+int jsmpeg_hip_ts_program_unit_range(jsmpeg_hip_ts_program_t *prog, uint32_t kind, uint32_t k, uint64_t *offset, uint32_t *bytes, uint32_t *psi_bytes);
+/* a stream's program to the host (at most cap; host NULL: none); stream UINT32_MAX: the whole buffer in ONE copy; returns the
+ * length or < 0 */
+int64_t jsmpeg_hip_ts_program_read(jsmpeg_hip_ts_program_t *prog, uint32_t stream, void *host, uint64_t cap);
+/* the stream's words behind the last call: the counters of PAT, PMT, video, audio (what their next packets carry), started */
+int jsmpeg_hip_ts_program_state(jsmpeg_hip_ts_program_t *prog, uint32_t stream, uint32_t out[5]);
+/* zeroes the five words of `stream` (UINT32_MAX: of every stream); refused while a pass is in flight */
+int jsmpeg_hip_ts_program_reset(jsmpeg_hip_ts_program_t *prog, uint32_t stream);
+/* sets the five words of `stream` (counters 0 .. 15, started 0 or 1): a relay that restarts goes on where its streams were;
+ * refused while a pass is in flight */
+int jsmpeg_hip_ts_program_set_state(jsmpeg_hip_ts_program_t *prog, uint32_t stream, const uint32_t in[5]);
+/* the last pass on the device: the uploads and the two kernels, the whole enqueue */
+int jsmpeg_hip_ts_program_timings(jsmpeg_hip_ts_program_t *prog, float out_ms[2]);
+/* THE SAME BYTES ON THE HOST (plain C, no device): the arguments of jsmpeg_hip_ts_program_mux over host bytes.  state: in /
+ * out, 5 words per stream number [config->max_streams] (NULL: zeros, nothing handed back); stream_begin / stream_end: out
+ * arrays [max_streams], may be NULL.  Returns the total bytes, or < 0 (ts_cap too small: nothing is written, the state
+ * stays); ts == NULL: the bytes needed, nothing changes. */
+int64_t jsmpeg_hip_ts_program_mux_host(const jsmpeg_hip_ts_program_config_t *config,
+                                       const uint8_t *video, const uint64_t *v_offset, const uint32_t *v_bytes, const uint32_t *v_stream, const uint64_t *v_pts, uint32_t n_v,
+                                       const uint8_t *audio, const uint64_t *a_offset, const uint32_t *a_bytes, const uint32_t *a_stream, const uint64_t *a_pts, uint32_t n_a,
+                                       uint32_t *state /* in/out */, uint8_t *ts, uint64_t ts_cap, uint64_t *stream_begin, uint64_t *stream_end);
+/* a safe max_ts_bytes: per unit at most bytes / 184 + 2 packets, 2 PSI packets per video unit and per stream, 15 per stream */
+uint64_t jsmpeg_hip_ts_program_bound(uint64_t v_bytes, uint32_t n_v, uint64_t a_bytes, uint32_t n_a, uint32_t streams);
+/* the PAT packet and the PMT packet of `config` (2 * 188 bytes, continuity 0), as the handle uploads them; plain C */
+int jsmpeg_hip_ts_program_psi(const jsmpeg_hip_ts_program_config_t *config, uint8_t out[376]);
 
 /* Last error of the calling thread ("" if none). */
 const char *jsmpeg_hip_last_error(void);

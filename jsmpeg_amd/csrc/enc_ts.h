@@ -26,7 +26,7 @@
  * DEFAULT PTS (jm_ts_default_pts): floor(ordinal * 90000 * den / num) in 64 bits, masked to 33 bits, num / den the pictures per
  *    second of the sequence header's frame_rate_code.
  * OUT OF SCOPE: PAT / PMT / PCR (jsmpeg's demuxer needs none; other players do), audio or a second PID in the same buffer
- *    (packets are self-contained, so a host may interleave).
+ *    (packets are self-contained, so a host may interleave) -- both are part 10's: ts_prog.h builds a program on this rule.
  */
 #pragma once
 #include <stdint.h>

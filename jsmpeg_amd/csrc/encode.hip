@@ -58,6 +58,7 @@
 #include "enc_pass.h"
 #include "enc_scale.h"
 #include "enc_ts.h"
+#include "ts_prog_sources.h"
 
 #define JM_ENC_LANES 64
 #define JM_ENC_MOTION_WAVES 4    /* macroblocks (one wavefront each) of a k_enc_motion workgroup */
@@ -531,6 +532,7 @@ struct jsmpeg_hip_encoder_t {
 	bool ts_pts_set;
 	bool pass_ts;                    /* the last call ran with TS on */
 	bool ts_overflowed;              /* ... and its TS did not fit */
+	JmEncArgs last_args;             /* of the last call that launched (count != 0): for the program mux (ts_prog_sources.h) */
 };
 
 static void enc_free_gop(jsmpeg_hip_encoder_t *e);
@@ -912,6 +914,7 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 	a.pics = e->d_pics; a.tables = e->d_tables; a.mb = e->d_mb; a.slice = e->d_slice; a.result = e->d_result;
 	a.max_streams = e->cfg.max_streams; a.max_pictures = e->cfg.max_pictures;
 	a.words = reinterpret_cast<uint32_t *>(e->d_es);
+	e->last_args = a;
 	const uint64_t lanes = (uint64_t)count * e->mbw * e->mbh;
 	const uint32_t mb_grid = (uint32_t)((lanes + JM_ENC_LANES - 1) / JM_ENC_LANES);
 	e->stream = st;
@@ -1144,6 +1147,26 @@ extern "C" int64_t jsmpeg_hip_encoder_read_ts(jsmpeg_hip_encoder_t *e, uint32_t 
 		HIP_TRY(hipMemcpy(host, e->d_ts + b, k, hipMemcpyDeviceToHost));
 	}
 	return (int64_t)n;
+}
+
+/* ------------------------------------------------------------------ the last call as the program mux's video source
+ * (ts_prog_sources.h): the device-side picture table becomes a unit table on the caller's stream; the host is not waited for */
+int jm_enc_tsp_source(jsmpeg_hip_encoder_t *e, JmTspVideoSource *out, uint32_t *stream, uint32_t *ordinal, uint32_t cap) {
+	if (!e) return fail("ts_program: NULL encoder");
+	if (!e->have_pass) return fail("ts_program: the encoder has not encoded anything yet");
+	if (e->count > cap) return fail("ts_program: the encoder's last call has %u pictures, max_video_units is %u", e->count, cap);
+	out->count = e->count; out->max_streams = e->cfg.max_streams; out->frame_rate_code = e->cfg.frame_rate_code; out->device = e->device;
+	out->d_es = e->d_es; out->d_result = e->d_result;
+	for (uint32_t k = 0; k < e->count; k++) { stream[k] = e->h_pics[k].stream; ordinal[k] = e->h_pics[k].ordinal; }
+	return 0;
+}
+
+int jm_enc_tsp_units(jsmpeg_hip_encoder_t *e, JmTsUnit *d_units, const uint64_t *d_pts, void *hip_stream) {
+	if (!e || !e->have_pass) return fail("ts_program: the encoder has not encoded anything yet");
+	if (!e->count) return 0;
+	k_ts_units<<<dim3((e->count + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream>>>(e->last_args, d_units, d_pts);
+	HIP_TRY(hipGetLastError());
+	return 0;
 }
 
 extern "C" uint64_t jsmpeg_hip_ts_bound(uint64_t es_bytes, uint32_t units, uint32_t streams) { return jm_ts_bound(es_bytes, units, streams); }

@@ -17,6 +17,7 @@
 #include "host_common.h"
 #include "jsmpeg_hip.h"
 #include "mp2_enc.h"
+#include "ts_prog_sources.h"
 
 /* ================================================================================================ kernel */
 
@@ -86,6 +87,7 @@ struct jsmpeg_hip_mp2_encoder_t {
 	uint32_t *d_stats = nullptr, *h_stats = nullptr;
 	std::vector<Mp2EncChain> chain;                            /* per stream number */
 	std::vector<uint64_t> begin, end, b_list, e_list;          /* per stream number; per listed stream */
+	std::vector<uint64_t> ordinal;                             /* per frame of the last call: its ordinal in its stream (ts_prog_sources.h) */
 	uint32_t count = 0;                                        /* frames of the last call */
 	uint64_t total = 0;
 	bool pending = false, have_pass = false;
@@ -194,6 +196,12 @@ extern "C" int jsmpeg_hip_mp2_encoder_encode(jsmpeg_hip_mp2_encoder_t *e, const 
 		const uint32_t s = stream_numbers ? stream_numbers[i] : i;
 		e->begin[s] = e->b_list[i]; e->end[s] = e->e_list[i];
 	}
+	e->ordinal.clear();
+	for (uint32_t i = 0; i < n_streams; i++) {
+		const Mp2EncChain &c = e->chain[stream_numbers ? stream_numbers[i] : i];
+		const uint64_t n0 = ((flags & JSMPEG_HIP_MP2_ENC_CHAIN) && c.have) ? c.n : 0;          /* as mp2e_plan continues the stream */
+		for (uint32_t k = 0; k < frames[i]; k++) e->ordinal.push_back(n0 + k);
+	}
 	mp2e_plan_commit(frames, stream_numbers, n_streams, flags, e->chain.data());
 	if ((flags & JSMPEG_HIP_MP2_ENC_CHAIN) && (flags & JSMPEG_HIP_MP2_ENC_END))
 		for (uint32_t i = 0; i < n_streams; i++) e->chain[stream_numbers ? stream_numbers[i] : i] = Mp2EncChain{ 0, 0, 0 };
@@ -299,5 +307,19 @@ extern "C" int jsmpeg_hip_mp2_encoder_timings(jsmpeg_hip_mp2_encoder_t *e, float
 	HIP_TRY(hipSetDevice(e->device));
 	HIP_TRY(hipEventElapsedTime(&out_ms[0], e->ev[0], e->ev[1]));
 	HIP_TRY(hipEventElapsedTime(&out_ms[1], e->ev[0], e->ev[2]));
+	return 0;
+}
+
+/* ------------------------------------------------------------------ the last call as the program mux's audio source
+ * (ts_prog_sources.h): closed form, so everything is the host's at enqueue time */
+int jm_mp2e_tsp_source(jsmpeg_hip_mp2_encoder_t *e, JmTspAudioSource *out, uint64_t *offset, uint32_t *bytes, uint32_t *stream, uint64_t *ordinal, uint32_t cap) {
+	if (!e) return fail("ts_program: NULL MP2 encoder");
+	if (!e->have_pass) return fail("ts_program: the MP2 encoder has not encoded anything yet");
+	if (e->count > cap) return fail("ts_program: the MP2 encoder's last call has %u frames, max_audio_units is %u", e->count, cap);
+	out->count = e->count; out->max_streams = e->cfg.max_streams; out->sample_rate = (uint32_t)e->R.fs; out->device = e->device;
+	out->d_es = e->d_es;
+	for (uint32_t k = 0; k < e->count; k++) {
+		offset[k] = e->h_frames[k].out; bytes[k] = e->h_frames[k].bytes; stream[k] = e->h_frames[k].stream; ordinal[k] = e->ordinal[k];
+	}
 	return 0;
 }
