@@ -151,12 +151,23 @@ def pcm_s16(x):
     return s.astype(np.int64)
 
 
+def window_sums(samples):
+    """samples: int64 [480 + 1152] of one channel -> Y [36][64]"""
+    idx = 480 + 32 * np.arange(36)[:, None] + 31 - np.arange(512)[None, :]
+    return (W[None, :] * samples[idx]).reshape(36, 8, 64).sum(axis=1)
+
+
+def fold(Y):
+    """Y [36][64] -> the kernel's folded Z [36][32]: Z[0] = Y[16], Z[t] = Y[16 + t] + Y[16 - t] (t <= 16), Y[16 + t] - Y[80 - t] above"""
+    t = np.arange(32)
+    other = np.where(t <= 16, Y[:, 16 - np.minimum(t, 16)], -Y[:, np.minimum(80 - t, 63)])
+    other[:, 0] = 0
+    return Y[:, 16 + t] + other
+
+
 def analysis(samples):
     """samples: int64 [480 + 1152] of one channel -> S [36][32]"""
-    idx = 480 + 32 * np.arange(36)[:, None] + 31 - np.arange(512)[None, :]
-    Z = W[None, :] * samples[idx]                              # [36][512]
-    Y = Z.reshape(36, 8, 64).sum(axis=1)                       # [36][64]
-    acc = Y @ MATRIX.T                                         # [36][32]
+    acc = window_sums(samples) @ MATRIX.T                      # [36][32]
     return (acc + (1 << 27)) >> 28
 
 
@@ -164,6 +175,12 @@ def scale_index(M):
     """largest i in 0..62 with scalefactor(i) >= 2 M, 0 if none"""
     ok = np.nonzero(SCALEFACTORS >= 2 * int(M))[0]
     return int(ok[-1]) if len(ok) else 0
+
+
+def dearest_raise(sblimit, high):
+    """the most bits one raise can cost in the table: over its subbands and codes, the first raise with three scalefactors"""
+    return max(12 * (granule_bits(steps_of(high, sb, code + 1)) - granule_bits(steps_of(high, sb, code))) + (20 if code == 0 else 0)
+               for sb in range(sblimit) for code in range((1 << nbal(high, sb)) - 1))
 
 
 class Bits:
@@ -182,7 +199,9 @@ class Bits:
 
 def encode_frame(cfg, samples, n, info=None):
     """cfg = (sample_rate_index, channels, bitrate_index); samples int64 [2][480 + 1152] (history first); n the ordinal.
-    -> the frame's bytes.  info (a dict) receives S, codes, indices, silent, nsf, left, used."""
+    -> the frame's bytes.  info (a dict) receives S, codes, indices, silent, nsf, scfsi, left, used, and what the tests assert
+    about their inputs: the pair that won each round (winners), the rounds several pairs tied in (ties), nsf of the first
+    raises (first_nsf), how the loop ended (end: "top" / "fit") and the samples clamped at either end of a quantiser."""
     sr, ch_n, br = cfg
     sblimit, high = table_select(sr, ch_n, br)
     size = frame_bytes(sr, br, n)
@@ -201,8 +220,10 @@ def encode_frame(cfg, samples, n, info=None):
     code = {p: 0 for p in pairs}
     left = 8 * size - 32 - sum(nbal(high, sb) for sb, _ in pairs)
     rounds = 0
+    winners, ties, first_nsf = [], [], set()
     while True:
         best, best_key = None, None
+        open_keys = []
         for p in pairs:
             sb, c = p
             if silent[p] or code[p] >= (1 << nbal(high, sb)) - 1:
@@ -212,10 +233,18 @@ def encode_frame(cfg, samples, n, info=None):
             if cost > left:
                 continue
             key = (-8 * min(idx[p]) - gain(so), -sb, -c)
+            open_keys.append((key[0], p))
             if best is None or key > best_key:
                 best, best_key, best_cost = p, key, cost
         if best is None:
             break
+        if info is not None:
+            winners.append(best)
+            tied = [p for noise, p in open_keys if noise == best_key[0]]
+            if len(tied) > 1:                                  # the order (lower subband, then channel 0) decided this round
+                ties.append(tied)
+            if code[best] == 0:
+                first_nsf.add(nsf[best])
         code[best] += 1
         left -= best_cost
         rounds += 1
@@ -251,7 +280,18 @@ def encode_frame(cfg, samples, n, info=None):
                         w.put(v, code_bits(st))
     if info is not None:
         info.update(S=S, code=code, idx=idx, silent=silent, nsf=nsf, left=left, used=w.n, rounds=rounds, pairs=pairs, high=high,
-                    codes={p: coded[p][1] for p in coded})
+                    codes={p: coded[p][1] for p in coded}, sel=sel, sblimit=sblimit, winners=winners, ties=ties, first_nsf=first_nsf)
+        # how the loop ended: every loud pair at its top code with more bits left than the table's dearest raise, or a raise that does not fit
+        loud = [p for p in pairs if not silent[p]]
+        at_top = all(code[p] == (1 << nbal(high, p[0])) - 1 for p in loud)
+        info["end"] = "top" if loud and at_top and left > dearest_raise(sblimit, high) else ("fit" if loud and not at_top else None)
+        low = high_end = 0
+        for (sb, c), (st, _) in coded.items():
+            for part in range(3):
+                c1 = np.searchsorted(-levels(st, idx[sb, c][part]), -S[c, 12 * part:12 * part + 12, sb], "left")
+                low += int((c1 == 0).sum())
+                high_end += int((c1 == st).sum())
+        info["clamped"] = (low, high_end)                      # samples at or above the top level, samples below the lowest one
     assert left == 8 * size - w.n
     return w.bytes(size)
 

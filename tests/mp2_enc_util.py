@@ -41,8 +41,21 @@ def sim_lib():
         L.sim_mp2_enc_frame_bytes.restype = ctypes.c_uint32
         L.sim_mp2_enc_frame_bytes.argtypes = [ctypes.c_int] * 3 + [ctypes.c_uint64]
         L.sim_mp2_enc_pcm_s16.argtypes = [ctypes.c_float]
+        L.sim_mp2_enc_analysis.restype = None
+        L.sim_mp2_enc_analysis.argtypes = [ctypes.c_void_p] * 5
         _sim = L
     return _sim
+
+
+def sim_analysis(samples):
+    """int16 [480 + 1152] of one channel (history first) -> (Y [36][64], Z [36][32], halves [36][32][2], S [36][32]) of the
+    kernel's own mp2e_window_sum, mp2e_window_fold, mp2e_y_lo / _hi and mp2e_matrix_sum"""
+    x = np.ascontiguousarray(samples, dtype=np.int16)
+    assert x.shape == (480 + 1152,)
+    Y, Z = np.zeros((36, 64), np.int64), np.zeros((36, 32), np.int64)
+    halves, S = np.zeros((36, 32, 2), np.int32), np.zeros((36, 32), np.int32)
+    sim_lib().sim_mp2_enc_analysis(x.ctypes.data, Y.ctypes.data, Z.ctypes.data, halves.ctypes.data, S.ctypes.data)
+    return Y, Z, halves, S
 
 
 def sim_main():
@@ -100,6 +113,7 @@ def sim_encode(cfg, streams, numbers=None, chain=False, state=None, want_debug=F
         gap_end = (int(end[i]) + 15) & ~15
         assert not out[int(end[i]):gap_end].any() and int(begin[i]) % 16 == 0
     assert total == ((int(end[n - 1]) + 15) & ~15 if n else 0)
+    assert (out[total:] == 0xAA).all()                            # nothing was written behind the call's bytes
     if want_debug:
         return pieces, stats[:total_frames], S[:total_frames], dbg[:total_frames]
     return pieces, stats[:total_frames]

@@ -71,6 +71,24 @@ int sim_mp2_enc_requantise(int code, int steps, int sf) { return mp2_requantise(
 int sim_mp2_enc_scale_index(int M) { return mp2e_scale_index(M); }
 int sim_mp2_enc_gain(int steps) { return mp2e_gain(steps); }
 int sim_mp2_enc_pcm_s16(float x) { return mp2e_pcm_s16(x); }
+// The analysis of one channel through the kernel's own functions, with what the frame's pass keeps only in passing: x = 480
+// samples of history and the frame's 1152; Y [36][64] (mp2e_window_sum), Z [36][32] (mp2e_window_fold), halves [36][32][2]
+// (mp2e_y_lo / mp2e_y_hi of Z) and S [36][32] (mp2e_matrix_sum over the halves).
+void sim_mp2_enc_analysis(const int16_t *x, int64_t *Y, int64_t *Z, int32_t *halves, int32_t *S) {
+	Mp2EncTables T;
+	mp2e_tables_make(&T);
+	for (int p = 0; p < 36; p++) {
+		const int16_t *newest = x + MP2E_HIST + 32 * p + 31;
+		int32_t z[32][2];
+		for (int i = 0; i < 64; i++) Y[64 * p + i] = mp2e_window_sum(newest, T.win, i);
+		for (int t = 0; t < 32; t++) {
+			const int64_t v = mp2e_window_fold(newest, T.win, t);
+			Z[32 * p + t] = v;
+			halves[64 * p + 2 * t] = z[t][0] = mp2e_y_lo(v); halves[64 * p + 2 * t + 1] = z[t][1] = mp2e_y_hi(v);
+		}
+		for (int k = 0; k < 32; k++) S[32 * p + k] = mp2e_matrix_sum(z, T.cosq, k);
+	}
+}
 void sim_mp2_enc_tables(int32_t *win512, int32_t *cos128) {
 	Mp2EncTables T;
 	mp2e_tables_make(&T);
