@@ -1139,6 +1139,84 @@ uint64_t jsmpeg_hip_ts_program_bound(uint64_t v_bytes, uint32_t n_v, uint64_t a_
 /* the PAT packet and the PMT packet of `config` (2 * 188 bytes, continuity 0), as the handle uploads them; plain C */
 int jsmpeg_hip_ts_program_psi(const jsmpeg_hip_ts_program_config_t *config, uint8_t out[376]);
 
+/* ------------------------------------------------------------------ part 11
+ * PCM RESAMPLER ON THE DEVICE: the audio side's tensor() and its rendition path, one kernel for both.  PCM in HBM -- float32
+ * [frame][2][1152], the layout parts 3 and 6 leave it in -- -> either a padded batch of WAVEFORMS for models (mono or stereo,
+ * f32 / f16 / bf16, e.g. 16 kHz mono f16 for a speech model) or FRAMES at another rate in the layout part 9 reads, so that a
+ * relay sends 48 kHz audio on at 32 kHz beside a smaller video rendition.  The rule is stated once, in
+ * jsmpeg_amd/csrc/pcm_resample.h.  In short: rates 32000 / 44100 / 48000 in, 8000 / 16000 / 22050 / 24000 / 32000 / 44100 /
+ * 48000 out, out != in (18 pairs); L = out / gcd, M = in / gcd; a Kaiser-windowed sinc (beta 9, cut-off 0.9 of the lower
+ * Nyquist, half width H = 16 input samples, ceil(16 M / L) when the rate goes down) as L phases of 2 H float32 taps computed in
+ * double on the host; output m of a stream is gain * sum_j h[(m M) mod L][j] x[floor(m M / L) - 2 H + 1 + j], accumulated in
+ * float32 with one fused multiply-add per tap in ascending j, x = 0 before the stream's first sample; a handle with one
+ * output channel filters 0.5f * (left + right).  After N input samples a stream has ceil(N L / M) outputs: counts are CLOSED
+ * FORM, the host knows every count and offset at enqueue time, a call is ONE kernel and a PURE ENQUEUE on hip_stream with an
+ * event at its end.  A stream resampled in pieces, chained call after chained call, is BIT FOR BIT the stream resampled in
+ * one call.
+ * DELAY: the output is the input delayed by H input samples, H / in_rate seconds (jsmpeg_hip_resample_plan gives H): a relay
+ * shifts its PTS by that much, or accepts it.
+ * LEVEL: gain multiplies every output once (0 means 1.0).  Parts 3 and 6 return half of ISO's level and part 9 expects ISO's,
+ * so a decode-to-encode relay passes gain 2.0 and keeps its level from generation to generation.
+ * One pass at a time per handle: a second call before the first is settled (sync, or timings) is REFUSED, as in parts 8 and
+ * 9.  Results are valid until the handle's next call.  A bad argument -- an unsupported pair, frames above max_frames, a
+ * stream number out of range or not ascending, a stream with more samples than row -- returns < 0 with jsmpeg_hip_last_error,
+ * launches nothing and leaves the handle usable.  Without a device create returns NULL (no CPU fallback).
+ * OUT OF SCOPE: a Node binding, other rates, dither, any filter choice but this one, sample-rate changes inside a stream. */
+typedef struct jsmpeg_hip_resampler_t jsmpeg_hip_resampler_t;
+#define JSMPEG_HIP_RESAMPLE_WAVEFORM 0u
+#define JSMPEG_HIP_RESAMPLE_FRAMES 1u
+#define JSMPEG_HIP_RESAMPLE_F32 0u
+#define JSMPEG_HIP_RESAMPLE_F16 1u
+#define JSMPEG_HIP_RESAMPLE_BF16 2u
+typedef struct jsmpeg_hip_resampler_config_t {
+	uint32_t in_rate, out_rate;   /* Hz */
+	uint32_t channels_out;        /* 2: left and right; 1: their mix, 0.5f * (left + right), made before the filter */
+	uint32_t form;                /* WAVEFORM: [stream of the call][channels_out][row] of dtype, zeros behind a stream's count;
+	                                 FRAMES: float32 [frame][2][1152] at out_rate (one channel: the mix in both), stream after stream */
+	uint32_t dtype;               /* WAVEFORM only; F16 / BF16: the float32 value rounded to nearest even */
+	float gain;                   /* 0: 1.0 */
+	uint32_t max_streams;         /* per call, and the stream numbers of chained calls lie below it */
+	uint32_t max_frames;          /* input frames per call */
+	uint32_t row;                 /* WAVEFORM: samples per stream and channel of the output; 0: what max_frames frames of one stream
+	                                 and END's tail yield */
+	int32_t device;               /* -1: current */
+} jsmpeg_hip_resampler_config_t;
+/* continue every listed stream that has any input -- in this call or in its chain -- by H zero samples, so that the filter's
+ * tail comes out; FRAMES: the last partial frame is filled with zeros.  With CHAIN the chains of the call's streams end
+ * behind it. */
+#define JSMPEG_HIP_RESAMPLE_END 1u
+/* CONTINUE the call's streams: the handle keeps, per stream number, whether the stream has state, its input and output
+ * counts, and which of two carries on the device holds its last 2 H - 1 input samples per channel (FRAMES: and its partial
+ * output frame).  A call reads one and writes the other.  A stream without frames in a call keeps its state; a call without
+ * the flag starts from nothing and stores nothing (FRAMES: without END its partial last frame is dropped). */
+#define JSMPEG_HIP_RESAMPLE_CHAIN 2u
+jsmpeg_hip_resampler_t *jsmpeg_hip_resampler_create(const jsmpeg_hip_resampler_config_t *config);
+void jsmpeg_hip_resampler_destroy(jsmpeg_hip_resampler_t *rs);
+/* the input convention of jsmpeg_hip_mp2_encoder_encode: stream i has frames[i] (0 allowed) contiguous frames at the device
+ * address pcm[i] (4-byte aligned; ignored for 0 frames) and the number stream_numbers[i] (strictly ascending, below
+ * max_streams; NULL: i) */
+int jsmpeg_hip_resampler_resample(jsmpeg_hip_resampler_t *rs, const void *const *pcm, const uint32_t *frames, const uint32_t *stream_numbers,
+                                  uint32_t n_streams, uint32_t flags, void *hip_stream);
+int jsmpeg_hip_resampler_sync(jsmpeg_hip_resampler_t *rs);
+/* 1: no pass in flight, 0: still running; never waits */
+int jsmpeg_hip_resampler_query(jsmpeg_hip_resampler_t *rs);
+/* the last call's buffer on the device and its bytes: closed form, NO wait -- the contents are there once the pass has
+ * finished, that is for work enqueued on the same hip_stream behind it, or after jsmpeg_hip_resampler_sync */
+void *jsmpeg_hip_resampler_out(jsmpeg_hip_resampler_t *rs, uint64_t *bytes);
+/* stream NUMBER `stream` in that buffer (0, 0: not in the call).  WAVEFORM: offset = the element index of its first channel's
+ * row, count = its samples per channel; FRAMES: its first frame and its whole frames.  Closed form, no wait. */
+int jsmpeg_hip_resampler_stream_out(jsmpeg_hip_resampler_t *rs, uint32_t stream, uint64_t *offset, uint64_t *count);
+/* ends the chain of `stream` (UINT32_MAX: of every stream); refused while a pass is in flight */
+int jsmpeg_hip_resampler_chain_reset(jsmpeg_hip_resampler_t *rs, uint32_t stream);
+/* out[0]: the stream has chain state; out[1]: input samples per channel it has taken; out[2]: outputs it has made */
+int jsmpeg_hip_resampler_chain_info(jsmpeg_hip_resampler_t *rs, uint32_t stream, uint64_t out[3]);
+/* the last pass on the device: the kernel, the whole enqueue (with the upload of its stream list) */
+int jsmpeg_hip_resampler_timings(jsmpeg_hip_resampler_t *rs, float out_ms[2]);
+/* The plan of a pair, no device needed: L, M and the half width H (any may be NULL); < 0: not a supported pair */
+int jsmpeg_hip_resample_plan(uint32_t in_rate, uint32_t out_rate, uint32_t *L, uint32_t *M, uint32_t *H);
+/* its taps, L * 2 H floats [phase][tap], as the handle uploads them; no device needed */
+int jsmpeg_hip_resample_taps(uint32_t in_rate, uint32_t out_rate, float *out);
+
 /* Last error of the calling thread ("" if none). */
 const char *jsmpeg_hip_last_error(void);
 /* Number of visible HIP devices (0 if none / runtime unusable). */
