@@ -193,7 +193,11 @@ JM_D uint32_t jm_tk_get2(const JmLane &L, uint32_t s) {
 	return (uint32_t)p[0] | ((uint32_t)p[JM_RING_STRIDE] << 16);
 }
 #else
+#ifndef JM_SIM_LOOK
+#define JM_SIM_LOOK(bp) ((void)0)   /* tests/sim counts the looks by bit phase and ring position (host form only) */
+#endif
 JM_HD uint32_t jm_bits32(const JmLane &L, uint32_t bp) {
+	JM_SIM_LOOK(bp);
 	const uint32_t d = (bp >> 5) & (JM_ES_RING_DW - 1);
 	const uint32_t hi = L.es_ring[d * JM_RING_STRIDE], lo = L.es_ring[(d + 1) * JM_RING_STRIDE];
 	return (uint32_t)(((((uint64_t)hi << 32) | lo) << (bp & 31)) >> 32);

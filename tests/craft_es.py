@@ -11,6 +11,9 @@ streams the reconstruct's tests are built from:
                     intra DC values up to 3953 and down to -3952, random full-amplitude blocks
                     (tests/golden/craft_bounds_192x192.m1v, registered in tests/golden/make_golden.py)
 
+The writer also places skipped macroblocks, increments with escapes and stuffing, slice breaks anywhere, forced escapes and user
+data: the slice parse's inputs are built on it in tests/parse_inputs.py.
+
 Nothing here includes or calls the code under test: the syntax is ISO 11172-2 as tests/enc/mpeg1_enc.py states it (its
 bit writer helpers and VLC tables are reused), the tile geometry is restated from the design (recon_block.h JmTiles:
 which block of a plane sits in which lane of which workgroup).
@@ -100,13 +103,67 @@ def _bytes_of(bits):
     return int(bits, 2).to_bytes(len(bits) // 8, "big") if bits else b""
 
 
+def coef_symbols(levels, first_is_special, esc=()):
+    """the DCT symbols of one block, in order: [(run, level, form, bits)] with form "first" (the non-intra first coefficient's
+    `1s`), "vlc" or "esc20" / "esc28"; esc: the scan INDICES into `levels` whose coefficient takes the escape whatever shorter code
+    exists (True: all of them).  The end_of_block is not in the list."""
+    out = []
+    run, first = 0, first_is_special
+    for i, lv in enumerate(levels):
+        if lv == 0:
+            run += 1
+            continue
+        assert -255 <= lv <= 255
+        mag = abs(lv)
+        forced = esc is True or i in esc
+        if not forced and run == 0 and mag == 1:
+            out.append((run, lv, "first" if first else "vlc", ("1" if first else "11") + ("1" if lv < 0 else "0")))
+        elif not forced and (run, mag) in E.COEFF:
+            out.append((run, lv, "vlc", E.COEFF[(run, mag)] + ("1" if lv < 0 else "0")))
+        else:
+            s = E.T["DCT_ESCAPE"] + format(run, "06b")
+            if -127 <= lv <= 127:
+                out.append((run, lv, "esc20", s + format(lv & 0xFF, "08b")))
+            else:
+                out.append((run, lv, "esc28", s + ("00000000" if lv > 0 else "10000000") + format(lv & 0xFF, "08b")))
+        run, first = 0, False
+    return out
+
+
+def _coef_bits_forms(levels, first_is_special, esc):
+    return "".join(s[3] for s in coef_symbols(levels, first_is_special, esc)) + "10"
+
+
+def _mba_bits(inc, stuffing=0):
+    """macroblock_address_increment: `stuffing` macroblock_stuffing codes, a macroblock_escape per 33, the code of the rest"""
+    parts = [E.INV["MBA"][34]] * stuffing
+    while inc > 33:
+        parts.append(E.INV["MBA"][35])
+        inc -= 33
+    parts.append(E.INV["MBA"][inc])
+    return "".join(parts)
+
+
+USER_DATA_BYTE = 0xA5
+
+
 def write_stream(desc):
     """desc: dict(width, height, frame_rate_code=5, intra_matrix=None, non_intra_matrix=None (64 values in scan order, as the
     header carries them), pictures=[...]); a picture: dict(type="I" | "P", full_pel=0, f_code=1, mbs=[...]) with one entry per
     macroblock in raster order; a macroblock: (q, kind, mv, blocks) with kind "intra" | "coded" (P, no vector) |
     "coded_mv" | "mv" (vector only), mv = (h, v) in the units the stream codes (half-pels, or pels with full_pel), blocks = six
     entries: intra (dc_differential, levels of scan positions 1..) ; else None (not coded) or the levels of scan positions 0..
-    (trailing zeros may be left out).  One slice per macroblock row.  -> (es: np.uint8[], pic_offsets: np.uint32[n + 1])"""
+    (trailing zeros may be left out).  One slice per macroblock row.  -> (es: np.uint8[], pic_offsets: np.uint32[n + 1])
+
+    Beyond that (the slice parse's inputs, tests/parse_inputs.py), all optional:
+      a macroblock (q, "skip", None, None) of a P picture is left out of the stream (the next coded one's increment covers it);
+      a fifth entry of a macroblock, a dict: stuffing=n (macroblock_stuffing codes in front of its increment), esc={block: scan
+      indices into that block's levels, or True} (coefficients that take the escape although a shorter code exists), mv_d=(dh, dv)
+      (a motion differential as given -- None: as computed --, where two land on the same vector: +16 f and -16 f);
+      a picture's slices=[start, ...] or [dict(start=macroblock, row=the row its start code names (default: the macroblock's own;
+      an earlier one makes the first increment that much larger), extra=n extra_information_slice bytes), ...]: a slice runs from
+      its start to the next one's, over row ends if need be (default: one per row); user_data=n: a user-data start code and n
+      bytes in front of the picture's start code (pic_offsets points at it)."""
     width, height = desc["width"], desc["height"]
     mbw, mbh = (width + 15) >> 4, (height + 15) >> 4
     cw, ch = mbw * 16, mbh * 16
@@ -132,6 +189,9 @@ def write_stream(desc):
         r_size = f_code - 1
         span = 16 << r_size
         pic_offsets.append(len(out))
+        if pic.get("user_data") is not None:
+            out += b"\x00\x00\x01\xb2" + bytes([USER_DATA_BYTE]) * pic["user_data"]
+            n_codes += 1
         ph = _StrBits()
         ph.put(t & 1023, 10); ph.put(2 if is_p else 1, 3); ph.put(0xFFFF, 16)
         if is_p:
@@ -143,17 +203,36 @@ def write_stream(desc):
         mbs = pic["mbs"]
         assert len(mbs) == mbw * mbh
         mbtype = E.INV["MBTYPE_P" if is_p else "MBTYPE_I"]
-        inc1 = E.INV["MBA"][1]
-        for row in range(mbh):
-            q = mbs[row * mbw][0]
-            parts = [format(q, "05b"), "0"]
+        slices = [s if isinstance(s, dict) else dict(start=s) for s in pic.get("slices", range(0, mbw * mbh, mbw))]
+        assert slices and slices[0]["start"] == 0 and all(a["start"] < b["start"] for a, b in zip(slices, slices[1:]))
+        for si, sl in enumerate(slices):
+            start = sl["start"]
+            stop = slices[si + 1]["start"] if si + 1 < len(slices) else mbw * mbh
+            code_row = sl.get("row", start // mbw)
+            assert 0 <= code_row <= start // mbw and code_row < 175
+            assert mbs[start][1] != "skip" and mbs[stop - 1][1] != "skip", "a slice begins and ends with a coded macroblock"
+            q = mbs[start][0]
+            parts = [format(q, "05b")] + ["1" + format(USER_DATA_BYTE, "08b")] * sl.get("extra", 0) + ["0"]
             dc = [128, 128, 128]
             pmh = pmv = 0
             last_len = 0
-            for col in range(mbw):
-                new_q, kind, mv, blocks = mbs[row * mbw + col]
+            inc = start - code_row * mbw + 1
+            for addr in range(start, stop):
+                row, col = divmod(addr, mbw)
+                entry = mbs[addr]
+                new_q, kind, mv, blocks = entry[:4]
+                opts = entry[4] if len(entry) > 4 else {}
+                if kind == "skip":
+                    # left out: the decoder's resets (mpeg1.c:1060-1082)
+                    assert is_p, "intra pictures skip nothing"
+                    inc += 1
+                    dc = [128, 128, 128]
+                    pmh = pmv = 0
+                    continue
+                esc = opts.get("esc", {})
                 assert 1 <= new_q <= 31 and len(blocks) == 6
-                mb = [inc1]
+                mb = [_mba_bits(inc, opts.get("stuffing", 0))]
+                inc = 1
                 use_q = new_q != q
                 if kind == "intra":
                     mb.append(mbtype[0x11 if use_q else 0x01])
@@ -165,7 +244,7 @@ def write_stream(desc):
                         dc[comp] += diff
                         assert abs(dc[comp]) <= DC_LIMIT, "intra DC %d" % dc[comp]
                         mb.append(_dc_bits(diff, b < 4))
-                        mb.append(_coef_bits(levels, False))
+                        mb.append(_coef_bits_forms(levels, False, esc[b]) if b in esc else _coef_bits(levels, False))
                 else:
                     assert is_p and kind in ("coded", "coded_mv", "mv")
                     cbp = 0
@@ -183,17 +262,20 @@ def write_stream(desc):
                     else:
                         mh, mvv = (mv[0] << 1, mv[1] << 1) if full_pel else mv
                         assert E.mv_ok(cw, ch, col, row, mh, mvv), "vector (%d, %d) leaves the picture at macroblock (%d, %d)" % (mh, mvv, col, row)
-                        for cur, prev in ((mv[0], pmh), (mv[1], pmv)):
+                        for cur, prev, given in ((mv[0], pmh, opts.get("mv_d", (None, None))[0]), (mv[1], pmv, opts.get("mv_d", (None, None))[1])):
                             assert -span <= cur < span
                             d = cur - prev
                             d = d + 2 * span if d < -span else (d - 2 * span if d >= span else d)
+                            if given is not None:                      # the other differential that lands on the same vector: +16 f for -16 f
+                                assert (given - d) % (2 * span) == 0 and -span <= given <= span
+                                d = given
                             mb.append(_mv_bits(d, r_size))
                         pmh, pmv = mv
                     if cbp:
                         mb.append(E.INV["CBP"][cbp])
                         for b in range(6):
                             if blocks[b] is not None:
-                                mb.append(_coef_bits(blocks[b], True))
+                                mb.append(_coef_bits_forms(blocks[b], True, esc[b]) if b in esc else _coef_bits(blocks[b], True))
                 q = new_q
                 s = "".join(mb)
                 last_len = len(s)
@@ -203,7 +285,7 @@ def write_stream(desc):
             assert last_len > 8, "the last macroblock of a slice is %d bits" % last_len
             payload = _bytes_of("".join(parts))
             assert payload.find(b"\x00\x00\x01") < 0, "start code emulated inside a slice"
-            out += bytes([0, 0, 1, row + 1]) + payload
+            out += bytes([0, 0, 1, code_row + 1]) + payload
             n_codes += 1
     out += b"\x00\x00\x01\xb7"
     n_codes += 1

@@ -14,7 +14,57 @@
 #include "index_tables.h"
 #include "recon_block.h"
 #include "recon_plan.h"
+static void sim_look(uint32_t bp);
+#define JM_SIM_LOOK(bp) sim_look(bp)   /* slice_parse.h, host form of jm_bits32: every look at the ring's bits */
 #include "slice_parse.h"
+
+// What the parse's inputs REACH (tests/test_parse_edges.py): figures of the walk that only matter on the device -- how close a
+// lane comes to the bits and token slots its rings hold, at which bit phases and ring positions it looks -- recorded by the
+// same loop that decodes.  One flat array; sim_reach_layout() names its fields.  Kinds: the four steps, then 4 = the slice
+// header (jm_lane_init).
+enum {
+	R_MAX_TURN_BITS = 0,                      // the most bits one lane consumed in one turn
+	R_MAX_STEP_BITS = 1,                      // [4] ... in one step of each kind
+	R_MIN_ROOM = 5,                           // the least fillc * 128 - bp at which a lane stepped
+	R_MIN_ROOM_TURN = 6,                      // ... at the first step a lane took in a turn
+	R_MIN_MARGIN = 7,                         // the least (room - 32 - the bits that step consumed), + 2^32 (negative values stay visible)
+	R_PHASE = 8,                              // [5][32] looks by kind and bp & 31
+	R_SPAN_ROW = R_PHASE + 5 * 32,            // [5] looks whose 32 bits lie in two ring rows, ...
+	R_SPAN_CHUNK = R_SPAN_ROW + 5,            // [5] ... in two 16-byte chunks, ...
+	R_SPAN_WRAP = R_SPAN_CHUNK + 5,           // [5] ... in row 15 and the copy of row 0
+	R_MAX_OCC_TURN = R_SPAN_WRAP + 5,         // the most token slots in use (tw7 - tf7) when a lane began a turn's steps, ...
+	R_MAX_OCC_STEP = R_MAX_OCC_TURN + 1,      // ... at the entry of any step, ...
+	R_MAX_OCC_AFTER = R_MAX_OCC_STEP + 1,     // ... and behind any step
+	R_DRAINS = R_MAX_OCC_AFTER + 1,           // [2] 16-token groups drained from ring slot 0, from slot 16
+	R_TAILS = R_DRAINS + 2,                   // [16] jm_lane_finish: tokens left for its dword-by-dword tail
+	R_HELD_BACK = R_TAILS + 16,               // services in which JM_REFILL_MIN held a lane's refill back
+	R_SERVED = R_HELD_BACK + 1,               // [5] services by the chunks a lane was given (0 .. 4)
+	R_LANDED_LATER = R_SERVED + 5,            // two-halves service: requests whose chunks landed at the top of the next turn
+	R_TURN_STEPS = R_LANDED_LATER + 1,        // [6] turns by the steps one lane took in them (0 .. 5)
+	R_COUNT = R_TURN_STEPS + 6
+};
+static uint64_t g_reach[R_COUNT];
+static int g_look_kind = 4;
+static void sim_reach_reset() {
+	memset(g_reach, 0, sizeof(g_reach));
+	g_reach[R_MIN_ROOM] = g_reach[R_MIN_ROOM_TURN] = g_reach[R_MIN_MARGIN] = ~0ull;
+}
+static void sim_look(uint32_t bp) {
+	const int k = g_look_kind;
+	g_reach[R_PHASE + 32 * k + (bp & 31)]++;
+	if (bp & 31) {
+		g_reach[R_SPAN_ROW + k]++;
+		if ((bp & 127) > 96) g_reach[R_SPAN_CHUNK + k]++;
+		if (((bp >> 5) & (JM_ES_RING_DW - 1)) == JM_ES_RING_DW - 1) g_reach[R_SPAN_WRAP + k]++;
+	}
+}
+static inline void reach_max(int i, uint64_t v) { if (v > g_reach[i]) g_reach[i] = v; }
+static inline void reach_min(int i, uint64_t v) { if (v < g_reach[i]) g_reach[i] = v; }
+static inline uint32_t reach_chunks(uint32_t n) { return n < 4 ? n : 4; }   /* (a damaged stream can move bp past the ring: more than four only there) */
+static void reach_drains(uint32_t tf_from, uint32_t tf_to) {
+	for (uint32_t t = tf_from; t + JM_TK_GROUP * JM_TW_UNIT <= tf_to; t += JM_TK_GROUP * JM_TW_UNIT)
+		g_reach[R_DRAINS + (((t >> JM_TW_SHIFT) & (JM_TK_RING - 1)) ? 1 : 0)]++;
+}
 
 struct HostSlot {
 	int16_t v[72];
@@ -63,6 +113,8 @@ void sim_set_dumps(uint32_t *sc_pos, uint8_t *sc_code, uint32_t *owner, uint8_t 
 	g_dump_sc_pos = sc_pos; g_dump_sc_code = sc_code; g_dump_owner = owner; g_dump_mb = mb; g_dump_tok = tok;
 }
 const uint32_t *sim_dump_counts(void) { return g_dump_counts; }
+static std::vector<uint64_t> g_dump_tok_off;      // per picture of the last decode: its first slot in the token dump (JmMbRec.tok counts from there)
+const uint64_t *sim_dump_tok_off(void) { return g_dump_tok_off.data(); }
 const uint64_t *sim_turns(void);
 const uint64_t *sim_served(void);
 void sim_reset_counters(void);
@@ -136,14 +188,25 @@ int sim_decode_stream(const uint8_t *es_in, uint32_t n, int width, int height, u
 			if (!limit_bytes) continue;
 			const uint32_t rel = (uint32_t)(pic.tok_off & (JM_TK_GROUP - 1));
 			const uint32_t slot = (rel + (pos - pic.pos) * JM_TOKENS_PER_BYTE + JM_TK_GROUP - 1) & ~(uint32_t)(JM_TK_GROUP - 1);
+			g_look_kind = 4;
 			jm_lane_init(L[l], reinterpret_cast<const uint4_like_t *>(es.data()), pos + 4, limit_bytes, sc_code[i], C[l],
 			             mb.data() + (size_t)p * g.mb_size,
 			             reinterpret_cast<uint4_like_t *>(tokens.data()) + ((pic.tok_off - rel) >> 3), slot, rel);
+			g_reach[R_SERVED + reach_chunks(L[l].fillc)]++;   /* the slice's first refill: the whole ring */
 			mine[l] = true;
 		}
 		bool landing = false;
 		for (;;) {
-			if (landing) { for (int l = 0; l < 64; l++) { jm_lane_land(L[l]); if (L[l].state != JM_ST_DONE) jm_lane_drain(L[l]); } landing = false; }
+			if (landing) {
+				for (int l = 0; l < 64; l++) {
+					const uint32_t f0 = L[l].fillc, req = L[l].pend_t;
+					jm_lane_land(L[l]);
+					if (req) { g_reach[R_SERVED + reach_chunks(L[l].fillc - f0)]++; if (L[l].fillc > f0) g_reach[R_LANDED_LATER]++; }
+					if (L[l].state != JM_ST_DONE) { const uint32_t t0 = L[l].tf7; jm_lane_drain(L[l]); reach_drains(t0, L[l].tf7); }
+				}
+				landing = false;
+			}
+			uint32_t turn_bits[64] = { 0 }, turn_steps[64] = { 0 };
 			bool ready[64];
 			int n_cold = 0, n_other = 0, n_blocked = 0;
 			for (int l = 0; l < 64; l++) {
@@ -157,7 +220,13 @@ int sim_decode_stream(const uint8_t *es_in, uint32_t n, int width, int height, u
 			g_picks++; g_cost += (uint64_t)g_kcost[JM_ST_KINDS];
 			if (n_blocked) {
 				g_turns[JM_ST_WAIT]++; g_served[JM_ST_WAIT] += n_blocked; g_cost += (uint64_t)g_kcost[JM_ST_WAIT];
-				if (!g_split_service) for (int l = 0; l < 64; l++) if (L[l].state != JM_ST_DONE) jm_lane_service(L[l]);
+				if (!g_split_service) for (int l = 0; l < 64; l++) if (L[l].state != JM_ST_DONE) {
+					const uint32_t f0 = L[l].fillc, t0 = L[l].tf7, target = (L[l].bp >> 7) + JM_ES_RING_DW / 4;
+					jm_lane_service(L[l]);
+					g_reach[R_SERVED + reach_chunks(L[l].fillc - f0)]++;
+					if (f0 < target && L[l].fillc == f0) g_reach[R_HELD_BACK]++;
+					reach_drains(t0, L[l].tf7);
+				}
 			}
 			bool live_top[64];                               /* (the two-halves form requests behind the header step: kernels.hip) */
 			for (int l = 0; l < 64; l++) live_top[l] = L[l].state != JM_ST_DONE;
@@ -171,7 +240,10 @@ int sim_decode_stream(const uint8_t *es_in, uint32_t n, int width, int height, u
 #endif
 				const int k = order[oi];
 				if (oi == 1 && n_blocked && g_split_service) {   /* behind the header step's place in the turn, whether or not it ran */
-					for (int l = 0; l < 64; l++) if (live_top[l]) jm_lane_request(L[l]);
+					for (int l = 0; l < 64; l++) if (live_top[l]) {
+						jm_lane_request(L[l]);
+						if (!L[l].pend_t && L[l].fillc < (L[l].bp >> 7) + JM_ES_RING_DW / 4) g_reach[R_HELD_BACK]++;
+					}
 					landing = true;
 				}
 				if (k == JM_ST_COLD && !cold) continue;
@@ -187,17 +259,37 @@ int sim_decode_stream(const uint8_t *es_in, uint32_t n, int width, int height, u
 				int served = 0;
 				for (int l = 0; l < 64; l++) if (ready[l] && L[l].state == k) {
 					served++;
+					const uint32_t bp0 = L[l].bp, room = L[l].fillc * 128u - L[l].bp, occ = (L[l].tw7 - L[l].tf7) >> JM_TW_SHIFT;
+					g_look_kind = k;
 					if (k == JM_ST_COLD) jm_step_cold(L[l], C[l]);
 					else if (k == JM_ST_DC) jm_step_dc(L[l], C[l]);
 					else if (k == JM_ST_COEF) jm_step_coef(L[l], C[l]);
 					else jm_step_slow(L[l], C[l]);
+					g_look_kind = 4;
+					const uint32_t bits = L[l].bp - bp0;
+					reach_max(R_MAX_STEP_BITS + k, bits);
+					reach_min(R_MIN_ROOM, room);
+					if (!turn_steps[l]) { reach_min(R_MIN_ROOM_TURN, room); reach_max(R_MAX_OCC_TURN, occ); }
+					reach_min(R_MIN_MARGIN, (uint64_t)((int64_t)room - 32 - (int64_t)bits + (1ll << 32)));
+					reach_max(R_MAX_OCC_STEP, occ);
+					reach_max(R_MAX_OCC_AFTER, (L[l].tw7 - L[l].tf7) >> JM_TW_SHIFT);
+					turn_bits[l] += bits; turn_steps[l]++;
+					reach_max(R_MAX_TURN_BITS, turn_bits[l]);
 				}
 				g_turns[k]++; g_served[k] += served; if (served) g_cost += (uint64_t)g_kcost[k];
 			}
+			for (int l = 0; l < 64; l++) if (mine[l]) g_reach[R_TURN_STEPS + (turn_steps[l] < 5 ? turn_steps[l] : 5)]++;
 		}
-		for (int l = 0; l < 64; l++) if (mine[l]) jm_lane_finish(L[l]);
+		for (int l = 0; l < 64; l++) if (mine[l]) {
+			const uint32_t left = (L[l].tw7 - L[l].tf7) >> JM_TW_SHIFT;
+			reach_drains(L[l].tf7, L[l].tf7 + (left & ~(uint32_t)(JM_TK_GROUP - 1)) * JM_TW_UNIT);
+			g_reach[R_TAILS + (left & (JM_TK_GROUP - 1))]++;
+			jm_lane_finish(L[l]);
+		}
 	}
 
+	g_dump_tok_off.assign(n_pics, 0);
+	for (uint32_t p = 0; p < n_pics; p++) g_dump_tok_off[p] = pics[p].tok_off;
 	g_dump_counts[0] = n_sc; g_dump_counts[1] = n_pics; g_dump_counts[2] = (uint32_t)g.mb_size; g_dump_counts[3] = (uint32_t)tokens.size();
 	if (g_dump_sc_pos) memcpy(g_dump_sc_pos, sc_pos.data(), n_sc * 4);
 	if (g_dump_sc_code) memcpy(g_dump_sc_code, sc_code.data(), n_sc);
@@ -302,6 +394,17 @@ unsigned long long jm_sim_stale_windows;   /* slice_parse.h jm_win (host form): 
 unsigned long long sim_stale_windows(void) { return jm_sim_stale_windows; }
 void sim_split_service(int on) { g_split_service = on; }
 void sim_reset_counters(void) { memset(g_turns, 0, sizeof(g_turns)); memset(g_served, 0, sizeof(g_served)); memset(g_states, 0, sizeof(g_states)); g_picks = 0; g_cost = 0; }
+// the reach figures (see the enum at the top): cleared by sim_reach_reset_all, accumulated over every decode until the next
+void sim_reach_reset_all(void) { sim_reach_reset(); jm_sim_stale_windows = 0; }
+const uint64_t *sim_reach(void) { return g_reach; }
+const char *sim_reach_layout(void) {
+	return "max_turn_bits:1,max_step_bits:4,min_room:1,min_room_turn:1,min_margin:1,phase:160,span_row:5,span_chunk:5,span_wrap:5,"
+	       "max_occ_turn:1,max_occ_step:1,max_occ_after:1,drains:2,tails:16,held_back:1,served:5,landed_later:1,turn_steps:6";
+}
+const int *sim_parse_constants(void) {
+	static const int c[] = { JM_STEP_BITS, JM_TK_RING, JM_COEF_SLOTS, JM_COEF_REPEAT, JM_REFILL_MIN, JM_ES_RING_DW, JM_TK_GROUP, R_COUNT };
+	return c;
+}
 
 // The engine's reconstruct plan (recon_plan.h) on plain arrays: stale[] and level[] out, returns the number of levels.
 int sim_plan(uint32_t n_pics, uint32_t n_streams, const uint8_t *decoded, const int32_t *fwd, const uint32_t *stream,
