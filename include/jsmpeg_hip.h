@@ -875,6 +875,41 @@ int jsmpeg_hip_encoder_encode_scaled(jsmpeg_hip_encoder_t *enc, const void *cons
  * frames[k] after jsmpeg_hip_encoder_encode, the handle's store after _encode_rgb (converted) and _encode_scaled (scaled).
  * Settles the pass first, like the other readers. */
 const void *jsmpeg_hip_encoder_source(jsmpeg_hip_encoder_t *enc, uint32_t k);
+/* A MOSAIC: one coded picture composed from MANY sources, plane to plane -- a wall of cameras, picture in picture.  A LAYOUT is
+ * a fill colour and 1 .. 64 cells; a cell is the geometry of its frames (the descriptor _encode_scaled reads: size, crop,
+ * antialias -- the sources may all differ) and a destination rectangle in the encoder's display pixels, x / y even, inside the
+ * picture.  Every plane is filled, then each cell's three scaled planes (enc_scale.h, at the cell's size) are pasted in index
+ * order: a later cell wins where cells overlap.  The rule, bit for bit, is jsmpeg_amd/csrc/enc_mosaic.h; one cell over the
+ * whole picture is jsmpeg_hip_encoder_encode_scaled of that source.
+ * OUT OF SCOPE: alpha blending, borders, labels and text, cells that change per picture within a call, rotation, a Node binding. */
+typedef struct jsmpeg_hip_enc_cell_t {
+	jsmpeg_hip_enc_source_t source;                       /* of this cell's frames */
+	uint32_t x, y, width, height;                         /* where it goes: display pixels of the encoder, x / y even */
+} jsmpeg_hip_enc_cell_t;   /* 44 bytes */
+/* The layout is STATE OF THE HANDLE, like the GOP: checked, planned, its table built and uploaded here (synchronously; this
+ * call allocates the table, max_pictures * n_cells frame pointers and, if no call has yet, the frame store).  fill: Y | Cr << 8 |
+ * Cb << 16.  n_cells = 0 removes the layout.  Refused while a pass is in flight, and -- with a message that names the cell -- for
+ * every breach of the rule: n_cells above 64, NULL cells, a bad source descriptor, a zero size, an odd x or y, a rectangle
+ * outside the picture; nothing changes then and the layout before stays. */
+int jsmpeg_hip_encoder_set_mosaic(jsmpeg_hip_encoder_t *enc, const jsmpeg_hip_enc_cell_t *cells, uint32_t n_cells, uint32_t fill);
+/* frames[k * n_cells + c]: DEVICE pointer to cell c's frame for picture k (Y | Cr | Cb of that cell's source's coded size, 16-byte
+ * aligned), or NULL: the cell is ABSENT from that picture and what lies under it shows; all NULL: the picture is all fill.  The
+ * host touches no pixel: only the pointer array goes up, from pinned memory on hip_stream.  Everything else is
+ * jsmpeg_hip_encoder_encode_scaled's: a pure enqueue; GOP, rate control, JSMPEG_HIP_ENC_CHAIN, TS, overflow and the readers
+ * behind the planes unchanged; "convert" of the timings covers the composition; jsmpeg_hip_encoder_source returns the composed
+ * planes.  Refused without a layout, for a misaligned frame, and by the argument checks of the other entry points. */
+int jsmpeg_hip_encoder_encode_mosaic(jsmpeg_hip_encoder_t *enc, const void *const *frames, const uint32_t *stream, const uint8_t *qscale,
+                                     uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream);
+/* What feeds a mosaic from part 5: device_frames[k] = the frame of the NEWEST decoded picture of live stream streams[k], from
+ * whichever tick decoded it (the ring slot jsmpeg_hip_live_render_tensor_latest reads), or NULL for a stream that has decoded
+ * nothing yet.  Settles a tick in flight first; a stream that is not open is an error.  HOW LONG THE POINTER HOLDS ITS PICTURE:
+ * a stream's ring has max_pictures_per_tick + 2 frames and its pictures are written to the slots after the newest one, in turn;
+ * so the frame is written again by the stream's (max_pictures_per_tick + 2)-th picture decoded after this call, and not before.
+ * A tick decodes at most max_pictures_per_tick pictures of a stream: the pointer always outlives the NEXT tick whole (that tick
+ * writes the other slots), and with one picture per tick the max_pictures_per_tick + 1 next ticks.  A consumer's work on the
+ * device must be over before the tick that decodes that picture is begun: ordering is the caller's, as everywhere in part 8.
+ * Closing the stream ends the promise. */
+int jsmpeg_hip_live_latest_frames(jsmpeg_hip_live_t *live, const uint32_t *streams, uint32_t count, const void **device_frames);
 int jsmpeg_hip_encoder_sync(jsmpeg_hip_encoder_t *enc);             /* settles; < 0 with a message on overflow: nothing of the call is valid */
 int jsmpeg_hip_encoder_query(jsmpeg_hip_encoder_t *enc);            /* 1 finished, 0 not; never blocks */
 void *jsmpeg_hip_encoder_es(jsmpeg_hip_encoder_t *enc, uint64_t *total_bytes);   /* device buffer of the last call; NULL after an overflow */

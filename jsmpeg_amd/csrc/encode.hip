@@ -9,6 +9,7 @@
  * A pass on the caller's stream, every size and offset worked out on the device:
  *   k_enc_rgb            tensor input only: RGB -> Y | Cr | Cb of the coded size in the encoder's frame store
  *   k_enc_scale          scaled input only: planes of another size, cropped and scaled into the same store (the rule: enc_scale.h)
+ *   k_enc_mosaic         mosaic input only: one picture of the store composed from many sources (the rule: enc_mosaic.h)
  *   k_enc_measure        a macroblock per lane: transform, quantise, count bits; 12 bytes per macroblock out
  *   k_enc_scan_slices    a slice per lane: the macroblocks' bit offsets (their DC codes depend on the predecessor), the slice's bytes
  *   k_enc_scan_pictures  a picture per lane: the slices' offsets, the picture's bytes
@@ -57,6 +58,7 @@
 #include "engine_internal.h"
 #include "enc_pass.h"
 #include "enc_scale.h"
+#include "enc_mosaic.h"
 #include "enc_ts.h"
 #include "ts_prog_sources.h"
 
@@ -177,6 +179,160 @@ __global__ void __launch_bounds__(256) k_enc_scale(JmEncArgs a, JmEncScaleArgs s
 			if (ol >= nh || cg * 4u >= nw) continue;
 			*reinterpret_cast<uint32_t *>(O + (size_t)(oy0 + ol) * q.out_w + ox0 + cg * 4u) =
 				jm_es_round_v(acc[i][0]) | (jm_es_round_v(acc[i][1]) << 8) | (jm_es_round_v(acc[i][2]) << 16) | (jm_es_round_v(acc[i][3]) << 24);
+		}
+	}
+}
+
+/* Mosaic input (the rule, the table and the tile plan: enc_mosaic.h; the CPU simulator tests/sim/sim_encode_mosaic.cpp pastes
+ * the same samples pixel by pixel).  A workgroup owns a tile of JM_ES_TW x JM_ES_TH samples of one plane of the coded size of
+ * one picture and composes it in LDS: the fill, then -- for each cell in index order whose rectangle in this plane meets the
+ * tile and whose frame is there (found by the first wavefront, a cell per lane) -- k_enc_scale's three steps over the
+ * intersection (stage the source rows in chunks, horizontal pass, vertical pass across chunks in registers; the cell's entries
+ * at cell-local indices), the result written over the composed bytes.  Every byte of the tile is this workgroup's, so overlapping cells are ordered by its barriers alone.  Then
+ * the last display column and row are replicated into the coded margin (every tile holds one of each: enc_mosaic.h TILES) and
+ * whole words are stored, once per word.  28.25 KiB of LDS: k_enc_scale's 24.25 and the composed tile. */
+/* src_frames: [count][p.n], the cells' frames, NULL = absent; tab: the layout's table.  Both are parameters of their own and restrict:
+ * nothing the kernel stores goes through them, so what is read from them stays in scalar registers across the barriers. */
+static_assert(JM_EM_MAX_CELLS == 64u, "k_enc_mosaic finds a tile's cells with one wavefront, a cell per lane");
+__global__ void __launch_bounds__(256) k_enc_mosaic(JmEncArgs a, JmEmPlan p, const uint8_t *const *__restrict__ src_frames,
+                                                    const uint32_t *__restrict__ tab) {
+	__shared__ __attribute__((aligned(16))) uint8_t src[JM_ES_SRC];
+	__shared__ __attribute__((aligned(16))) uint16_t ts[JM_ES_CR][JM_ES_TW];
+	__shared__ uint32_t vt[JM_ES_TH][2];
+	__shared__ __attribute__((aligned(16))) uint8_t comp[JM_ES_TH][JM_ES_TW];
+	__shared__ uint32_t hit[2];      /* the cells of this picture that meet the tile, a bit each */
+	const uint32_t nl = p.tiles_x[0] * p.tiles_y[0], nc = p.tiles_x[1] * p.tiles_y[1];
+	uint32_t tile = blockIdx.x, plane = 0;
+	if (tile >= nl) { tile -= nl; plane = 1; if (tile >= nc) { tile -= nc; plane = 2; } }
+	const uint32_t ck = plane ? 1u : 0u;
+	const uint32_t out_w = p.out_w[ck], out_h = p.out_h[ck];
+	const uint32_t ox0 = (tile % p.tiles_x[ck]) * JM_ES_TW, oy0 = (tile / p.tiles_x[ck]) * JM_ES_TH;
+	const uint32_t nw = min(JM_ES_TW, out_w - ox0), nh = min(JM_ES_TH, out_h - oy0);
+	/* the display samples of the tile: vw x vh, at least 1 x 1 */
+	const uint32_t vw = min(nw, p.disp_w[ck] - ox0), vh = min(nh, p.disp_h[ck] - oy0);
+	const uint32_t tid = threadIdx.x;
+	/* rg is the same in all 64 lanes of a wavefront.  Read as a scalar, the 16 row offsets of the horizontal pass live in scalar
+	 * registers; as a per-lane value they took 16 vector registers which, beside acc[][] and a cell's values, left the compiler
+	 * none under the 128 of four wavefronts per SIMD to keep the tap's 16 LDS reads in flight together: it issued them one at a
+	 * time, each waited for (profiles/enc_mosaic_notes.md). */
+	const uint32_t col = tid & (JM_ES_TW - 1u), rg = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid / JM_ES_TW));
+	const uint32_t gran = plane ? 8u : 16u;
+	const uint32_t out_off = plane == 0 ? 0u : plane == 1 ? p.out_luma : p.out_luma + p.out_chroma;
+	const uint32_t fill4 = ((p.fill >> (8u * plane)) & 0xffu) * 0x01010101u;
+	const JmEmCellRec *recs = reinterpret_cast<const JmEmCellRec *>(tab);
+	for (uint32_t k = blockIdx.y; k < a.count; k += gridDim.y) {
+		uint8_t *O = const_cast<uint8_t *>(a.pics[k].frame) + out_off;
+		__syncthreads();                                           /* the last picture's readers of comp are done */
+#pragma unroll
+		for (uint32_t i = 0; i < 4u; i++) reinterpret_cast<uint32_t *>(&comp[0][0])[tid + 256u * i] = fill4;
+		/* which cells meet the tile: the first wavefront, a cell per lane (JM_EM_MAX_CELLS is its 64 lanes) */
+		if (tid < 64u) {
+			bool meets = false;
+			if (tid < p.n && src_frames[(size_t)k * p.n + tid]) {
+				const JmEmCellRec &r = recs[tid];
+				const uint32_t dx = plane ? r.dx >> 1 : r.dx, dy = plane ? r.dy >> 1 : r.dy;
+				meets = max(dx, ox0) < min(dx + r.pl[ck].ax.n_out, ox0 + vw) && max(dy, oy0) < min(dy + r.pl[ck].ay.n_out, oy0 + vh);
+			}
+			const unsigned long long m = __ballot(meets);
+			if (tid == 0) { hit[0] = (uint32_t)m; hit[1] = (uint32_t)(m >> 32); }
+		}
+		__syncthreads();
+		uint32_t todo[2] = { (uint32_t)__builtin_amdgcn_readfirstlane((int)hit[0]), (uint32_t)__builtin_amdgcn_readfirstlane((int)hit[1]) };
+		for (uint32_t half = 0; half < 2u; half++) while (todo[half]) {
+			const uint32_t c = 32u * half + (uint32_t)__builtin_ctz(todo[half]);
+			todo[half] &= todo[half] - 1u;
+			const uint8_t *F = src_frames[(size_t)k * p.n + c];
+			const JmEmCellRec &rec = recs[c];
+			const JmEsPlane q = rec.pl[ck];
+			const uint32_t dx = plane ? rec.dx >> 1 : rec.dx, dy = plane ? rec.dy >> 1 : rec.dy;
+			/* the intersection of the cell and the tile's display samples, in plane coordinates: not empty */
+			const uint32_t ix0 = max(dx, ox0), ix1 = min(dx + q.ax.n_out, ox0 + vw);
+			const uint32_t iy0 = max(dy, oy0), iy1 = min(dy + q.ay.n_out, oy0 + vh);
+			const uint32_t cw = ix1 - ix0, chh = iy1 - iy0;        /* <= JM_ES_TW, JM_ES_TH */
+			const uint32_t lx0 = ix0 - dx, ly0 = iy0 - dy;         /* cell-local output indices of the intersection's corner */
+			const uint32_t tx0 = ix0 - ox0, ty0 = iy0 - oy0;       /* ... and where it lies in the tile */
+			const uint32_t *ex = tab + q.ent_x, *ey = tab + q.ent_y;
+			const uint16_t *wt = reinterpret_cast<const uint16_t *>(tab + rec.wts);
+			__syncthreads();                                       /* the last cell's readers of vt are done */
+			if (tid < chh) { vt[tid][0] = ey[2u * (ly0 + tid)]; vt[tid][1] = ey[2u * (ly0 + tid) + 1u]; }
+			const bool hcol = col < cw;
+			const uint32_t ci = lx0 + min(col, cw - 1u);
+			const uint32_t he = ex[2u * ci], hoff = ex[2u * ci + 1u], hsize = he >> 16;
+			const uint32_t ef = ex[2u * lx0], el = ex[2u * (lx0 + cw - 1u)];
+			const uint32_t vf = ey[2u * ly0], vl = ey[2u * (ly0 + chh - 1u)];
+			const uint32_t ax0 = (q.x0 + (ef & 0xffffu)) & ~(gran - 1u), ax1 = (q.x0 + (el & 0xffffu) + (el >> 16) + gran - 1u) & ~(gran - 1u);
+			const uint32_t stride = ax1 - ax0, cr_max = min(JM_ES_CR, JM_ES_SRC / stride);
+			const uint32_t sy0 = vf & 0xffffu, sy1 = (vl & 0xffffu) + (vl >> 16);
+			const uint32_t hbase = q.x0 - ax0 + (he & 0xffffu);
+			const uint32_t src_luma = rec.src_luma;
+			const uint32_t src_off = plane == 0 ? 0u : plane == 1 ? src_luma : src_luma + (src_luma >> 2);
+			const uint8_t *P = F + src_off + (size_t)q.y0 * q.src_w + ax0;
+			uint32_t acc[4][4] = {};
+			for (uint32_t r0 = sy0; r0 < sy1; r0 += cr_max) {
+				const uint32_t cn = min(cr_max, sy1 - r0);
+				__syncthreads();                                   /* the last chunk's readers are done */
+				if (plane == 0) {
+					const uint32_t gpr = stride / 16u;
+					for (uint32_t g = tid; g < cn * gpr; g += 256u) {
+						const uint32_t r = g / gpr, x = (g - r * gpr) * 16u;
+						*reinterpret_cast<uint4 *>(src + r * stride + x) = *reinterpret_cast<const uint4 *>(P + (size_t)(r0 + r) * q.src_w + x);
+					}
+				} else {
+					const uint32_t gpr = stride / 8u;
+					for (uint32_t g = tid; g < cn * gpr; g += 256u) {
+						const uint32_t r = g / gpr, x = (g - r * gpr) * 8u;
+						*reinterpret_cast<uint2 *>(src + r * stride + x) = *reinterpret_cast<const uint2 *>(P + (size_t)(r0 + r) * q.src_w + x);
+					}
+				}
+				__syncthreads();
+				if (hcol) {
+					uint32_t h[JM_ES_CR / 2u] = {};
+					for (uint32_t j = 0; j < hsize; j++) {
+						const uint32_t w = wt[hoff + j];
+#pragma unroll
+						for (uint32_t i = 0; i < JM_ES_CR / 2u; i++) h[i] += w * src[min(rg + 2u * i, cn - 1u) * stride + hbase + j];
+					}
+#pragma unroll
+					for (uint32_t i = 0; i < JM_ES_CR / 2u; i++)
+						if (rg + 2u * i < cn) ts[rg + 2u * i][col] = (uint16_t)jm_es_round_h(h[i]);
+				}
+				__syncthreads();
+				/* (columns of ts from cw up to the end of a thread's four were not written for this cell: what is summed from them
+				 * is dropped where the composed bytes are written) */
+#pragma unroll
+				for (uint32_t i = 0; i < 4u; i++) {
+					const uint32_t idx = tid + 256u * i, ol = idx / (JM_ES_TW / 4u), cg = idx % (JM_ES_TW / 4u);
+					if (ol >= chh || cg * 4u >= cw) continue;
+					const uint32_t xmin = vt[ol][0] & 0xffffu, xsize = vt[ol][0] >> 16, woff = vt[ol][1];
+					const uint32_t lo = max(xmin, r0), hi = min(xmin + xsize, r0 + cn);
+					for (uint32_t sr = lo; sr < hi; sr++) {
+						const uint32_t w = wt[woff + sr - xmin];
+						const uint2 v = *reinterpret_cast<const uint2 *>(&ts[sr - r0][cg * 4u]);
+						acc[i][0] += w * (v.x & 0xffffu); acc[i][1] += w * (v.x >> 16);
+						acc[i][2] += w * (v.y & 0xffffu); acc[i][3] += w * (v.y >> 16);
+					}
+				}
+			}
+			/* over the composed bytes (the cell before wrote them ahead of this cell's barriers) */
+#pragma unroll
+			for (uint32_t i = 0; i < 4u; i++) {
+				const uint32_t idx = tid + 256u * i, ol = idx / (JM_ES_TW / 4u), cg = idx % (JM_ES_TW / 4u);
+				if (ol >= chh || cg * 4u >= cw) continue;
+#pragma unroll
+				for (uint32_t j = 0; j < 4u; j++)
+					if (cg * 4u + j < cw) comp[ty0 + ol][tx0 + cg * 4u + j] = (uint8_t)jm_es_round_v(acc[i][j]);
+			}
+		}
+		__syncthreads();
+#pragma unroll
+		for (uint32_t i = 0; i < 4u; i++) {
+			const uint32_t idx = tid + 256u * i, ol = idx / (JM_ES_TW / 4u), x = (idx % (JM_ES_TW / 4u)) * 4u;
+			if (ol >= nh || x >= nw) continue;
+			const uint8_t *row = comp[min(ol, vh - 1u)];
+			const uint32_t v = x + 3u < vw ? *reinterpret_cast<const uint32_t *>(row + x)
+			                               : (uint32_t)row[min(x, vw - 1u)] | ((uint32_t)row[min(x + 1u, vw - 1u)] << 8) |
+			                                 ((uint32_t)row[min(x + 2u, vw - 1u)] << 16) | ((uint32_t)row[vw - 1u] << 24);
+			*reinterpret_cast<uint32_t *>(O + (size_t)(oy0 + ol) * out_w + ox0 + x) = v;
 		}
 	}
 }
@@ -494,6 +650,12 @@ struct jsmpeg_hip_encoder_t {
 	jsmpeg_hip_enc_source_t scale_key;            /* the geometry scale_plan and d_scale_tab were made for */
 	JmEsPlan scale_plan;
 	bool scale_have;
+	/* mosaic input (jsmpeg_hip_encoder_set_mosaic / _encode_mosaic; enc_mosaic.h), everything allocated by set_mosaic */
+	uint32_t *d_mosaic_tab;                       /* the layout's table */
+	uint32_t mosaic_tab_words;                    /* ... and what it holds at most */
+	const uint8_t **d_mosaic_src, **h_mosaic_src; /* [max_pictures][cells] frames; h_: pinned */
+	uint32_t mosaic_src_cells;                    /* the cells per picture they hold at most */
+	JmEmPlan mosaic_plan;                         /* mosaic_plan.n 0: no layout */
 	hipStream_t stream;
 	hipEvent_t ev[4], ev_done;
 	bool pending, valid, have_pass;
@@ -552,6 +714,8 @@ static void enc_free(jsmpeg_hip_encoder_t *e) {
 	hipFree(e->d_scale_tab); hipFree(e->d_scale_src);
 	if (e->h_scale_tab) hipHostFree(e->h_scale_tab);
 	if (e->h_scale_src) hipHostFree(e->h_scale_src);
+	hipFree(e->d_mosaic_tab); hipFree(e->d_mosaic_src);
+	if (e->h_mosaic_src) hipHostFree(e->h_mosaic_src);
 	for (hipEvent_t &v : e->ev) if (v) hipEventDestroy(v);
 	if (e->ev_done) hipEventDestroy(e->ev_done);
 	delete e;
@@ -846,7 +1010,7 @@ static int enc_run_gop(jsmpeg_hip_encoder_t *e, const JmEncArgs &a, uint32_t cou
 }
 
 static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const void *dev_rgb, uint32_t layout, uint32_t order,
-                   const jsmpeg_hip_enc_source_t *source, const uint32_t *stream, const uint8_t *qscale, uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream) {
+                   const jsmpeg_hip_enc_source_t *source, const void *const *cell_frames, const uint32_t *stream, const uint8_t *qscale, uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream) {
 	g_err[0] = 0;
 	if (!e) return fail("encoder: NULL handle");
 	if (e->pending) return fail("encoder: an encode is in flight: jsmpeg_hip_encoder_sync (or a reader) settles it first");
@@ -855,7 +1019,7 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 	if (have_pts && e->ts_pts.size() != count) return fail("encoder: %u pts values for a call of %u pictures", (unsigned)e->ts_pts.size(), count);
 	if (count > e->cfg.max_pictures) return fail("encoder: %u pictures > max_pictures %u", count, e->cfg.max_pictures);
 	if (flags & ~(JSMPEG_HIP_ENC_END | JSMPEG_HIP_ENC_CHAIN)) return fail("encoder: unknown flags 0x%x", flags);
-	if (count && !frames && !dev_rgb) return fail("encoder: NULL frames");
+	if (count && !frames && !dev_rgb && !cell_frames) return fail("encoder: NULL frames");
 	if (dev_rgb && (layout > JSMPEG_HIP_TENSOR_NHWC || order > JSMPEG_HIP_TENSOR_BGR)) return fail("encoder: layout %u / order %u unknown", layout, order);
 	if (!qscale && (quantiser_scale < 1 || quantiser_scale > 31)) return fail("encoder: quantiser_scale %u, must be 1 .. 31", quantiser_scale);
 	if (source) {
@@ -868,6 +1032,12 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 		if (qscale && (qscale[k] < 1 || qscale[k] > 31)) return fail("encoder: qscale[%u] = %u, must be 1 .. 31", k, qscale[k]);
 		if (stream && stream[k] >= e->cfg.max_streams) return fail("encoder: stream[%u] = %u >= max_streams %u", k, stream[k], e->cfg.max_streams);
 		if (stream && k && stream[k] < stream[k - 1]) return fail("encoder: stream[] must ascend (stream[%u] = %u after %u)", k, stream[k], stream[k - 1]);
+	}
+	if (cell_frames) {
+		if (!e->mosaic_plan.n) return fail("encoder: no mosaic layout is set (jsmpeg_hip_encoder_set_mosaic)");
+		for (uint64_t i = 0; i < (uint64_t)count * e->mosaic_plan.n; i++)
+			if ((uintptr_t)cell_frames[i] & 15u)
+				return fail("encoder: the frame of cell %u of picture %u is not 16-byte aligned", (unsigned)(i % e->mosaic_plan.n), (unsigned)(i / e->mosaic_plan.n));
 	}
 	HIP_TRY(hipSetDevice(e->device));
 	hipStream_t st = (hipStream_t)hip_stream;
@@ -938,6 +1108,12 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 		s.plan = e->scale_plan; s.src = e->d_scale_src; s.tab = e->d_scale_tab;
 		k_enc_scale<<<dim3(s.plan.tiles, std::min(count, 65535u)), dim3(256), 0, st>>>(a, s);
 	}
+	if (cell_frames) {
+		const size_t np = (size_t)count * e->mosaic_plan.n;        /* (no pass is in flight: the pinned pointers are free) */
+		for (size_t i = 0; i < np; i++) e->h_mosaic_src[i] = (const uint8_t *)cell_frames[i];
+		HIP_TRY(hipMemcpyAsync(e->d_mosaic_src, e->h_mosaic_src, sizeof(uint8_t *) * np, hipMemcpyHostToDevice, st));
+		k_enc_mosaic<<<dim3(e->mosaic_plan.tiles, std::min(count, 65535u)), dim3(256), 0, st>>>(a, e->mosaic_plan, e->d_mosaic_src, e->d_mosaic_tab);
+	}
 	HIP_TRY(hipEventRecord(e->ev[1], st));
 	e->pass_rate = rate;
 	e->pass_gop = level_loop;
@@ -965,7 +1141,7 @@ static int enc_run(jsmpeg_hip_encoder_t *e, const void *const *frames, const voi
 extern "C" int jsmpeg_hip_encoder_encode(jsmpeg_hip_encoder_t *e, const void *const *frames, const uint32_t *stream, const uint8_t *qscale,
                                          uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream) {
 	if (count && !frames) { g_err[0] = 0; return fail("encoder: NULL frames"); }
-	return enc_run(e, frames, nullptr, 0, 0, nullptr, stream, qscale, count, quantiser_scale, flags, hip_stream);
+	return enc_run(e, frames, nullptr, 0, 0, nullptr, nullptr, stream, qscale, count, quantiser_scale, flags, hip_stream);
 }
 
 extern "C" int jsmpeg_hip_encoder_encode_scaled(jsmpeg_hip_encoder_t *e, const void *const *frames, const jsmpeg_hip_enc_source_t *source,
@@ -973,13 +1149,67 @@ extern "C" int jsmpeg_hip_encoder_encode_scaled(jsmpeg_hip_encoder_t *e, const v
                                                 uint32_t flags, void *hip_stream) {
 	if (!source) { g_err[0] = 0; return fail("encoder: null source descriptor"); }
 	if (count && !frames) { g_err[0] = 0; return fail("encoder: NULL frames"); }
-	return enc_run(e, frames, nullptr, 0, 0, source, stream, qscale, count, quantiser_scale, flags, hip_stream);
+	return enc_run(e, frames, nullptr, 0, 0, source, nullptr, stream, qscale, count, quantiser_scale, flags, hip_stream);
 }
 
 extern "C" int jsmpeg_hip_encoder_encode_rgb(jsmpeg_hip_encoder_t *e, const void *dev_rgb, uint32_t layout, uint32_t order, const uint32_t *stream,
                                              const uint8_t *qscale, uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream) {
 	if (count && !dev_rgb) { g_err[0] = 0; return fail("encoder: NULL tensor"); }
-	return enc_run(e, nullptr, dev_rgb, layout, order, nullptr, stream, qscale, count, quantiser_scale, flags, hip_stream);
+	return enc_run(e, nullptr, dev_rgb, layout, order, nullptr, nullptr, stream, qscale, count, quantiser_scale, flags, hip_stream);
+}
+
+/* The layout of the mosaic input: checked, planned and uploaded here; a refusal leaves the layout before as it was */
+extern "C" int jsmpeg_hip_encoder_set_mosaic(jsmpeg_hip_encoder_t *e, const jsmpeg_hip_enc_cell_t *cells, uint32_t n_cells, uint32_t fill) {
+	g_err[0] = 0;
+	if (!e) return fail("encoder: NULL handle");
+	if (e->pending) return fail("encoder: an encode is in flight: jsmpeg_hip_encoder_sync (or a reader) settles it first");
+	if (n_cells == 0) { e->mosaic_plan.n = 0; return 0; }
+	const uint32_t W = (uint32_t)e->cfg.width, H = (uint32_t)e->cfg.height;
+	uint32_t cell;
+	if (const char *why = jm_em_check(cells, n_cells, fill, W, H, &cell))
+		return cell == 0xffffffffu ? fail("encoder: mosaic: %s", why) : fail("encoder: mosaic cell %u: %s", cell, why);
+	const JmEmPlan plan = jm_em_plan(cells, n_cells, fill, W, H);
+	if (plan.words > jm_em_table_bound(n_cells, W, H)) return fail("encoder: the mosaic table is larger than its bound");
+	if (!jm_em_tiles_ok(plan)) return fail("encoder: a mosaic tile without a display sample");
+	HIP_TRY(hipSetDevice(e->device));
+	/* what is missing is allocated beside what is there, and swapped in once nothing can fail any more */
+	uint32_t *d_tab = nullptr;
+	const uint8_t **d_src = nullptr, **h_src = nullptr;
+	const size_t np = (size_t)e->cfg.max_pictures * n_cells;
+	hipError_t r = hipSuccess;
+	if (plan.words > e->mosaic_tab_words) r = jm_malloc(&d_tab, 4 * (size_t)plan.words);
+	if (r == hipSuccess && n_cells > e->mosaic_src_cells) {
+		r = jm_malloc(&d_src, sizeof(uint8_t *) * np);
+		if (r == hipSuccess) r = hipHostMalloc(reinterpret_cast<void **>(&h_src), sizeof(uint8_t *) * np, hipHostMallocDefault);
+	}
+	if (r == hipSuccess && !e->d_store) r = jm_malloc(&e->d_store, (size_t)e->frame_bytes * e->cfg.max_pictures);
+	if (r == hipSuccess) {
+		std::vector<uint32_t> tab(plan.words);
+		jm_em_table(plan, cells, tab.data());
+		/* (the one exception to "a refusal leaves the layout before as it was": a table that fits the allocation in use is
+		 * copied over it, so if this copy itself fails -- the device is lost then -- the old layout's table is not whole either) */
+		r = hipMemcpy(d_tab ? d_tab : e->d_mosaic_tab, tab.data(), 4 * (size_t)plan.words, hipMemcpyHostToDevice);
+	}
+	if (r != hipSuccess) {
+		hipFree(d_tab); hipFree(d_src);
+		if (h_src) hipHostFree(h_src);
+		return fail("encoder: set_mosaic: %s", hipGetErrorString(r));
+	}
+	if (d_tab) { hipFree(e->d_mosaic_tab); e->d_mosaic_tab = d_tab; e->mosaic_tab_words = plan.words; }
+	if (d_src) {
+		hipFree(e->d_mosaic_src);
+		if (e->h_mosaic_src) hipHostFree(e->h_mosaic_src);
+		e->d_mosaic_src = d_src; e->h_mosaic_src = h_src; e->mosaic_src_cells = n_cells;
+	}
+	e->mosaic_plan = plan;
+	return 0;
+}
+
+extern "C" int jsmpeg_hip_encoder_encode_mosaic(jsmpeg_hip_encoder_t *e, const void *const *frames, const uint32_t *stream, const uint8_t *qscale,
+                                                uint32_t count, uint32_t quantiser_scale, uint32_t flags, void *hip_stream) {
+	static const void *const none[1] = { nullptr };
+	if (count && !frames) { g_err[0] = 0; return fail("encoder: NULL frames"); }
+	return enc_run(e, nullptr, nullptr, 0, 0, nullptr, frames ? frames : none, stream, qscale, count, quantiser_scale, flags, hip_stream);
 }
 
 extern "C" int jsmpeg_hip_encoder_sync(jsmpeg_hip_encoder_t *e) {

@@ -830,6 +830,26 @@ extern "C" int jsmpeg_hip_live_render_tensor_latest(jsmpeg_hip_live_t *l, const 
 	return 0;
 }
 
+/* The ring rule behind the promise in the header: live_assign_slots gives a stream's k-th picture of a tick the slot
+ * (head + 1 + k) % ring and a tick ends with head += its pictures, so slot `head` is written again by the stream's ring-th
+ * picture from here -- ring = max_pictures_per_tick + 2, a tick decodes at most ring - 2: never in the next tick. */
+extern "C" int jsmpeg_hip_live_latest_frames(jsmpeg_hip_live_t *l, const uint32_t *streams, uint32_t count, const void **device_frames) {
+	g_err[0] = 0;
+	if (!l) return fail("null live handle");
+	if (count == 0) return 0;
+	if (!streams || !device_frames) return fail("null argument");
+	if (live_settle(l) < 0) return -1;
+	for (uint32_t k = 0; k < count; k++) {
+		const uint32_t s = streams[k];
+		if (s >= l->streams.size() || !l->streams[s].open) return fail("latest_frames: stream %u is not open", s);
+	}
+	for (uint32_t k = 0; k < count; k++) {
+		const LiveStream &S = l->streams[streams[k]];
+		device_frames[k] = S.have ? l->b->d_pool + (uint64_t)(streams[k] * l->ring + S.head) * l->b->g.frame_bytes : nullptr;
+	}
+	return 0;
+}
+
 extern "C" int jsmpeg_hip_live_frame_hashes(jsmpeg_hip_live_t *l, uint64_t *out) {
 	g_err[0] = 0;
 	if (!l || !out) return fail("null argument");

@@ -3,7 +3,8 @@ the TS mux: on the device behind the pass (Encoder.set_ts), over any device byte
 -> elementary streams in a device buffer that Batch.attach_device takes as it is.  I pictures, or -- Encoder.set_gop -- I + P
 with motion search on the device and a closed loop; one quantiser scale per picture, the caller's or -- Encoder.set_rate --
 chosen on the device for a budget in bytes.  Frames of another size than the encoder's are cropped and scaled on the device,
-plane by plane (Encoder.encode_scaled: renditions).  torch is imported only when a tensor is handed in."""
+plane by plane (Encoder.encode_scaled: renditions), and many sources are composed into one picture the same way
+(Encoder.set_mosaic / encode_mosaic / encode_mosaic_latest: a wall of cameras).  torch is imported only when a tensor is handed in."""
 import ctypes
 
 import numpy as np
@@ -19,6 +20,7 @@ SYMBOLS = ("jsmpeg_hip_encoder_create", "jsmpeg_hip_encoder_destroy", "jsmpeg_hi
            "jsmpeg_hip_encoder_set_gop", "jsmpeg_hip_encoder_recon", "jsmpeg_hip_encoder_picture_stats",
            "jsmpeg_hip_encoder_set_rate", "jsmpeg_hip_encoder_picture_rate", "jsmpeg_hip_encoder_chain_reset", "jsmpeg_hip_encoder_chain_info",
            "jsmpeg_hip_encoder_encode_scaled", "jsmpeg_hip_encoder_source",
+           "jsmpeg_hip_encoder_set_mosaic", "jsmpeg_hip_encoder_encode_mosaic",
            "jsmpeg_hip_encoder_set_ts", "jsmpeg_hip_encoder_ts_pts", "jsmpeg_hip_encoder_ts", "jsmpeg_hip_encoder_ts_range",
            "jsmpeg_hip_encoder_ts_picture_range", "jsmpeg_hip_encoder_read_ts", "jsmpeg_hip_ts_bound", "jsmpeg_hip_ts_mux_device")
 
@@ -42,6 +44,32 @@ class EncoderConfig(ctypes.Structure):
 class EncSource(ctypes.Structure):
     """jsmpeg_hip_enc_source_t: the geometry of the frames an Encoder.encode_scaled call scales"""
     _fields_ = [(n, ctypes.c_uint32) for n in ("width", "height", "crop_x", "crop_y", "crop_width", "crop_height", "antialias")]
+
+
+class EncCell(ctypes.Structure):
+    """jsmpeg_hip_enc_cell_t: a cell of a mosaic layout -- the geometry of its frames and where they go in the picture"""
+    _fields_ = [("source", EncSource)] + [(n, ctypes.c_uint32) for n in ("x", "y", "width", "height")]
+
+
+def cell(source_size, x, y, width, height, crop=None, antialias=True):
+    """an EncCell: frames of source_size = (width, height), cropped as in Encoder.encode_scaled, scaled to width x height and
+    pasted at (x, y) -- both even -- of the encoder's picture"""
+    src = EncSource(int(source_size[0]), int(source_size[1]), *([int(v) for v in crop] if crop is not None else [0, 0, 0, 0]), 1 if antialias else 0)
+    return EncCell(src, int(x), int(y), int(width), int(height))
+
+
+def grid(cols, rows, size, source_size, gap=0, crop=None, antialias=True):
+    """the cells of a regular wall, row by row: cols x rows cells that share the `size` = (width, height) of the encoder's picture
+    equally, `gap` pixels of fill between neighbours (none around the wall).  A cell's width is (size[0] - gap * (cols - 1)) //
+    cols rounded DOWN to an even number, its x a multiple of width + gap (gap is rounded up to even), and the same for the rows:
+    what is left over stays fill at the right and bottom.  Every cell reads frames of source_size with the same crop."""
+    cols, rows, gap = int(cols), int(rows), (int(gap) + 1) & ~1
+    if cols < 1 or rows < 1:
+        raise ValueError("grid: %d x %d cells: at least one column and one row" % (cols, rows))
+    cw, ch = ((size[0] - gap * (cols - 1)) // cols) & ~1, ((size[1] - gap * (rows - 1)) // rows) & ~1
+    if cw < 2 or ch < 2:
+        raise ValueError("grid: %d x %d cells with a gap of %d do not fit %d x %d" % (cols, rows, gap, size[0], size[1]))
+    return [cell(source_size, c * (cw + gap), r * (ch + gap), cw, ch, crop, antialias) for r in range(rows) for c in range(cols)]
 
 
 _bound = None
@@ -90,6 +118,10 @@ def lib():
         L.jsmpeg_hip_encoder_chain_info.argtypes = [vp, u32, ctypes.POINTER(u32)]
         L.jsmpeg_hip_encoder_encode_scaled.restype = ctypes.c_int
         L.jsmpeg_hip_encoder_encode_scaled.argtypes = [vp, vp, ctypes.POINTER(EncSource), vp, vp, u32, u32, u32, vp]
+        L.jsmpeg_hip_encoder_set_mosaic.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_set_mosaic.argtypes = [vp, ctypes.POINTER(EncCell), u32, u32]
+        L.jsmpeg_hip_encoder_encode_mosaic.restype = ctypes.c_int
+        L.jsmpeg_hip_encoder_encode_mosaic.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp]
         L.jsmpeg_hip_encoder_source.restype = vp
         L.jsmpeg_hip_encoder_source.argtypes = [vp, u32]
         L.jsmpeg_hip_ts_mux_host.restype = ctypes.c_int64
@@ -196,6 +228,7 @@ class Encoder:
         self.device = device
         self.count = 0
         self._continuity = 0
+        self.cells = []             # the mosaic layout (set_mosaic)
 
     def _ok(self, rc):
         if rc < 0:
@@ -264,6 +297,59 @@ class Encoder:
         self._ok(self.L.jsmpeg_hip_encoder_encode_scaled(self.h, arr, ctypes.byref(src), None if s is None else s.ctypes.data,
                                                          None if q is None else q.ctypes.data, n, qs, self._flags(end, chain), stream))
         self.count = n
+
+    def set_mosaic(self, cells, fill=(16, 128, 128)):
+        """The layout of encode_mosaic: a list of EncCell (cell(), grid()), at most 64, and the fill colour (Y, Cr, Cb) of what
+        no cell covers.  Every plane is filled, then the cells are pasted in list order -- a later cell wins where they overlap
+        (picture in picture); bit for bit jsmpeg_amd/csrc/enc_mosaic.h.  State of the handle, like set_gop; an empty list
+        removes the layout.  Refused while a pass is in flight, and for a layout the rule does not cover: the layout before
+        stays then."""
+        cells = list(cells)
+        arr = (EncCell * max(1, len(cells)))(*cells)
+        y, cr, cb = (int(v) for v in fill)
+        if min(y, cr, cb) < 0 or max(y, cr, cb) > 255:
+            raise ValueError("fill: three bytes (Y, Cr, Cb)")
+        self._ok(self.L.jsmpeg_hip_encoder_set_mosaic(self.h, arr if cells else None, len(cells), y | cr << 8 | cb << 16))
+        self.cells = [EncCell.from_buffer_copy(c) for c in cells]
+
+    def encode_mosaic(self, frame_ptrs, streams=None, qscale=8, end=True, stream=None, chain=False, pts=None):
+        """encode() of pictures COMPOSED on the device from the layout's cells: frame_ptrs is a list of pictures, each a list
+        of one device address per cell -- Y | Cr | Cb planes of that cell's source's coded size, e.g. Live.latest_frames --
+        or None / 0 for a cell that is absent from that picture (what lies under it shows).  Everything else is
+        encode_scaled's; source(k) returns the composed planes."""
+        n, nc = len(frame_ptrs), len(self.cells)
+        flat = []
+        for k, pic in enumerate(frame_ptrs):
+            pic = list(pic)
+            if len(pic) != nc:
+                raise ValueError("encode_mosaic: picture %d has %d frame pointers, the layout has %d cells" % (k, len(pic), nc))
+            flat += [int(p) if p else 0 for p in pic]
+        arr = (ctypes.c_void_p * max(1, len(flat)))(*flat)
+        s, q, qs = self._lists(n, streams, qscale)
+        self._pts(pts)
+        self._ok(self.L.jsmpeg_hip_encoder_encode_mosaic(self.h, arr, None if s is None else s.ctypes.data, None if q is None else q.ctypes.data,
+                                                         n, qs, self._flags(end, chain), stream))
+        self.count = n
+
+    def encode_mosaic_latest(self, sources, streams=None, qscale=8, end=True, stream=None, chain=False, pts=None):
+        """ONE picture from the newest decoded picture of a live stream per cell: sources[c] = (live, stream id) -- the Lives
+        may differ, e.g. a router's Lives of several sizes; each must have the size of its cell's source.  A stream that has
+        decoded nothing yet leaves its cell absent.  Returns [present] per cell.  The frames hold their pictures through the
+        next tick of their Live (Live.latest_frames)."""
+        if len(sources) != len(self.cells):
+            raise ValueError("encode_mosaic_latest: %d sources, the layout has %d cells" % (len(sources), len(self.cells)))
+        by_live = {}
+        for c, (lv, sid) in enumerate(sources):
+            src = self.cells[c].source
+            if (lv.width, lv.height) != (src.width, src.height):
+                raise ValueError("encode_mosaic_latest: cell %d reads %d x %d frames, its live is %d x %d" % (c, src.width, src.height, lv.width, lv.height))
+            by_live.setdefault(id(lv), (lv, []))[1].append((c, int(sid)))
+        ptrs = [0] * len(sources)
+        for lv, want in by_live.values():
+            for (c, _), p in zip(want, lv.latest_frames([sid for _, sid in want])):
+                ptrs[c] = p or 0
+        self.encode_mosaic([ptrs], streams, qscale, end, stream, chain, pts)
+        return [bool(p) for p in ptrs]
 
     def _encode_from(self, ptrs, size, crop, antialias, streams, qscale, end, stream, chain, pts=None):
         """planes of `size`: straight in when that is the encoder's size and nothing is cropped, scaled otherwise"""

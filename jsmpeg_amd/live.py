@@ -14,7 +14,7 @@ LIVE_SYMBOLS = ("jsmpeg_hip_live_create", "jsmpeg_hip_live_destroy", "jsmpeg_hip
                 "jsmpeg_hip_live_write", "jsmpeg_hip_live_write_v", "jsmpeg_hip_live_write_ts", "jsmpeg_hip_live_tick", "jsmpeg_hip_live_tick_begin", "jsmpeg_hip_live_tick_end", "jsmpeg_hip_live_picture_count", "jsmpeg_hip_live_picture",
                 "jsmpeg_hip_live_geometry", "jsmpeg_hip_live_read_frame", "jsmpeg_hip_live_read_frames", "jsmpeg_hip_live_read_frames_begin", "jsmpeg_hip_live_read_frames_end", "jsmpeg_hip_live_read_rgba",
                 "jsmpeg_hip_host_alloc", "jsmpeg_hip_host_free", "jsmpeg_hip_host_register", "jsmpeg_hip_host_unregister",
-                "jsmpeg_hip_live_frame_hashes", "jsmpeg_hip_live_stream_info", "jsmpeg_hip_live_timings")
+                "jsmpeg_hip_live_frame_hashes", "jsmpeg_hip_live_stream_info", "jsmpeg_hip_live_timings", "jsmpeg_hip_live_latest_frames")
 
 
 class LiveConfig(ctypes.Structure):
@@ -87,6 +87,8 @@ def lib():
         L.jsmpeg_hip_live_frame_hashes.argtypes = [vp, vp]
         L.jsmpeg_hip_live_stream_info.restype = ctypes.c_int
         L.jsmpeg_hip_live_stream_info.argtypes = [vp, u32, ctypes.POINTER(LiveStreamInfo)]
+        L.jsmpeg_hip_live_latest_frames.restype = ctypes.c_int
+        L.jsmpeg_hip_live_latest_frames.argtypes = [vp, vp, u32, vp]
         L.jsmpeg_hip_live_timings.restype = ctypes.c_int
         L.jsmpeg_hip_live_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
         _bound = True
@@ -252,6 +254,16 @@ class Live:
                            self.device, self.width, self.height, count, size, crop, dtype, layout, order, antialias, mean, std,
                            out)
         return t, have[:count].astype(bool)
+
+    def latest_frames(self, streams):
+        """The device address of the NEWEST decoded picture of each listed stream (Y | Cr | Cb of the coded size, in the
+        stream's ring), from whichever tick decoded it, or None for a stream with no picture yet: what
+        Encoder.encode_mosaic takes.  The frame holds its picture until the stream has decoded pictures_per_tick + 1 more:
+        always through the next tick."""
+        ids = np.ascontiguousarray(list(streams), dtype=np.uint32)
+        out = (ctypes.c_void_p * max(1, ids.size))()
+        self._ok(self.L.jsmpeg_hip_live_latest_frames(self.h, ids.ctypes.data if ids.size else None, ids.size, out))
+        return [out[k] for k in range(ids.size)]
 
     def frame_hashes(self):
         n = self.picture_count
