@@ -1252,6 +1252,86 @@ int jsmpeg_hip_resample_plan(uint32_t in_rate, uint32_t out_rate, uint32_t *L, u
 /* its taps, L * 2 H floats [phase][tap], as the handle uploads them; no device needed */
 int jsmpeg_hip_resample_taps(uint32_t in_rate, uint32_t out_rate, float *out);
 
+/* ------------------------------------------------------------------ part 12
+ * LOG-MEL FEATURES ON THE DEVICE: the last step between decoded audio and a speech model.  Float32 mono PCM in HBM -- part 11's
+ * waveform, or any such buffer -- -> log-mel spectrograms [stream of the call][n_mels][row] (MEL_MAJOR, what Whisper reads) or
+ * [stream of the call][row][n_mels] (TIME_MAJOR) in f32 / f16 / bf16.  The rule is stated once, in jsmpeg_amd/csrc/logmel.h.
+ * In short: framing as torch.stft(center=True, pad_mode="reflect"), frame t covers [t hop - n_fft / 2, t hop + n_fft / 2); the
+ * DFT is a GEMM against a basis with the window folded in (computed in double, rounded once), re and im each ONE k-ascending
+ * float32 fmaf chain, done by v_mfma_f32_32x32x2_f32; power fmaf(re, re, im * im); mel sums in ascending bins; the header's own
+ * logarithm.  A stream that has taken n samples has n <= n_fft / 2 ? 0 : (n - n_fft / 2) / hop + 1 frames while it is open and
+ * n <= n_fft / 2 ? 0 : n / hop + 1 with END (torch refuses n <= n_fft / 2; here such a stream has no frame): CLOSED FORM, so a
+ * call is ONE kernel (WHISPER: two) and a PURE ENQUEUE on hip_stream with an event at its end.  Columns at and behind a
+ * stream's count hold the PAD VALUE, what a frame of zeros gets: 0 (POWER), the scale of floor (the logs), the stream's own
+ * lower clamp (WHISPER).  A stream handed over in pieces, chained call after chained call, yields BIT FOR BIT the frames of one
+ * call.  One pass at a time per handle; results are valid until the handle's next call.  A bad argument returns < 0 with
+ * jsmpeg_hip_last_error, launches nothing and leaves the handle usable.  Without a device create returns NULL (no CPU
+ * fallback).
+ * OUT OF SCOPE: a Node binding, the magnitude (square-root) spectrogram, deltas, dithering, pre-emphasis. */
+typedef struct jsmpeg_hip_logmel_t jsmpeg_hip_logmel_t;
+#define JSMPEG_HIP_LOGMEL_POWER 0u       /* the linear mel power */
+#define JSMPEG_HIP_LOGMEL_LOG 1u         /* ln max(mel, floor) */
+#define JSMPEG_HIP_LOGMEL_LOG10 2u       /* log10 max(mel, floor) */
+#define JSMPEG_HIP_LOGMEL_DB 3u          /* 10 log10 max(mel, floor) */
+#define JSMPEG_HIP_LOGMEL_WHISPER 4u     /* (max(log10 max(mel, floor), M - 8) + 4) / 4, M the stream's largest log10 value of the call */
+#define JSMPEG_HIP_LOGMEL_MEL_MAJOR 0u
+#define JSMPEG_HIP_LOGMEL_TIME_MAJOR 1u
+#define JSMPEG_HIP_LOGMEL_HTK 0u
+#define JSMPEG_HIP_LOGMEL_SLANEY 1u
+typedef struct jsmpeg_hip_logmel_config_t {
+	uint32_t sample_rate;         /* 8000 .. 48000 Hz: the filterbank's only */
+	uint32_t n_fft;               /* even, 32 .. 1024 */
+	uint32_t hop;                 /* 1 .. n_fft / 2 */
+	uint32_t n_mels;              /* 1 .. 256 */
+	float f_min, f_max;           /* Hz; f_max 0: sample_rate / 2 */
+	uint32_t mel_scale;           /* HTK or SLANEY */
+	uint32_t mel_norm;            /* 0: none; 1: slaney, every filter divided by half its width in Hz */
+	const float *window;          /* n_fft floats read at create; NULL: the periodic Hann window, computed in double */
+	float floor;                  /* the logs take max(mel, floor); 0: 1e-10 */
+	uint32_t scale, layout;
+	uint32_t dtype;               /* JSMPEG_HIP_RESAMPLE_F32 / _F16 / _BF16: the float32 value rounded to nearest even */
+	uint32_t max_streams;         /* per call, and the stream numbers of chained calls lie below it */
+	uint32_t max_samples;         /* samples of ONE stream per call */
+	uint32_t row;                 /* columns per stream of the output; 0: (max_samples + n_fft / 2) / hop + 2, what any call yields */
+	int32_t device;               /* -1: current */
+} jsmpeg_hip_logmel_config_t;
+/* the call's streams end here: indices behind a stream's last sample reflect, and the frames up to n / hop come out.  With
+ * CHAIN the chains of the call's streams end behind it; an END call with 0 new samples lets the tail frames come out. */
+#define JSMPEG_HIP_LOGMEL_END 1u
+/* CONTINUE the call's streams: the handle keeps, per stream number, whether the stream has state, the samples it has taken,
+ * and which of two carries on the device holds the samples that later frames and END's reflection can still read (at most
+ * n_fft - 1; the exact rule: logmel.h).  A call reads one carry and writes the other.  A stream without samples in a call
+ * keeps its state; a call without the flag starts from nothing and stores nothing.  Refused with the WHISPER scale, whose
+ * maximum belongs to a whole call. */
+#define JSMPEG_HIP_LOGMEL_CHAIN 2u
+jsmpeg_hip_logmel_t *jsmpeg_hip_logmel_create(const jsmpeg_hip_logmel_config_t *config);
+void jsmpeg_hip_logmel_destroy(jsmpeg_hip_logmel_t *lm);
+/* stream i has samples[i] (0 allowed) float32 samples at the device address pcm[i] (4-byte aligned; ignored for 0 samples) and
+ * the number stream_numbers[i] (strictly ascending, below max_streams; NULL: i) */
+int jsmpeg_hip_logmel_features(jsmpeg_hip_logmel_t *lm, const void *const *pcm, const uint32_t *samples, const uint32_t *stream_numbers, uint32_t n_streams,
+                               uint32_t flags, void *hip_stream);
+int jsmpeg_hip_logmel_sync(jsmpeg_hip_logmel_t *lm);
+/* 1: no pass in flight, 0: still running; never waits */
+int jsmpeg_hip_logmel_query(jsmpeg_hip_logmel_t *lm);
+/* the last call's buffer on the device and its bytes (streams of the call * n_mels * row elements): closed form, NO wait */
+void *jsmpeg_hip_logmel_out(jsmpeg_hip_logmel_t *lm, uint64_t *bytes);
+/* stream NUMBER `stream` in that buffer (0, 0: not in the call): the element index of its first row and its frames.  No wait. */
+int jsmpeg_hip_logmel_stream_out(jsmpeg_hip_logmel_t *lm, uint32_t stream, uint64_t *offset, uint64_t *count);
+/* ends the chain of `stream` (UINT32_MAX: of every stream); refused while a pass is in flight */
+int jsmpeg_hip_logmel_chain_reset(jsmpeg_hip_logmel_t *lm, uint32_t stream);
+/* out[0]: the stream has chain state; out[1]: samples it has taken; out[2]: frames it has made */
+int jsmpeg_hip_logmel_chain_info(jsmpeg_hip_logmel_t *lm, uint32_t stream, uint64_t out[3]);
+/* the last pass on the device: the kernels, the whole enqueue (with the upload of its stream list) */
+int jsmpeg_hip_logmel_timings(jsmpeg_hip_logmel_t *lm, float out_ms[2]);
+/* The tables of a config, no device needed (max_streams, max_samples and device are not looked at).
+ * plan: out = { bins, padded columns of the basis, frames of n samples open, frames of n samples with END, frames per
+ * workgroup, LDS bytes of a workgroup, floats per carry, row }. */
+int jsmpeg_hip_logmel_plan(const jsmpeg_hip_logmel_config_t *config, uint64_t n, uint64_t out[8]);
+/* the basis as the handle uploads it: [n_fft][padded columns], column 2 b = w cos, 2 b + 1 = -w sin, zeros behind 2 bins */
+int jsmpeg_hip_logmel_basis(const jsmpeg_hip_logmel_config_t *config, float *out);
+/* the filterbank [n_mels][bins] and the ranges [n_mels][2] = lo, hi of each row's nonzero span (either may be NULL) */
+int jsmpeg_hip_logmel_filters(const jsmpeg_hip_logmel_config_t *config, float *fb, int32_t *ranges);
+
 /* Last error of the calling thread ("" if none). */
 const char *jsmpeg_hip_last_error(void);
 /* Number of visible HIP devices (0 if none / runtime unusable). */

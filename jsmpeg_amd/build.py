@@ -113,7 +113,7 @@ def check_kernel_resources():
     import re
     usage, name = {}, None
     out = ""
-    for f in ("kernels.hip", "ts_kernels.hip", "mp2_stage.hip", "encode.hip", "mp2_encode.hip", "ts_program.hip", "pcm_resample.hip"):
+    for f in ("kernels.hip", "ts_kernels.hip", "mp2_stage.hip", "encode.hip", "mp2_encode.hip", "ts_program.hip", "pcm_resample.hip", "logmel.hip"):
         src = os.path.join(CSRC, f)
         out += subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"),
                                "-I", CSRC, "--cuda-device-only", "-c", src, "-o", os.devnull,
