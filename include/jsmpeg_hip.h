@@ -782,6 +782,42 @@ int jsmpeg_hip_live_render_tensor_latest(jsmpeg_hip_live_t *l, const uint32_t *s
                                          const jsmpeg_hip_tensor_desc_t *desc, void *dev_out, void *hip_stream,
                                          uint8_t *have);
 
+/* Per-box crops: tensor rows from REGIONS OF INTEREST that lie in device memory (a detector's boxes in front of a classifier,
+ * re-identifier, OCR or face model), with no host wait in between (kernel k_tensor_roi; the rule: jm_roi_clip in tensor_plan.h).
+ * Output row r is made from rois[r]: a box of display pixels in picture pictures[row] of the call (streams[row] for the latest
+ * call).  The box is clipped to the picture, [0, width) x [0, height), in 64-bit arithmetic -- x = width = INT32_MAX is an
+ * ordinary box -- and the row's status says what became of it:
+ *   0  empty: row outside 0 .. count-1, width <= 0, height <= 0, no overlap with the picture, or no picture there (a live stream
+ *      that has no frame yet).  Every byte of the output row is zero;
+ *   1  the box lies inside the picture as given;
+ *   2  the box was clipped to the picture.
+ * For status 1 and 2 the row is EXACTLY what jsmpeg_hip_*_render_tensor gives for that picture with crop = the clipped box:
+ * the same RGB, taps, pass order, value, dtype, layout and order, bit for bit.  A bad box is never an error: it is device data
+ * that the host has not seen.  What the host can see keeps part 7's errors, with nothing launched: the descriptor, the picture
+ * or stream indices, undecoded pictures -- and a descriptor whose own crop fields are not 0 (crop and rois exclude each other).
+ *   dev_rois    DEVICE pointer, n_rois boxes, 4-byte aligned.  They must be READY ON hip_stream: written by earlier work on
+ *               that stream, or by work it has been made to wait for; they are read by the kernel, never by the host;
+ *   dev_out     n_rois rows of desc->width x desc->height (desc->layout, desc->dtype);
+ *   dev_status  DEVICE pointer, n_rois bytes, or NULL: nothing is written.
+ * The rest is part 7's contract: an enqueued pass is settled first, hip_stream waits for the pool's last writer, and the next
+ * decode, enqueue or tick waits for the render.  n_rois 0: returns 0, launches nothing.  Not covered: aspect-preserving
+ * letterbox or fill, rotated boxes, sub-pixel (roi_align) sampling. */
+typedef struct jsmpeg_hip_roi_t {
+	int32_t row;                              /* index into the call's picture (or stream) list */
+	int32_t x, y, width, height;              /* display pixels */
+} jsmpeg_hip_roi_t;
+enum { JSMPEG_HIP_ROI_EMPTY = 0, JSMPEG_HIP_ROI_INSIDE = 1, JSMPEG_HIP_ROI_CLIPPED = 2 };
+int jsmpeg_hip_batch_render_tensor_rois(jsmpeg_hip_batch_t *b, const uint32_t *pictures, uint32_t count,
+                                        const jsmpeg_hip_tensor_desc_t *desc, const jsmpeg_hip_roi_t *dev_rois, uint32_t n_rois,
+                                        void *dev_out, uint8_t *dev_status, void *hip_stream);
+int jsmpeg_hip_live_render_tensor_rois(jsmpeg_hip_live_t *l, const uint32_t *pictures, uint32_t count,
+                                       const jsmpeg_hip_tensor_desc_t *desc, const jsmpeg_hip_roi_t *dev_rois, uint32_t n_rois,
+                                       void *dev_out, uint8_t *dev_status, void *hip_stream);
+/* have[k] (may be NULL): stream streams[k] has a frame; the boxes of one that has none get status 0 */
+int jsmpeg_hip_live_render_tensor_rois_latest(jsmpeg_hip_live_t *l, const uint32_t *streams, uint32_t count,
+                                              const jsmpeg_hip_tensor_desc_t *desc, const jsmpeg_hip_roi_t *dev_rois, uint32_t n_rois,
+                                              void *dev_out, uint8_t *dev_status, void *hip_stream, uint8_t *have);
+
 /* ------------------------------------------------------------------ part 8
  * The way back: an MPEG-1 ENCODER on the device, I pictures and -- with a GOP, jsmpeg_hip_encoder_set_gop -- I + P.  Frames in HBM (a pool slot, a live picture's device_frame, the caller's
  * own planes) or RGB tensors -> elementary streams that a jsmpeg player, the reference decoder and parts 2 and 5 of this header

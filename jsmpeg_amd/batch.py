@@ -303,6 +303,21 @@ class Batch:
                               self.device, self.width, self.height, count, size, crop, dtype, layout, order, antialias, mean,
                               std, out)
 
+    def tensor_rois(self, rois, pictures=None, size=None, dtype=None, layout="nchw", order="rgb", antialias=True, mean=None,
+                    std=None, out=None):
+        """Per-box crops in ONE call: row r of the tensor is box rois[r] = (row, x, y, width, height) -- display pixels of
+        picture pictures[row] (None: all pictures of the last decode) -- clipped to the picture and resized to size
+        (height, width; required), exactly as tensor([that picture], crop=clipped box, ...) gives it.  rois: an int32 CUDA
+        tensor [R, 5] on the batch's device is read in place by the kernel on torch's current stream -- a detector's output
+        goes in with no host step (tensor.rois_from_xyxy) -- anything else array-like is copied there.  Returns
+        (tensor, status): status a uint8 device tensor [R], 0 = no picture area (empty or outside box, row out of range: the
+        row is all zeros), 1 = inside, 2 = clipped.  A bad box is never an error; the other arguments keep tensor()'s."""
+        idx, count = _tensor.indices(pictures, self.picture_count if pictures is None else 0)
+        ptr = idx.ctypes.data if idx is not None else None
+        return _tensor.render_rois(
+            lambda d, r, n, o, s, st: self._ok(self.L.jsmpeg_hip_batch_render_tensor_rois(self.h, ptr, count, d, r, n, o, s, st)),
+            self.device, self.width, self.height, rois, size, dtype, layout, order, antialias, mean, std, out)
+
     def read_rgba(self, p):
         """Picture p as RGBA uint8[height, width, 4]: device conversion, then a copy to the host."""
         out = np.empty((self.height, self.width, 4), dtype=np.uint8)

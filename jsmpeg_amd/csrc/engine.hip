@@ -1189,6 +1189,11 @@ extern "C" int jsmpeg_hip_batch_render_rgba(jsmpeg_hip_batch_t *b, uint32_t firs
 
 int batch_render_tensor(jsmpeg_hip_batch_t *b, const uint32_t *slots, uint32_t count, const jsmpeg_hip_tensor_desc_t *desc,
                         void *dev_out, hipStream_t st) {
+	return batch_render_tensor_rois(b, slots, count, desc, nullptr, 0, dev_out, nullptr, st);
+}
+
+int batch_render_tensor_rois(jsmpeg_hip_batch_t *b, const uint32_t *slots, uint32_t count, const jsmpeg_hip_tensor_desc_t *desc,
+                             const jsmpeg_hip_roi_t *dev_rois, uint32_t n_rois, void *dev_out, uint8_t *dev_status, hipStream_t st) {
 	HIP_TRY(hipSetDevice(b->device));
 	if (!b->ev_pool) {
 		HIP_TRY(hipEventCreateWithFlags(&b->ev_pool, hipEventDisableTiming));
@@ -1208,16 +1213,23 @@ int batch_render_tensor(jsmpeg_hip_batch_t *b, const uint32_t *slots, uint32_t c
 		HIP_TRY(jm_malloc(&s->d, sizeof(uint32_t) * cap));
 		s->cap = (uint32_t)std::min<uint64_t>(cap, 0xffffffffu);
 	}
-	memcpy(s->h, slots, sizeof(uint32_t) * count);
+	if (count) memcpy(s->h, slots, sizeof(uint32_t) * count);
 	/* in: the frames are written on the decode's stream; the renders since the last decode are one chain (ev_tensor covers all) */
 	HIP_TRY(hipEventRecord(b->ev_pool, b->stream));
 	HIP_TRY(hipStreamWaitEvent(st, b->ev_pool, 0));
 	if (b->tensor_pending) HIP_TRY(hipStreamWaitEvent(st, b->ev_tensor, 0));
-	HIP_TRY(hipMemcpyAsync(s->d, s->h, sizeof(uint32_t) * count, hipMemcpyHostToDevice, st));
+	if (count) HIP_TRY(hipMemcpyAsync(s->d, s->h, sizeof(uint32_t) * count, hipMemcpyHostToDevice, st));
 	JmTensorBufs tb;
 	tb.pool = b->d_pool; tb.frame_bytes = b->g.frame_bytes; tb.luma_bytes = b->g.luma_bytes; tb.chroma_bytes = b->g.chroma_bytes;
 	tb.coded_width = b->g.coded_width; tb.slots = s->d; tb.count = count; tb.out = dev_out;
-	HIP_TRY(jm_launch_tensor(tb, jm_tensor_plan(desc, (uint32_t)b->cfg.width, (uint32_t)b->cfg.height), st));
+	const JmTensorPlan plan = jm_tensor_plan(desc, (uint32_t)b->cfg.width, (uint32_t)b->cfg.height);
+	if (dev_rois) {
+		JmTensorRois q;
+		q.rois = dev_rois; q.n_rois = n_rois; q.status = dev_status; q.w = (uint32_t)b->cfg.width; q.h = (uint32_t)b->cfg.height;
+		HIP_TRY(jm_launch_tensor_roi(tb, plan, q, st));
+	} else {
+		HIP_TRY(jm_launch_tensor(tb, plan, st));
+	}
 	/* out: the next decode, enqueue or tick waits for this on its own stream */
 	HIP_TRY(hipEventRecord(s->done, st));
 	HIP_TRY(hipEventRecord(b->ev_tensor, st));
@@ -1243,6 +1255,29 @@ extern "C" int jsmpeg_hip_batch_render_tensor(jsmpeg_hip_batch_t *b, const uint3
 	HIP_TRY(hipSetDevice(b->device));
 	if (batch_settle_pending(b) < 0) return -1;
 	return batch_render_tensor(b, slots.data(), count, desc, dev_out, (hipStream_t)hip_stream);
+}
+
+/* ... and rows from regions of interest in device memory (k_tensor_roi): what the host can see is checked as above, the boxes
+ * are the kernel's to judge */
+extern "C" int jsmpeg_hip_batch_render_tensor_rois(jsmpeg_hip_batch_t *b, const uint32_t *pictures, uint32_t count,
+                                                   const jsmpeg_hip_tensor_desc_t *desc, const jsmpeg_hip_roi_t *dev_rois, uint32_t n_rois,
+                                                   void *dev_out, uint8_t *dev_status, void *hip_stream) {
+	g_err[0] = 0;
+	if (!b) return fail("null batch");
+	if (n_rois == 0) return 0;
+	if (!desc || !dev_rois || !dev_out) return fail("null argument");
+	if (batch_settle_enqueued(b) < 0) return -1;
+	if (const char *m = jm_tensor_roi_check(desc, (uint32_t)b->cfg.width, (uint32_t)b->cfg.height)) return fail("render_tensor_rois: %s", m);
+	std::vector<uint32_t> slots(count);
+	for (uint32_t k = 0; k < count; k++) {
+		const uint32_t p = pictures ? pictures[k] : k;
+		if (p >= b->n_pics) return fail("render_tensor_rois: picture %u outside the %u pictures of the last decode", p, b->n_pics);
+		if (!b->h_pics[p].decoded) return fail("render_tensor_rois: picture %u was not decoded (picture_info.decoded 0)", p);
+		slots[k] = b->slot.empty() ? p : b->slot[p];
+	}
+	HIP_TRY(hipSetDevice(b->device));
+	if (batch_settle_pending(b) < 0) return -1;
+	return batch_render_tensor_rois(b, slots.data(), count, desc, dev_rois, n_rois, dev_out, dev_status, (hipStream_t)hip_stream);
 }
 
 /* The same in the reference's WebGL renderer's arithmetic (src/webgl.js:259-281). */

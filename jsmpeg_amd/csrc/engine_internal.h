@@ -160,6 +160,10 @@ struct jsmpeg_hip_batch_t {
 /* part 7: rows of pool slots (JM_NONE: a row of zeros) -> a tensor on `st`; the descriptor has passed jm_tensor_check */
 int batch_render_tensor(jsmpeg_hip_batch_t *b, const uint32_t *slots, uint32_t count, const jsmpeg_hip_tensor_desc_t *desc,
                         void *dev_out, hipStream_t st);
+/* ... with dev_rois (device memory, ready on `st`): a row per region of interest of those slots, n_rois rows, their status to
+ * dev_status (or null); the descriptor has passed jm_tensor_roi_check.  dev_rois null: batch_render_tensor. */
+int batch_render_tensor_rois(jsmpeg_hip_batch_t *b, const uint32_t *slots, uint32_t count, const jsmpeg_hip_tensor_desc_t *desc,
+                             const jsmpeg_hip_roi_t *dev_rois, uint32_t n_rois, void *dev_out, uint8_t *dev_status, hipStream_t st);
 /* ... and the wait of a stream that is about to write the pool for the renders since the last one */
 static inline int batch_wait_tensor(jsmpeg_hip_batch_t *b, hipStream_t st) {
 	if (!b->tensor_pending) return 0;

@@ -225,6 +225,16 @@ struct JmTensorBufs {
 	void *out;                   /* [count] rows of 3 * out_w * out_h elements */
 };
 hipError_t jm_launch_tensor(const JmTensorBufs &b, const JmTensorPlan &p, hipStream_t st);
+/* ... and a row per region of interest: row r is box rois[r] of pool slot slots[rois[r].row], clipped by jm_roi_clip to the
+ * w x h display picture; `p`: the descriptor's plan with no crop (the box gives each row its own, jm_tensor_roi_plan).  Here
+ * b.count is the length of the slot list and b.out holds n_rois rows. */
+struct JmTensorRois {
+	const jsmpeg_hip_roi_t *rois;    /* device [n_rois], read by the kernel only */
+	uint32_t n_rois;
+	uint8_t *status;                 /* device [n_rois] JSMPEG_HIP_ROI_*, or null */
+	uint32_t w, h;
+};
+hipError_t jm_launch_tensor_roi(const JmTensorBufs &b, const JmTensorPlan &p, const JmTensorRois &q, hipStream_t st);
 
 /* ---- ingest side: MPEG-TS -> elementary streams (ts_kernels.hip; reference src/ts.js) ---- */
 struct JmTsRec {                 /* what one 188-byte packet says by itself, 16 bytes */

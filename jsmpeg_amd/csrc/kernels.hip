@@ -1634,3 +1634,122 @@ hipError_t jm_launch_tensor(const JmTensorBufs &b, const JmTensorPlan &p, hipStr
 	hipLaunchKernelGGL(k_tensor, dim3(tiles_x * tiles_y, min(b.count, 65535u)), dim3(JM_WG), 0, st, b, p, tiles_x);
 	return hipGetLastError();
 }
+
+/* Rows from regions of interest: k_tensor's tile body with the geometry of every row read from device memory.  What k_tensor
+ * works out once per workgroup -- the axes, the lane's taps, the tile's source rectangle, vt[], cr_max -- depends on the row's
+ * clipped box here and is computed inside the row loop (jm_roi_clip, jm_tensor_roi_plan: the simulator's functions).  vt[] and
+ * the staging buffers are rewritten per row, so a barrier holds the row's first write behind the last row's readers.  A
+ * sibling of k_tensor, not a shared body: k_tensor keeps its geometry outside its loop, and its code stays as measured. */
+__global__ __launch_bounds__(JM_WG) void k_tensor_roi(JmTensorBufs b, JmTensorPlan p0, JmTensorRois q, uint32_t tiles_x) {
+	__shared__ uint32_t src[JM_TT_SRC];
+	__shared__ float hs[3][JM_TT_CR][JM_TT_W];
+	__shared__ JmTaps vt[JM_TT_H];
+	const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+	const uint32_t ox0 = (blockIdx.x % tiles_x) * JM_TT_W, oy0 = (blockIdx.x / tiles_x) * JM_TT_H;
+	const uint32_t nw = min(JM_TT_W, p0.out_w - ox0), nh = min(JM_TT_H, p0.out_h - oy0);
+	const bool col = lane < nw;
+	const uint32_t cw = (uint32_t)b.coded_width;
+	const uint64_t plane = (uint64_t)p0.out_w * p0.out_h;
+	for (uint32_t k = blockIdx.y; k < q.n_rois; k += gridDim.y) {
+		const jsmpeg_hip_roi_t roi = q.rois[k];
+		const JmRoiClip clip = jm_roi_clip(roi, b.count, q.w, q.h);
+		const uint32_t slot = clip.status != JSMPEG_HIP_ROI_EMPTY ? b.slots[roi.row] : JM_NONE;      /* (row checked by the clip) */
+		if (q.status && blockIdx.x == 0 && threadIdx.x == 0) q.status[k] = slot != JM_NONE ? (uint8_t)clip.status : (uint8_t)JSMPEG_HIP_ROI_EMPTY;
+		float acc[4][3] = {};
+		if (slot != JM_NONE) {                                     /* (the same for the whole workgroup) */
+			const JmTensorPlan p = jm_tensor_roi_plan(p0, clip);
+			__syncthreads();                                       /* the last row's readers of vt[] are done */
+			if (threadIdx.x < nh) vt[threadIdx.x] = jm_tp_taps(p.ay, (int32_t)(oy0 + threadIdx.x));
+			const JmTaps ht = jm_tp_taps(p.ax, (int32_t)(ox0 + min(lane, nw - 1)));
+			/* the tile's source rectangle in this row's box: columns 16-aligned in the coded row */
+			const JmTaps hf = jm_tp_taps(p.ax, (int32_t)ox0), hl = jm_tp_taps(p.ax, (int32_t)(ox0 + nw - 1));
+			const JmTaps vf = jm_tp_taps(p.ay, (int32_t)oy0), vl = jm_tp_taps(p.ay, (int32_t)(oy0 + nh - 1));
+			const uint32_t ax0 = (p.crop_x + (uint32_t)hf.xmin) & ~15u, ax1 = (p.crop_x + (uint32_t)(hl.xmin + hl.xsize) + 15u) & ~15u;
+			const uint32_t stride = ax1 - ax0, gpr = stride / 16u;
+			const uint32_t cr_max = min(JM_TT_CR, JM_TT_SRC / stride);
+			const int32_t sy0 = vf.xmin, sy1 = vl.xmin + vl.xsize;
+			const int32_t hbase = (int32_t)(p.crop_x - ax0) + ht.xmin;
+			const uint8_t *Y = b.pool + (uint64_t)slot * b.frame_bytes, *Cr = Y + b.luma_bytes, *Cb = Cr + b.chroma_bytes;
+			for (int32_t r0 = sy0; r0 < sy1; r0 += (int32_t)cr_max) {
+				const uint32_t cn = min(cr_max, (uint32_t)(sy1 - r0));
+				__syncthreads();                                   /* the last chunk's (or row's) readers are done; vt[] is written */
+				for (uint32_t g = threadIdx.x; g < cn * gpr; g += JM_WG) {
+					const uint32_t r = g / gpr, x = ax0 + (g - r * gpr) * 16u, y = p.crop_y + (uint32_t)r0 + r;
+					const uint4 yv = *reinterpret_cast<const uint4 *>(Y + (size_t)y * cw + x);
+					const uint2 crv = *reinterpret_cast<const uint2 *>(Cr + (size_t)(y >> 1) * (cw >> 1) + (x >> 1));
+					const uint2 cbv = *reinterpret_cast<const uint2 *>(Cb + (size_t)(y >> 1) * (cw >> 1) + (x >> 1));
+					const uint32_t yw[4] = { yv.x, yv.y, yv.z, yv.w }, crw[2] = { crv.x, crv.y }, cbw[2] = { cbv.x, cbv.y };
+					uint32_t px[16];
+#pragma unroll
+					for (int i = 0; i < 16; i++)
+						px[i] = jm_tp_rgb((int)((yw[i >> 2] >> (8 * (i & 3))) & 255u), (int)((crw[i >> 3] >> (8 * ((i >> 1) & 3))) & 255u),
+						                  (int)((cbw[i >> 3] >> (8 * ((i >> 1) & 3))) & 255u));
+					uint4 *d = reinterpret_cast<uint4 *>(src + r * stride + (x - ax0));
+#pragma unroll
+					for (int i = 0; i < 4; i++) d[i] = make_uint4(px[4 * i], px[4 * i + 1], px[4 * i + 2], px[4 * i + 3]);
+				}
+				__syncthreads();
+				if (col) {
+					float h[4][3] = {};
+					uint32_t rb[4];
+#pragma unroll
+					for (int i = 0; i < 4; i++) rb[i] = min(wv + 4u * i, cn - 1u) * stride + (uint32_t)hbase;
+					for (int32_t j = 0; j < ht.xsize; j++) {
+						const float w = jm_tp_weight(p.ax, ht, j);
+#pragma unroll
+						for (int i = 0; i < 4; i++) {
+							const uint32_t v = src[rb[i] + (uint32_t)j];
+							h[i][0] += w * (float)(v & 255u); h[i][1] += w * (float)((v >> 8) & 255u); h[i][2] += w * (float)((v >> 16) & 255u);
+						}
+					}
+#pragma unroll
+					for (int i = 0; i < 4; i++)
+						if (wv + 4u * i < cn)
+							for (int c = 0; c < 3; c++) hs[c][wv + 4u * i][lane] = h[i][c];
+				}
+				__syncthreads();
+				if (col) {
+#pragma unroll
+					for (int i = 0; i < 4; i++) {
+						const uint32_t ol = wv + 4u * i;
+						if (ol >= nh) continue;
+						const JmTaps t = vt[ol];
+						const int32_t lo = max(t.xmin, r0), hi = min(t.xmin + t.xsize, r0 + (int32_t)cn);
+						for (int32_t sr = lo; sr < hi; sr++) {
+							const float w = jm_tp_weight(p.ay, t, sr - t.xmin);
+#pragma unroll
+							for (int c = 0; c < 3; c++) acc[i][c] += w * hs[c][sr - r0][lane];
+						}
+					}
+				}
+			}
+		}
+		if (!col) continue;
+#pragma unroll
+		for (int i = 0; i < 4; i++) {
+			const uint32_t ol = wv + 4u * i;
+			if (ol >= nh) continue;
+			const uint64_t oy = oy0 + ol, ox = ox0 + lane;
+#pragma unroll
+			for (int c = 0; c < 3; c++) {
+				const int oc = p0.order == JSMPEG_HIP_TENSOR_BGR ? 2 - c : c;
+				const uint64_t idx = p0.layout == JSMPEG_HIP_TENSOR_NCHW ? ((uint64_t)k * 3 + oc) * plane + oy * p0.out_w + ox
+				                                                          : (((uint64_t)k * p0.out_h + oy) * p0.out_w + ox) * 3 + oc;
+				if (slot == JM_NONE) {
+					if (p0.dtype == JSMPEG_HIP_TENSOR_U8) reinterpret_cast<uint8_t *>(b.out)[idx] = 0;
+					else if (p0.dtype == JSMPEG_HIP_TENSOR_F32) reinterpret_cast<uint32_t *>(b.out)[idx] = 0;
+					else reinterpret_cast<uint16_t *>(b.out)[idx] = 0;
+				} else {
+					jm_tt_store(p0, b.out, idx, oc, acc[i][c]);
+				}
+			}
+		}
+	}
+}
+
+hipError_t jm_launch_tensor_roi(const JmTensorBufs &b, const JmTensorPlan &p, const JmTensorRois &q, hipStream_t st) {
+	if (q.n_rois == 0) return hipSuccess;
+	const uint32_t tiles_x = (p.out_w + JM_TT_W - 1) / JM_TT_W, tiles_y = (p.out_h + JM_TT_H - 1) / JM_TT_H;
+	hipLaunchKernelGGL(k_tensor_roi, dim3(tiles_x * tiles_y, min(q.n_rois, 65535u)), dim3(JM_WG), 0, st, b, p, q, tiles_x);
+	return hipGetLastError();
+}

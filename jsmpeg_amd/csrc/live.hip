@@ -830,6 +830,48 @@ extern "C" int jsmpeg_hip_live_render_tensor_latest(jsmpeg_hip_live_t *l, const 
 	return 0;
 }
 
+/* ... and rows from regions of interest in device memory (engine.hip batch_render_tensor_rois) */
+extern "C" int jsmpeg_hip_live_render_tensor_rois(jsmpeg_hip_live_t *l, const uint32_t *pictures, uint32_t count,
+                                                  const jsmpeg_hip_tensor_desc_t *desc, const jsmpeg_hip_roi_t *dev_rois, uint32_t n_rois,
+                                                  void *dev_out, uint8_t *dev_status, void *hip_stream) {
+	g_err[0] = 0;
+	if (!l) return fail("null live handle");
+	if (n_rois == 0) return 0;
+	if (!desc || !dev_rois || !dev_out) return fail("null argument");
+	if (live_settle(l) < 0) return -1;
+	if (const char *m = jm_tensor_roi_check(desc, (uint32_t)l->cfg.width, (uint32_t)l->cfg.height)) return fail("render_tensor_rois: %s", m);
+	std::vector<uint32_t> slots(count);
+	for (uint32_t k = 0; k < count; k++) {
+		const uint32_t i = pictures ? pictures[k] : k;
+		if (i >= l->out.size()) return fail("render_tensor_rois: picture %u outside the %u pictures of the last tick", i, (unsigned)l->out.size());
+		slots[k] = l->out[i].slot;
+	}
+	return batch_render_tensor_rois(l->b, slots.data(), count, desc, dev_rois, n_rois, dev_out, dev_status, (hipStream_t)hip_stream);
+}
+
+extern "C" int jsmpeg_hip_live_render_tensor_rois_latest(jsmpeg_hip_live_t *l, const uint32_t *streams, uint32_t count,
+                                                         const jsmpeg_hip_tensor_desc_t *desc, const jsmpeg_hip_roi_t *dev_rois,
+                                                         uint32_t n_rois, void *dev_out, uint8_t *dev_status, void *hip_stream,
+                                                         uint8_t *have) {
+	g_err[0] = 0;
+	if (!l) return fail("null live handle");
+	if ((count && !streams) || (n_rois && (!desc || !dev_rois || !dev_out))) return fail("null argument");
+	if (live_settle(l) < 0) return -1;
+	if (n_rois)                                                  /* (no boxes: nothing is launched, `have` is still answered) */
+		if (const char *m = jm_tensor_roi_check(desc, (uint32_t)l->cfg.width, (uint32_t)l->cfg.height)) return fail("render_tensor_rois_latest: %s", m);
+	std::vector<uint32_t> slots(count);
+	for (uint32_t k = 0; k < count; k++) {
+		const uint32_t s = streams[k];
+		if (s >= l->streams.size() || !l->streams[s].open) return fail("render_tensor_rois_latest: stream %u is not open", s);
+		const LiveStream &S = l->streams[s];
+		slots[k] = S.have ? s * l->ring + S.head : JM_NONE;
+	}
+	if (n_rois && batch_render_tensor_rois(l->b, slots.data(), count, desc, dev_rois, n_rois, dev_out, dev_status, (hipStream_t)hip_stream) < 0) return -1;
+	if (have)
+		for (uint32_t k = 0; k < count; k++) have[k] = slots[k] != JM_NONE;
+	return 0;
+}
+
 /* The ring rule behind the promise in the header: live_assign_slots gives a stream's k-th picture of a tick the slot
  * (head + 1 + k) % ring and a tick ends with head += its pictures, so slot `head` is written again by the stream's ring-th
  * picture from here -- ring = max_pictures_per_tick + 2, a tick decodes at most ring - 2: never in the next tick. */

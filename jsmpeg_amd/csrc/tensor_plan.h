@@ -12,6 +12,10 @@
  *                 a sum in tap order starting with tap 0 -- torch's separable order;
  *   output        float: (v / 255 - mean[c]) / std[c] as v * a[c] + b[c]; uint8: rint(v) clamped to 0 .. 255.
  * An axis whose size does not change is a copy (one tap of weight 1), as torch skips it.
+ *
+ * Rows from regions of interest (jsmpeg_hip_*_render_tensor_rois, k_tensor_roi, tests/sim/sim_tensor_roi.cpp): the crop of
+ * every row is a box from device memory, clipped to the picture by jm_roi_clip; jm_tensor_roi_plan gives the row the plan
+ * that jm_tensor_plan gives a descriptor with that crop, so the value above holds per row.
  */
 #pragma once
 #include <stdint.h>
@@ -148,6 +152,43 @@ JM_TP_FN JmTensorPlan jm_tensor_plan(const jsmpeg_hip_tensor_desc_t *d, uint32_t
 		p.a[c] = d->dtype == JSMPEG_HIP_TENSOR_U8 ? 1.0f : 1.0f / (255.0f * d->std[c]);
 		p.b[c] = d->dtype == JSMPEG_HIP_TENSOR_U8 ? 0.0f : -d->mean[c] / d->std[c];
 	}
+	return p;
+}
+
+/* ---- rows from regions of interest (jsmpeg_hip_*_render_tensor_rois; k_tensor_roi, tests/sim/sim_tensor_roi.cpp) ---- */
+
+/* A box clipped to the w x h picture of a call with `count` pictures: the rectangle, and the status the header defines (the
+ * fourth reason for EMPTY, a picture list entry with no picture, is the caller's to add: it knows the slots).  64-bit sums:
+ * x + width does not wrap for any int32 pair. */
+struct JmRoiClip {
+	int32_t x, y, width, height;
+	uint32_t status;
+};
+JM_TP_FN JmRoiClip jm_roi_clip(const jsmpeg_hip_roi_t &r, uint32_t count, uint32_t w, uint32_t h) {
+	JmRoiClip c;
+	c.x = 0; c.y = 0; c.width = 0; c.height = 0; c.status = JSMPEG_HIP_ROI_EMPTY;
+	if (r.row < 0 || (uint32_t)r.row >= count || r.width <= 0 || r.height <= 0) return c;
+	const int64_t x0 = r.x > 0 ? (int64_t)r.x : 0, y0 = r.y > 0 ? (int64_t)r.y : 0;
+	const int64_t xe = (int64_t)r.x + r.width, ye = (int64_t)r.y + r.height;
+	const int64_t x1 = xe < (int64_t)w ? xe : (int64_t)w, y1 = ye < (int64_t)h ? ye : (int64_t)h;
+	if (x1 <= x0 || y1 <= y0) return c;
+	c.x = (int32_t)x0; c.y = (int32_t)y0; c.width = (int32_t)(x1 - x0); c.height = (int32_t)(y1 - y0);
+	c.status = (c.x == r.x && c.y == r.y && c.width == r.width && c.height == r.height) ? JSMPEG_HIP_ROI_INSIDE : JSMPEG_HIP_ROI_CLIPPED;
+	return c;
+}
+
+/* The descriptor check of a call with boxes: the descriptor's own crop must be unset */
+JM_TP_FN const char *jm_tensor_roi_check(const jsmpeg_hip_tensor_desc_t *d, uint32_t w, uint32_t h) {
+	if (d && (d->crop_x || d->crop_y || d->crop_width || d->crop_height)) return "crop and rois exclude each other";
+	return jm_tensor_check(d, w, h);
+}
+
+/* ... and the plan of one row: the call's plan (the descriptor's, whole picture) with the crop and both axes of a clipped box
+ * (status 1 or 2) -- what jm_tensor_plan makes of the same descriptor with crop = that box */
+JM_TP_FN JmTensorPlan jm_tensor_roi_plan(JmTensorPlan p, const JmRoiClip &c) {
+	p.crop_x = (uint32_t)c.x; p.crop_y = (uint32_t)c.y;
+	p.ax = jm_tp_axis(c.width, (int32_t)p.out_w, p.ax.aa);
+	p.ay = jm_tp_axis(c.height, (int32_t)p.out_h, p.ay.aa);
 	return p;
 }
 

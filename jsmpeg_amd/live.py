@@ -255,6 +255,29 @@ class Live:
                            out)
         return t, have[:count].astype(bool)
 
+    def tensor_rois(self, rois, pictures=None, size=None, dtype=None, layout="nchw", order="rgb", antialias=True, mean=None,
+                    std=None, out=None):
+        """Per-box crops of the last tick's pictures: Batch.tensor_rois's arguments and contract, rois[r][0] an index into
+        `pictures` (None: all of the tick's).  Returns (tensor, status); the next tick waits for it on the device."""
+        idx, count = _tensor.indices(pictures, self.picture_count if pictures is None else 0)
+        ptr = idx.ctypes.data if idx is not None else None
+        return _tensor.render_rois(
+            lambda d, r, n, o, s, st: self._ok(self.L.jsmpeg_hip_live_render_tensor_rois(self.h, ptr, count, d, r, n, o, s, st)),
+            self.device, self.width, self.height, rois, size, dtype, layout, order, antialias, mean, std, out)
+
+    def latest_tensor_rois(self, rois, streams, size=None, dtype=None, layout="nchw", order="rgb", antialias=True, mean=None,
+                           std=None, out=None):
+        """Per-box crops of the NEWEST decoded frame of each listed stream, rois[r][0] an index into `streams`: returns
+        (tensor, status, have) -- the boxes of a stream that has no frame yet get status 0 and rows of zeros."""
+        idx, count = _tensor.indices(streams, 0)
+        have = np.zeros(max(1, count), dtype=np.uint8)
+        ptr = idx.ctypes.data if count else None
+        t, status = _tensor.render_rois(
+            lambda d, r, n, o, s, st: self._ok(self.L.jsmpeg_hip_live_render_tensor_rois_latest(self.h, ptr, count, d, r, n, o, s, st,
+                                                                                              have.ctypes.data)),
+            self.device, self.width, self.height, rois, size, dtype, layout, order, antialias, mean, std, out)
+        return t, status, have[:count].astype(bool)
+
     def latest_frames(self, streams):
         """The device address of the NEWEST decoded picture of each listed stream (Y | Cr | Cb of the coded size, in the
         stream's ring), from whichever tick decoded it, or None for a stream with no picture yet: what

@@ -18,6 +18,9 @@ class TensorDesc(ctypes.Structure):
 
 
 SYMBOLS = ("jsmpeg_hip_batch_render_tensor", "jsmpeg_hip_live_render_tensor", "jsmpeg_hip_live_render_tensor_latest")
+ROI_SYMBOLS = ("jsmpeg_hip_batch_render_tensor_rois", "jsmpeg_hip_live_render_tensor_rois",
+               "jsmpeg_hip_live_render_tensor_rois_latest")
+ROI_EMPTY, ROI_INSIDE, ROI_CLIPPED = 0, 1, 2          # a row's status (include/jsmpeg_hip.h, jsmpeg_hip_roi_t)
 
 
 def bind(L):
@@ -29,6 +32,10 @@ def bind(L):
         fn.argtypes = [vp, vp, u32, ctypes.POINTER(TensorDesc), vp, vp]
     L.jsmpeg_hip_live_render_tensor_latest.restype = ctypes.c_int
     L.jsmpeg_hip_live_render_tensor_latest.argtypes = [vp, vp, u32, ctypes.POINTER(TensorDesc), vp, vp, vp]
+    for name in ROI_SYMBOLS:
+        fn = getattr(L, name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, u32, ctypes.POINTER(TensorDesc), vp, u32, vp, vp, vp] + ([vp] if name.endswith("latest") else [])
     return L
 
 
@@ -115,3 +122,61 @@ def render(call, device, width, height, count, size=None, crop=None, dtype=None,
     stream = torch.cuda.current_stream(dev).cuda_stream
     call(ctypes.byref(desc), out.data_ptr() if count else None, stream)
     return out
+
+
+def render_rois(call, device, width, height, rois, size, dtype=None, layout="nchw", order="rgb", antialias=True, mean=None,
+                std=None, out=None):
+    """A row per region of interest: `rois` goes to the handle's device as int32 [R, 5] (row, x, y, width, height) -- an int32
+    CUDA tensor of that shape there is used in place, anything else array-like is copied -- then render() with
+    call(desc, rois_ptr, R, out_ptr, status_ptr, stream).  Returns (tensor, status); no host wait."""
+    import torch
+    if size is None:
+        raise ValueError("size: (height, width) is required with rois (every row has a box of its own)")
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None or device < 0 else device)
+    if isinstance(rois, torch.Tensor):
+        if rois.is_floating_point() or rois.is_complex() or rois.dtype == torch.bool:
+            raise ValueError("rois: integers (row, x, y, width, height) are needed, got %s (rois_from_xyxy makes them of float boxes)" % rois.dtype)
+        r = rois
+    else:
+        a = np.asarray(rois)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("rois: integers (row, x, y, width, height) are needed, got %s" % a.dtype)
+        a = a.reshape(0, 5) if a.size == 0 else a
+        if a.size and (a.min() < -(1 << 31) or a.max() >= 1 << 31):
+            raise ValueError("rois: values must be int32")
+        r = torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32))
+    if r.dim() != 2 or r.shape[1] != 5:
+        raise ValueError("rois: shape [R, 5] (row, x, y, width, height) is needed, got %r" % (tuple(r.shape),))
+    if r.dtype != torch.int32 and r.numel() and (int(r.min()) < -(1 << 31) or int(r.max()) >= 1 << 31):      # (a host wait: pass int32)
+        raise ValueError("rois: values must be int32")
+    r = r.to(device=dev, dtype=torch.int32).contiguous()          # (itself when it is int32, contiguous and there)
+    n = int(r.shape[0])
+    status = torch.empty((n,), dtype=torch.uint8, device=dev)
+    t = render(lambda d, o, st: call(d, r.data_ptr() if n else None, n, o, status.data_ptr() if n else None, st),
+               device, width, height, n, size, None, dtype, layout, order, antialias, mean, std, out)
+    return t, status
+
+
+def rois_from_xyxy(boxes, rows, scale=(1, 1), pad=0):
+    """Float boxes [R, 4] (x1, y1, x2, y2), as a detector gives them, and the picture index `rows` [R] of each -> int32 [R, 5]
+    (row, x, y, width, height) for tensor_rois, in torch ops on the boxes' device (no host step): the coordinates times
+    scale = (sx, sy) -- the detector's input to display pixels -- grown by `pad` pixels on every side, then the smallest
+    pixel rectangle that covers them (floor of the near edges, ceil of the far ones).  A box with a NaN gets width 0 (status
+    0); values beyond int32 are clamped.  The box is NOT clipped to the picture: the render does that and reports it."""
+    import torch
+    b = torch.as_tensor(boxes)
+    if b.dim() != 2 or b.shape[1] != 4:
+        raise ValueError("boxes: shape [R, 4] (x1, y1, x2, y2) is needed, got %r" % (tuple(b.shape),))
+    rows = torch.as_tensor(rows, device=b.device)
+    if rows.dim() != 1 or rows.shape[0] != b.shape[0] or rows.is_floating_point():
+        raise ValueError("rows: %d integers are needed, one per box" % b.shape[0])
+    sx, sy = (float(scale), float(scale)) if isinstance(scale, (int, float)) else (float(v) for v in scale)
+    lim = (-float(1 << 31), float((1 << 31) - 1))
+    b = b.to(torch.float64)
+    bad = torch.isnan(b).any(dim=1)
+    b = torch.nan_to_num(b, nan=0.0) * torch.tensor([sx, sy, sx, sy], dtype=torch.float64, device=b.device)
+    lo = torch.floor(b[:, :2] - float(pad)).clamp(*lim).to(torch.int64)
+    hi = torch.ceil(b[:, 2:] + float(pad)).clamp(*lim).to(torch.int64)
+    wh = (hi - lo).clamp(int(lim[0]), int(lim[1]))
+    wh = torch.where(bad[:, None], torch.zeros_like(wh), wh)
+    return torch.cat([rows.to(torch.int64).clamp(int(lim[0]), int(lim[1]))[:, None], lo, wh], dim=1).to(torch.int32)
