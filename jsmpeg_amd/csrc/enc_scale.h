@@ -18,8 +18,11 @@
  *             otherwise                     num = max(0, (2i + 1) n_in - n_out), i0 = num div 2 n_out, r = num mod 2 n_out:
  *                                           i0 >= n_in - 1: the single tap n_in - 1; r == 0: the single tap i0;
  *                                           else tap i0 with n = 2 n_out - r and tap i0 + 1 with n = r
- *           weights: N = sum n_j, W_j = (2 * 16384 n_j + N) div 2N, and the first tap of the largest W takes 16384 - sum W:
- *           non-negative, summing to exactly 16384.
+ *           weights: N = sum n_j, W_j = (2 * 16384 n_j + N) div 2N, and the first tap of the largest W takes 16384 - sum W.
+ *           An output index where that tap would go below 0 -- the roundings of very many small weights add up to more than
+ *           the largest: only antialiased n_out = 1 with n_in from 1280 and n_out = 2 with n_in from 2870, within 1 .. 4095 --
+ *           takes cumulative rounding instead: C_j = n_0 + .. + n_(j-1), R(c) = (2 * 16384 c + N) div 2N in 64 bits,
+ *           W_j = R(C_(j+1)) - R(C_j), no remainder tap.  Either way every weight is 0 .. 16384 and they sum to exactly 16384.
  * VALUE     horizontal pass, then vertical:  t = (sum_j Wx_j p[x0 + j] + 32) >> 6   (<= 65280)
  *                                            out = (sum_k Wy_k t[y0 + k] + 2^21) >> 22   (0 .. 255 without a clamp)
  *           everything fits 32 bits.
@@ -54,6 +57,7 @@ struct JmEsTaps {
 	uint32_t N;                  /* sum of the n_j */
 	uint32_t p;                  /* antialiased: the centre c; two plain taps: r */
 	uint32_t fix_j, fix;         /* the tap that takes the remainder, and the remainder */
+	uint32_t cum;                /* 1: that tap would go below 0, the weights are the cumulative roundings instead */
 };
 
 JM_ES_FN uint32_t jm_es_n(const JmEsAxis &a, const JmEsTaps &t, uint32_t j) {
@@ -67,9 +71,23 @@ JM_ES_FN uint32_t jm_es_n(const JmEsAxis &a, const JmEsTaps &t, uint32_t j) {
 
 JM_ES_FN uint32_t jm_es_weight_raw(const JmEsTaps &t, uint32_t n) { return (2u * JM_ES_ONE * n + t.N) / (2u * t.N); }
 
+/* C_j = n_0 + .. + n_(j-1) (0 <= j <= t.xsize) without a loop: the antialiased n_k = 2 n_in - |d_0 + 2 n_out k| is linear on
+ * either side of the centre, the first m of the k < j lie below it */
+JM_ES_FN uint64_t jm_es_cum(const JmEsAxis &a, const JmEsTaps &t, uint32_t j) {
+	if (!(a.aa && a.n_in > a.n_out)) return j == 0 ? 0u : j == 1 ? jm_es_n(a, t, 0) : t.N;
+	const int64_t d0 = (int64_t)(2u * t.xmin + 1u) * a.n_out - (int64_t)t.p, s = 2 * (int64_t)a.n_out;
+	int64_t m = d0 < 0 ? (-d0 + s - 1) / s : 0;
+	if (m > (int64_t)j) m = j;
+	const int64_t tri_m = m * (m - 1) / 2, tri_j = (int64_t)j * ((int64_t)j - 1) / 2;
+	const int64_t below = -(d0 * m + s * tri_m), above = d0 * ((int64_t)j - m) + s * (tri_j - tri_m);
+	return (uint64_t)(2 * (int64_t)a.n_in * j - below - above);
+}
+
+JM_ES_FN uint32_t jm_es_round_cum(const JmEsTaps &t, uint64_t c) { return (uint32_t)((2u * (uint64_t)JM_ES_ONE * c + t.N) / (2u * (uint64_t)t.N)); }
+
 JM_ES_FN JmEsTaps jm_es_taps(const JmEsAxis &a, uint32_t i) {
 	JmEsTaps t;
-	t.N = 1; t.p = 0; t.fix_j = 0; t.fix = 0;
+	t.N = 1; t.p = 0; t.fix_j = 0; t.fix = 0; t.cum = 0;
 	if (a.n_in == a.n_out) { t.xmin = i; t.xsize = 1; return t; }
 	if (a.aa && a.n_in > a.n_out) {
 		const uint32_t c = (2u * i + 1u) * a.n_in, lo = c - 2u * a.n_in, hi = c + 2u * a.n_in;    /* (lo as a signed number: i = 0 gives -n_in) */
@@ -95,12 +113,14 @@ JM_ES_FN JmEsTaps jm_es_taps(const JmEsAxis &a, uint32_t i) {
 		if (w > best) { best = w; t.fix_j = j; }
 	}
 	t.fix = JM_ES_ONE - sum;         /* (mod 2^32: the sum may exceed 16384 by the roundings) */
+	t.cum = sum > JM_ES_ONE + best ? 1u : 0u;
 	return t;
 }
 
-/* weight of tap j (0 <= j < t.xsize) */
+/* weight of tap j (0 <= j < t.xsize): 0 .. JM_ES_ONE */
 JM_ES_FN uint32_t jm_es_weight(const JmEsAxis &a, const JmEsTaps &t, uint32_t j) {
 	if (t.xsize == 1) return JM_ES_ONE;
+	if (t.cum) return jm_es_round_cum(t, jm_es_cum(a, t, j + 1u)) - jm_es_round_cum(t, jm_es_cum(a, t, j));
 	return jm_es_weight_raw(t, jm_es_n(a, t, j)) + (j == t.fix_j ? t.fix : 0u);
 }
 

@@ -97,6 +97,19 @@ LAYOUTS = {
                            [(1,) * 64, tuple(int(k % 3 != 0) for k in range(64))]),
 }
 
+# Beside LAYOUTS (same tuple): cells whose sources are enc_scale_inputs.RATIOS geometries -- a horizontal tap run whose weights
+# take enc_scale.h's second form -- pasted 1 and 2 pixels wide at even x over a whole-picture cell
+RATIO_LAYOUT = (64, 48, FILL, [(64, 48, None, 1, 0, 0, 64, 48), si.RATIOS["worst_3120_to_1"][:3] + (1, 22, 10, 1, 9),
+                               si.RATIOS["worst_3418_to_2"][:3] + (1, 40, 20, 2, 6)], [(1, 1, 1), (0, 1, 1)])
+
+
+def ratio_layout_frames():
+    """[picture][cell] -> source frame or None, noise throughout"""
+    _, _, _, cells, present = RATIO_LAYOUT
+    return [[ei.noise_frame(c[0], c[1], seed=40 + 3 * p + k) if here else None for k, (c, here) in enumerate(zip(cells, pic))]
+            for p, pic in enumerate(present)]
+
+
 _frames = {}
 
 

@@ -1,6 +1,8 @@
 """TEST INFRASTRUCTURE ONLY -- the numpy restatement of the encoder's scaled input (jsmpeg_amd/csrc/enc_scale.h), written from
 the rule's text and sharing nothing with the header: the taps of an axis as a dense weight matrix, the two passes as exact
-matrix products, the three planes, the edge replication."""
+matrix products, the three planes, the edge replication.  The weights of an output index: W_j = (2 * 16384 n_j + N) div 2N with
+the remainder 16384 - sum W on the first tap of the largest W; the indices where that tap would go below 0 (antialiased
+n_out = 1 from n_in = 1280, n_out = 2 from n_in = 2870) take the differences of the rounded running sums instead."""
 import numpy as np
 
 ONE = 16384
@@ -35,7 +37,14 @@ def axis_taps(n_in, n_out, aa):
                 first, ns = i0, [2 * n_out - r, r]
         N = sum(ns)
         w = [(2 * ONE * v + N) // (2 * N) for v in ns]
-        w[w.index(max(w))] += ONE - sum(w)
+        at = w.index(max(w))
+        if w[at] + ONE - sum(w) >= 0:
+            w[at] += ONE - sum(w)                       # the first tap of the largest W takes the remainder
+        else:
+            # that tap would go below 0 (antialiased n_out = 1 from n_in = 1280, n_out = 2 from 2870): the differences of the
+            # rounded running sums instead -- R(c) = (2 * 16384 c + N) div 2N over c = 0, n_0, n_0 + n_1, .. , N
+            r = [(2 * ONE * int(c) + N) // (2 * N) for c in np.concatenate([[0], np.cumsum(np.asarray(ns, dtype=np.int64))])]
+            w = [b - a for a, b in zip(r, r[1:])]
         out.append((first, w))
     return out
 

@@ -30,6 +30,21 @@ def test_named_layouts_simulator_equals_restatement(name):
     assert rc == 0 and plan["words"] <= plan["bound"] and plan["rows"] >= 4, (rc, plan)
 
 
+def test_cells_of_the_largest_ratios_simulator_equals_restatement():
+    """cells 1 and 2 pixels wide from sources 3120 and 3418 wide: their horizontal weights take enc_scale.h's second form (the
+    first form's remainder tap would be negative there); the device runs the same layout in tests/test_gpu_encode_scale_edges.py"""
+    w, h, fill, cells, _ = mi.RATIO_LAYOUT
+    assert all(c[4] % 2 == 0 and c[6] in (1, 2) for c in cells[1:])
+    assert all(si.axis_scan(c[0], c[6], 1)[3] == c[6] for c in cells[1:]), "every output column of these cells is on the second form"
+    for k, fr in enumerate(mi.ratio_layout_frames()):
+        got, want = mi.sim_frame(cells, fr, w, h, fill), em.compose(cells, fr, w, h, fill)
+        assert got is not None and np.array_equal(got, want), k
+        y = planes(want, w, h)[0]
+        assert k == 1 or not np.array_equal(y[10:19, 22], planes(em.compose(cells[:1], fr[:1], w, h, fill), w, h)[0][10:19, 22]), "the cell is seen"
+    rc, plan = mi.plan_check(cells, w, h, fill)
+    assert rc == 0 and plan["words"] <= plan["bound"] and plan["rows"] >= 4, (rc, plan)
+
+
 def test_the_named_wall_is_what_the_kernel_test_counts_on():
     w, h, fill, cells, present = mi.LAYOUTS["1_wall_273x71"]
     rc, plan = mi.plan_check(cells, w, h, fill)
