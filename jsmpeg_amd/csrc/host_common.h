@@ -1,8 +1,9 @@
 /*
  * The one error and allocation dialect of the host runtime: every translation unit of the library (engine.hip, live.hip,
- * decoder.hip, encode.hip through engine_internal.h; ts_ingest.hip, mp2_stage.hip, mp2_live.hip, shard.hip directly) reports
- * through fail() into the calling thread's message and allocates device memory through jm_malloc.  Knows nothing of the
- * batch object.  Not installed; nothing outside jsmpeg_amd/csrc includes it.
+ * decoder.hip, encode.hip through engine_internal.h; ts_ingest.hip, mp2_stage.hip, mp2_live.hip, shard.hip directly;
+ * pcm_resample.hip, logmel.hip, mp2_encode.hip, ts_program.hip with pass_state.h, the lifecycle of their handles, on top)
+ * reports through fail() into the calling thread's message and allocates device memory through jm_malloc.  Knows nothing of
+ * the batch object.  Not installed; nothing outside jsmpeg_amd/csrc includes it.
  */
 #pragma once
 #include <hip/hip_runtime.h>

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "host_common.h"
+#include "pass_state.h"
 #include "jsmpeg_hip.h"
 #include "logmel.h"
 
@@ -141,7 +142,7 @@ __global__ void __launch_bounds__(256) k_logmel_clamp(LmRule R, const LmStream *
 
 struct jsmpeg_hip_logmel_t {
 	jsmpeg_hip_logmel_config_t cfg;
-	int device = 0;
+	JmPass pass{ "logmel: a pass is in flight: jsmpeg_hip_logmel_sync (or a reader) settles it first", "logmel: no features were computed yet" };
 	LmRule R;
 	float *d_basis = nullptr, *d_fb = nullptr, *d_carry = nullptr, *d_tmp = nullptr;
 	int32_t *d_range = nullptr;
@@ -150,9 +151,7 @@ struct jsmpeg_hip_logmel_t {
 	std::vector<LmChain> chain;                                /* per stream number */
 	std::vector<uint64_t> offset, count, c_list;               /* per stream number; per listed stream */
 	uint64_t total = 0;                                        /* elements of the last call */
-	bool pending = false, have_pass = false;
-	hipEvent_t ev[3] = { nullptr, nullptr, nullptr };          /* begin, behind the upload, done */
-};
+};                                                             /* pass.ev[1]: behind the upload */
 
 static size_t lm_elem_bytes(const LmRule &R) { return R.dtype == RS_F32 ? 4 : 2; }
 
@@ -228,11 +227,9 @@ extern "C" int jsmpeg_hip_logmel_filters(const jsmpeg_hip_logmel_config_t *confi
 
 static void lm_free(jsmpeg_hip_logmel_t *h) {
 	if (!h) return;
-	hipSetDevice(h->device);
-	if (h->pending) hipEventSynchronize(h->ev[2]);
+	jm_pass_close(h->pass);
 	hipFree(h->d_basis); hipFree(h->d_fb); hipFree(h->d_range); hipFree(h->d_carry); hipFree(h->d_tmp); hipFree(h->d_streams); hipFree(h->d_out);
 	if (h->h_streams) hipHostFree(h->h_streams);
-	for (hipEvent_t v : h->ev) if (v) hipEventDestroy(v);
 	delete h;
 }
 
@@ -252,7 +249,7 @@ static int lm_alloc(jsmpeg_hip_logmel_t *h, const std::vector<float> &basis, con
 	if (h->R.scale == LM_WHISPER) HIP_TRY(jm_malloc(&h->d_tmp, cap * sizeof(float)));
 	/* the attribute belongs to the kernel, not to the handle: every handle asks for the whole LDS, so that none lowers another's */
 	HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_logmel), hipFuncAttributeMaxDynamicSharedMemorySize, LM_LDS_MAX));
-	for (hipEvent_t &v : h->ev) HIP_TRY(hipEventCreate(&v));
+	if (jm_pass_events(h->pass) < 0) return -1;
 	HIP_TRY(hipDeviceSynchronize());
 	return 0;
 }
@@ -277,8 +274,7 @@ extern "C" jsmpeg_hip_logmel_t *jsmpeg_hip_logmel_create(const jsmpeg_hip_logmel
 	h->cfg = *config;
 	h->cfg.window = nullptr;
 	h->R = R;
-	if (config->device >= 0 && hipSetDevice(config->device) != hipSuccess) { fail("hipSetDevice(%d) failed", config->device); delete h; return nullptr; }
-	if (hipGetDevice(&h->device) != hipSuccess) { fail("hipGetDevice failed"); delete h; return nullptr; }
+	if (jm_pass_open(h->pass, config->device) < 0) { delete h; return nullptr; }
 	h->chain.assign(config->max_streams, LmChain{ 0, 0, 0 });
 	h->offset.assign(config->max_streams, 0); h->count.assign(config->max_streams, 0);
 	h->c_list.resize(config->max_streams);
@@ -288,40 +284,27 @@ extern "C" jsmpeg_hip_logmel_t *jsmpeg_hip_logmel_create(const jsmpeg_hip_logmel
 
 extern "C" void jsmpeg_hip_logmel_destroy(jsmpeg_hip_logmel_t *h) { lm_free(h); }
 
-/* waits for the pass in flight */
-static int lm_settle(jsmpeg_hip_logmel_t *h) {
-	if (!h->pending) return 0;
-	HIP_TRY(hipSetDevice(h->device));
-	h->pending = false;
-	HIP_TRY(hipEventSynchronize(h->ev[2]));
-	return 0;
-}
-
 extern "C" int jsmpeg_hip_logmel_features(jsmpeg_hip_logmel_t *h, const void *const *pcm, const uint32_t *samples, const uint32_t *stream_numbers, uint32_t n_streams,
                                           uint32_t flags, void *hip_stream) {
 	g_err[0] = 0;
 	if (!h) return fail("logmel: NULL handle");
-	if (h->pending) return fail("logmel: a pass is in flight: jsmpeg_hip_logmel_sync (or a reader) settles it first");
+	if (jm_pass_idle(h->pass) < 0) return -1;
 	if (flags & ~(JSMPEG_HIP_LOGMEL_END | JSMPEG_HIP_LOGMEL_CHAIN)) return fail("logmel: unknown flags 0x%x", flags);
 	if ((flags & JSMPEG_HIP_LOGMEL_CHAIN) && h->R.scale == LM_WHISPER) return fail("logmel: the whisper scale takes its maximum over a whole call, so it is refused with CHAIN");
 	if (n_streams > h->cfg.max_streams) return fail("logmel: %u streams > max_streams %u", n_streams, h->cfg.max_streams);
 	if (n_streams && (!pcm || !samples)) return fail("logmel: NULL pcm or samples");
 	for (uint32_t i = 0; i < n_streams; i++) {
-		const uint32_t s = stream_numbers ? stream_numbers[i] : i;
-		if (s >= h->cfg.max_streams) return fail("logmel: stream_numbers[%u] = %u >= max_streams %u", i, s, h->cfg.max_streams);
-		if (stream_numbers && i && s <= stream_numbers[i - 1]) return fail("logmel: stream_numbers[] must ascend (stream_numbers[%u] = %u after %u)", i, s, stream_numbers[i - 1]);
+		if (jm_pass_check_number("logmel", stream_numbers, i, h->cfg.max_streams) < 0) return -1;
 		if (samples[i] > h->cfg.max_samples) return fail("logmel: stream %u of the call has %u samples > max_samples %u: nothing was enqueued", i, samples[i], h->cfg.max_samples);
-		if (samples[i] && !pcm[i]) return fail("logmel: pcm[%u] is NULL", i);
-		if (samples[i] && ((uintptr_t)pcm[i] & 3u)) return fail("logmel: pcm[%u] is not 4-byte aligned", i);
+		if (jm_pass_check_pcm("logmel", pcm, samples, i) < 0) return -1;
 	}
 	const int rc = lm_plan_call(h->R, reinterpret_cast<const float *const *>(pcm), samples, stream_numbers, n_streams, flags, h->chain.data(), h->h_streams, h->c_list.data());
 	if (rc < 0) return fail("logmel: stream %d of the call yields %llu frames, row is %u: nothing was enqueued", -1 - rc, (unsigned long long)h->c_list[-1 - rc], h->R.row);
 	const uint64_t total = (uint64_t)n_streams * (uint64_t)h->R.n_mels * h->R.row;
-	HIP_TRY(hipSetDevice(h->device));
 	hipStream_t st = (hipStream_t)hip_stream;
-	HIP_TRY(hipEventRecord(h->ev[0], st));
+	if (jm_pass_begin(h->pass, st) < 0) return -1;
 	if (n_streams) HIP_TRY(hipMemcpyAsync(h->d_streams, h->h_streams, sizeof(LmStream) * n_streams, hipMemcpyHostToDevice, st));
-	HIP_TRY(hipEventRecord(h->ev[1], st));
+	if (jm_pass_mark(h->pass, st) < 0) return -1;
 	if (n_streams) {
 		hipLaunchKernelGGL(k_logmel, dim3((h->R.row + LM_F - 1) / LM_F, n_streams), dim3(LM_WG), lm_lds_floats(h->R) * sizeof(float), st, h->R, h->d_streams, h->d_basis,
 		                   h->d_fb, h->d_range, h->d_carry, h->d_out, h->d_tmp);
@@ -331,7 +314,7 @@ extern "C" int jsmpeg_hip_logmel_features(jsmpeg_hip_logmel_t *h, const void *co
 			HIP_TRY(hipGetLastError());
 		}
 	}
-	HIP_TRY(hipEventRecord(h->ev[2], st));
+	if (jm_pass_end(h->pass, st) < 0) return -1;
 	std::fill(h->offset.begin(), h->offset.end(), 0); std::fill(h->count.begin(), h->count.end(), 0);
 	for (uint32_t i = 0; i < n_streams; i++) {
 		const uint32_t s = stream_numbers ? stream_numbers[i] : i;
@@ -339,32 +322,27 @@ extern "C" int jsmpeg_hip_logmel_features(jsmpeg_hip_logmel_t *h, const void *co
 	}
 	lm_plan_commit(samples, stream_numbers, n_streams, flags, h->chain.data());
 	h->total = total;
-	h->pending = true; h->have_pass = true;
+	h->pass.pending = true; h->pass.have_pass = true;
 	return 0;
 }
 
 extern "C" int jsmpeg_hip_logmel_sync(jsmpeg_hip_logmel_t *h) {
 	g_err[0] = 0;
 	if (!h) return fail("logmel: NULL handle");
-	return lm_settle(h);
+	return jm_pass_settle(h->pass);
 }
 
 extern "C" int jsmpeg_hip_logmel_query(jsmpeg_hip_logmel_t *h) {
 	g_err[0] = 0;
 	if (!h) return fail("logmel: NULL handle");
-	if (!h->pending) return 1;
-	HIP_TRY(hipSetDevice(h->device));
-	const hipError_t e = hipEventQuery(h->ev[2]);
-	if (e == hipSuccess) return 1;
-	if (e == hipErrorNotReady) return 0;
-	return fail("hipEventQuery: %s", hipGetErrorString(e));
+	return jm_pass_query(h->pass);
 }
 
 /* the address and the bytes are the plan's: answered without waiting */
 extern "C" void *jsmpeg_hip_logmel_out(jsmpeg_hip_logmel_t *h, uint64_t *bytes) {
 	g_err[0] = 0;
 	if (!h) { fail("logmel: NULL handle"); return nullptr; }
-	if (!h->have_pass) { fail("logmel: no features were computed yet"); return nullptr; }
+	if (jm_pass_have(h->pass) < 0) return nullptr;
 	if (bytes) *bytes = h->total * lm_elem_bytes(h->R);
 	return h->d_out;
 }
@@ -373,8 +351,7 @@ extern "C" void *jsmpeg_hip_logmel_out(jsmpeg_hip_logmel_t *h, uint64_t *bytes) 
 extern "C" int jsmpeg_hip_logmel_stream_out(jsmpeg_hip_logmel_t *h, uint32_t stream, uint64_t *offset, uint64_t *count) {
 	g_err[0] = 0;
 	if (!h) return fail("logmel: NULL handle");
-	if (!h->have_pass) return fail("logmel: no features were computed yet");
-	if (stream >= h->cfg.max_streams) return fail("logmel: stream %u >= max_streams %u", stream, h->cfg.max_streams);
+	if (jm_pass_have(h->pass) < 0 || jm_pass_stream_bound("logmel", stream, h->cfg.max_streams) < 0) return -1;
 	if (offset) *offset = h->offset[stream];
 	if (count) *count = h->count[stream];
 	return 0;
@@ -383,18 +360,14 @@ extern "C" int jsmpeg_hip_logmel_stream_out(jsmpeg_hip_logmel_t *h, uint32_t str
 extern "C" int jsmpeg_hip_logmel_chain_reset(jsmpeg_hip_logmel_t *h, uint32_t stream) {
 	g_err[0] = 0;
 	if (!h) return fail("logmel: NULL handle");
-	if (h->pending) return fail("logmel: a pass is in flight: jsmpeg_hip_logmel_sync (or a reader) settles it first");
-	if (stream != 0xffffffffu && stream >= h->cfg.max_streams) return fail("logmel: stream %u >= max_streams %u", stream, h->cfg.max_streams);
-	for (uint32_t s = 0; s < h->cfg.max_streams; s++)
-		if (stream == 0xffffffffu || stream == s) h->chain[s] = LmChain{ 0, 0, 0 };
-	return 0;
+	return jm_pass_chain_reset(h->pass, "logmel", h->chain, stream);
 }
 
 extern "C" int jsmpeg_hip_logmel_chain_info(jsmpeg_hip_logmel_t *h, uint32_t stream, uint64_t out[3]) {
 	g_err[0] = 0;
 	if (!h) return fail("logmel: NULL handle");
 	if (!out) return fail("logmel: NULL out");
-	if (stream >= h->cfg.max_streams) return fail("logmel: stream %u >= max_streams %u", stream, h->cfg.max_streams);
+	if (jm_pass_stream_bound("logmel", stream, h->cfg.max_streams) < 0) return -1;
 	const LmChain &c = h->chain[stream];
 	out[0] = c.have; out[1] = c.have ? c.n : 0; out[2] = c.have ? lm_frames(h->R, c.n, false) : 0;
 	return 0;
@@ -403,11 +376,8 @@ extern "C" int jsmpeg_hip_logmel_chain_info(jsmpeg_hip_logmel_t *h, uint32_t str
 extern "C" int jsmpeg_hip_logmel_timings(jsmpeg_hip_logmel_t *h, float out_ms[2]) {
 	g_err[0] = 0;
 	if (!h) return fail("logmel: NULL handle");
-	if (lm_settle(h) < 0) return -1;
-	if (!h->have_pass) return fail("logmel: no features were computed yet");
+	if (jm_pass_ready(h->pass) < 0) return -1;
 	if (!out_ms) return fail("logmel: NULL out_ms");
-	HIP_TRY(hipSetDevice(h->device));
-	HIP_TRY(hipEventElapsedTime(&out_ms[0], h->ev[1], h->ev[2]));
-	HIP_TRY(hipEventElapsedTime(&out_ms[1], h->ev[0], h->ev[2]));
-	return 0;
+	if (jm_pass_elapsed(h->pass, 1, 2, &out_ms[0]) < 0) return -1;
+	return jm_pass_elapsed(h->pass, 0, 2, &out_ms[1]);
 }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "host_common.h"
+#include "pass_state.h"
 #include "jsmpeg_hip.h"
 #include "mp2_enc.h"
 #include "ts_prog_sources.h"
@@ -78,7 +79,7 @@ __global__ void __launch_bounds__(MP2E_WG) k_mp2e_frame(Mp2EncRule R, const Mp2E
 
 struct jsmpeg_hip_mp2_encoder_t {
 	jsmpeg_hip_mp2_encoder_config_t cfg;
-	int device = 0;
+	JmPass pass{ "MP2 encoder: an encode is in flight: jsmpeg_hip_mp2_encoder_sync (or a reader) settles it first", "MP2 encoder: nothing was encoded yet" };
 	Mp2EncRule R;
 	Mp2EncTables *d_tables = nullptr;
 	Mp2EncFrame *d_frames = nullptr, *h_frames = nullptr;      /* h_: pinned */
@@ -90,18 +91,14 @@ struct jsmpeg_hip_mp2_encoder_t {
 	std::vector<uint64_t> ordinal;                             /* per frame of the last call: its ordinal in its stream (ts_prog_sources.h) */
 	uint32_t count = 0;                                        /* frames of the last call */
 	uint64_t total = 0;
-	bool pending = false, have_pass = false;
-	hipEvent_t ev[3] = { nullptr, nullptr, nullptr };          /* begin, behind the kernel, done */
-};
+};                                                             /* pass.ev[1]: behind the kernel */
 
 static void mp2e_free(jsmpeg_hip_mp2_encoder_t *e) {
 	if (!e) return;
-	hipSetDevice(e->device);
-	if (e->pending) hipEventSynchronize(e->ev[2]);
+	jm_pass_close(e->pass);
 	hipFree(e->d_tables); hipFree(e->d_frames); hipFree(e->d_carry); hipFree(e->d_es); hipFree(e->d_stats);
 	if (e->h_frames) hipHostFree(e->h_frames);
 	if (e->h_stats) hipHostFree(e->h_stats);
-	for (hipEvent_t v : e->ev) if (v) hipEventDestroy(v);
 	delete e;
 }
 
@@ -118,7 +115,7 @@ static int mp2e_alloc(jsmpeg_hip_mp2_encoder_t *e) {
 	HIP_TRY(jm_malloc(&e->d_es, ((size_t)e->cfg.max_es_bytes + 15) & ~(size_t)15));
 	HIP_TRY(jm_malloc(&e->d_stats, sizeof(uint32_t) * 4 * nf));
 	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_stats), sizeof(uint32_t) * 4 * nf, hipHostMallocDefault));
-	for (hipEvent_t &v : e->ev) HIP_TRY(hipEventCreate(&v));
+	if (jm_pass_events(e->pass) < 0) return -1;
 	HIP_TRY(hipDeviceSynchronize());
 	return 0;
 }
@@ -138,8 +135,7 @@ extern "C" jsmpeg_hip_mp2_encoder_t *jsmpeg_hip_mp2_encoder_create(const jsmpeg_
 	jsmpeg_hip_mp2_encoder_t *e = new jsmpeg_hip_mp2_encoder_t();
 	e->cfg = *config;
 	e->R = R;
-	if (config->device >= 0 && hipSetDevice(config->device) != hipSuccess) { fail("hipSetDevice(%d) failed", config->device); delete e; return nullptr; }
-	if (hipGetDevice(&e->device) != hipSuccess) { fail("hipGetDevice failed"); delete e; return nullptr; }
+	if (jm_pass_open(e->pass, config->device) < 0) { delete e; return nullptr; }
 	e->chain.assign(config->max_streams, Mp2EncChain{ 0, 0, 0 });
 	e->begin.assign(config->max_streams, 0); e->end.assign(config->max_streams, 0);
 	e->b_list.resize(config->max_streams); e->e_list.resize(config->max_streams);
@@ -149,48 +145,32 @@ extern "C" jsmpeg_hip_mp2_encoder_t *jsmpeg_hip_mp2_encoder_create(const jsmpeg_
 
 extern "C" void jsmpeg_hip_mp2_encoder_destroy(jsmpeg_hip_mp2_encoder_t *e) { mp2e_free(e); }
 
-/* waits for the pass in flight */
-static int mp2e_settle(jsmpeg_hip_mp2_encoder_t *e) {
-	if (!e->pending) return 0;
-	HIP_TRY(hipSetDevice(e->device));
-	e->pending = false;
-	HIP_TRY(hipEventSynchronize(e->ev[2]));
-	return 0;
-}
-
 extern "C" int jsmpeg_hip_mp2_encoder_encode(jsmpeg_hip_mp2_encoder_t *e, const void *const *pcm, const uint32_t *frames, const uint32_t *stream_numbers,
                                              uint32_t n_streams, uint32_t flags, void *hip_stream) {
 	g_err[0] = 0;
 	if (!e) return fail("MP2 encoder: NULL handle");
-	if (e->pending) return fail("MP2 encoder: an encode is in flight: jsmpeg_hip_mp2_encoder_sync (or a reader) settles it first");
+	if (jm_pass_idle(e->pass) < 0) return -1;
 	if (flags & ~(JSMPEG_HIP_MP2_ENC_END | JSMPEG_HIP_MP2_ENC_CHAIN)) return fail("MP2 encoder: unknown flags 0x%x", flags);
 	if (n_streams > e->cfg.max_streams) return fail("MP2 encoder: %u streams > max_streams %u", n_streams, e->cfg.max_streams);
 	if (n_streams && (!pcm || !frames)) return fail("MP2 encoder: NULL pcm or frames");
+	if (jm_pass_check_streams("MP2 encoder", pcm, frames, stream_numbers, n_streams, e->cfg.max_streams) < 0) return -1;
 	uint64_t count = 0;
-	for (uint32_t i = 0; i < n_streams; i++) {
-		const uint32_t s = stream_numbers ? stream_numbers[i] : i;
-		if (s >= e->cfg.max_streams) return fail("MP2 encoder: stream_numbers[%u] = %u >= max_streams %u", i, s, e->cfg.max_streams);
-		if (stream_numbers && i && s <= stream_numbers[i - 1]) return fail("MP2 encoder: stream_numbers[] must ascend (stream_numbers[%u] = %u after %u)", i, s, stream_numbers[i - 1]);
-		if (frames[i] && !pcm[i]) return fail("MP2 encoder: pcm[%u] is NULL", i);
-		if (frames[i] && ((uintptr_t)pcm[i] & 3u)) return fail("MP2 encoder: pcm[%u] is not 4-byte aligned", i);
-		count += frames[i];
-	}
+	for (uint32_t i = 0; i < n_streams; i++) count += frames[i];
 	if (count > e->cfg.max_frames) return fail("MP2 encoder: %llu frames > max_frames %u", (unsigned long long)count, e->cfg.max_frames);
 	const uint64_t total = mp2e_plan(e->R, reinterpret_cast<const float *const *>(pcm), frames, stream_numbers, n_streams, flags, e->chain.data(), e->h_frames,
 	                                 e->b_list.data(), e->e_list.data());
 	if (total > e->cfg.max_es_bytes)
 		return fail("MP2 encoder: the call's streams need %llu bytes, max_es_bytes is %llu: nothing was enqueued", (unsigned long long)total, (unsigned long long)e->cfg.max_es_bytes);
-	HIP_TRY(hipSetDevice(e->device));
 	hipStream_t st = (hipStream_t)hip_stream;
-	HIP_TRY(hipEventRecord(e->ev[0], st));
+	if (jm_pass_begin(e->pass, st) < 0) return -1;
 	if (count) {
 		HIP_TRY(hipMemcpyAsync(e->d_frames, e->h_frames, sizeof(Mp2EncFrame) * count, hipMemcpyHostToDevice, st));
 		hipLaunchKernelGGL(k_mp2e_frame, dim3((uint32_t)count), dim3(MP2E_WG), 0, st, e->R, e->d_frames, e->d_tables, e->d_carry, e->d_es, e->d_stats);
 		HIP_TRY(hipGetLastError());
 	}
-	HIP_TRY(hipEventRecord(e->ev[1], st));
+	if (jm_pass_mark(e->pass, st) < 0) return -1;
 	if (count) HIP_TRY(hipMemcpyAsync(e->h_stats, e->d_stats, sizeof(uint32_t) * 4 * count, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipEventRecord(e->ev[2], st));
+	if (jm_pass_end(e->pass, st) < 0) return -1;
 	std::fill(e->begin.begin(), e->begin.end(), 0); std::fill(e->end.begin(), e->end.end(), 0);
 	for (uint32_t i = 0; i < n_streams; i++) {
 		const uint32_t s = stream_numbers ? stream_numbers[i] : i;
@@ -206,34 +186,27 @@ extern "C" int jsmpeg_hip_mp2_encoder_encode(jsmpeg_hip_mp2_encoder_t *e, const 
 	if ((flags & JSMPEG_HIP_MP2_ENC_CHAIN) && (flags & JSMPEG_HIP_MP2_ENC_END))
 		for (uint32_t i = 0; i < n_streams; i++) e->chain[stream_numbers ? stream_numbers[i] : i] = Mp2EncChain{ 0, 0, 0 };
 	e->count = (uint32_t)count; e->total = total;
-	e->pending = true; e->have_pass = true;
+	e->pass.pending = true; e->pass.have_pass = true;
 	return 0;
 }
 
 extern "C" int jsmpeg_hip_mp2_encoder_sync(jsmpeg_hip_mp2_encoder_t *e) {
 	g_err[0] = 0;
 	if (!e) return fail("MP2 encoder: NULL handle");
-	return mp2e_settle(e);
+	return jm_pass_settle(e->pass);
 }
 
 extern "C" int jsmpeg_hip_mp2_encoder_query(jsmpeg_hip_mp2_encoder_t *e) {
 	g_err[0] = 0;
 	if (!e) return fail("MP2 encoder: NULL handle");
-	if (!e->pending) return 1;
-	HIP_TRY(hipSetDevice(e->device));
-	const hipError_t r = hipEventQuery(e->ev[2]);
-	if (r == hipSuccess) return 1;
-	if (r == hipErrorNotReady) return 0;
-	return fail("hipEventQuery: %s", hipGetErrorString(r));
+	return jm_pass_query(e->pass);
 }
 
 /* the readers of the device's results: settle, then refuse a handle without a pass */
 static int mp2e_ready(jsmpeg_hip_mp2_encoder_t *e) {
 	g_err[0] = 0;
 	if (!e) return fail("MP2 encoder: NULL handle");
-	if (mp2e_settle(e) < 0) return -1;
-	if (!e->have_pass) return fail("MP2 encoder: nothing was encoded yet");
-	return 0;
+	return jm_pass_ready(e->pass);
 }
 
 extern "C" void *jsmpeg_hip_mp2_encoder_es(jsmpeg_hip_mp2_encoder_t *e, uint64_t *total_bytes) {
@@ -246,8 +219,7 @@ extern "C" void *jsmpeg_hip_mp2_encoder_es(jsmpeg_hip_mp2_encoder_t *e, uint64_t
 extern "C" int jsmpeg_hip_mp2_encoder_stream_range(jsmpeg_hip_mp2_encoder_t *e, uint32_t stream, uint64_t *begin, uint64_t *end) {
 	g_err[0] = 0;
 	if (!e) return fail("MP2 encoder: NULL handle");
-	if (!e->have_pass) return fail("MP2 encoder: nothing was encoded yet");
-	if (stream >= e->cfg.max_streams) return fail("MP2 encoder: stream %u >= max_streams %u", stream, e->cfg.max_streams);
+	if (jm_pass_have(e->pass) < 0 || jm_pass_stream_bound("MP2 encoder", stream, e->cfg.max_streams) < 0) return -1;
 	if (begin) *begin = e->begin[stream];
 	if (end) *end = e->end[stream];
 	return 0;
@@ -256,7 +228,7 @@ extern "C" int jsmpeg_hip_mp2_encoder_stream_range(jsmpeg_hip_mp2_encoder_t *e, 
 extern "C" int jsmpeg_hip_mp2_encoder_frame_range(jsmpeg_hip_mp2_encoder_t *e, uint32_t k, uint64_t *offset, uint32_t *bytes) {
 	g_err[0] = 0;
 	if (!e) return fail("MP2 encoder: NULL handle");
-	if (!e->have_pass) return fail("MP2 encoder: nothing was encoded yet");
+	if (jm_pass_have(e->pass) < 0) return -1;
 	if (k >= e->count) return fail("MP2 encoder: frame %u of %u", k, e->count);
 	if (offset) *offset = e->h_frames[k].out;
 	if (bytes) *bytes = e->h_frames[k].bytes;
@@ -265,10 +237,10 @@ extern "C" int jsmpeg_hip_mp2_encoder_frame_range(jsmpeg_hip_mp2_encoder_t *e, u
 
 extern "C" int64_t jsmpeg_hip_mp2_encoder_read_es(jsmpeg_hip_mp2_encoder_t *e, uint32_t stream, void *host, uint64_t cap) {
 	if (mp2e_ready(e) < 0) return -1;
-	if (stream >= e->cfg.max_streams) return fail("MP2 encoder: stream %u >= max_streams %u", stream, e->cfg.max_streams);
+	if (jm_pass_stream_bound("MP2 encoder", stream, e->cfg.max_streams) < 0) return -1;
 	const uint64_t b = e->begin[stream], n = e->end[stream] - b, k = std::min(n, cap);
 	if (k && host) {
-		HIP_TRY(hipSetDevice(e->device));
+		HIP_TRY(hipSetDevice(e->pass.device));
 		HIP_TRY(hipMemcpy(host, e->d_es + b, k, hipMemcpyDeviceToHost));
 	}
 	return (int64_t)n;
@@ -285,18 +257,14 @@ extern "C" int jsmpeg_hip_mp2_encoder_frame_stats(jsmpeg_hip_mp2_encoder_t *e, u
 extern "C" int jsmpeg_hip_mp2_encoder_chain_reset(jsmpeg_hip_mp2_encoder_t *e, uint32_t stream) {
 	g_err[0] = 0;
 	if (!e) return fail("MP2 encoder: NULL handle");
-	if (e->pending) return fail("MP2 encoder: an encode is in flight: jsmpeg_hip_mp2_encoder_sync (or a reader) settles it first");
-	if (stream != 0xffffffffu && stream >= e->cfg.max_streams) return fail("MP2 encoder: stream %u >= max_streams %u", stream, e->cfg.max_streams);
-	for (uint32_t s = 0; s < e->cfg.max_streams; s++)
-		if (stream == 0xffffffffu || stream == s) e->chain[s] = Mp2EncChain{ 0, 0, 0 };
-	return 0;
+	return jm_pass_chain_reset(e->pass, "MP2 encoder", e->chain, stream);
 }
 
 extern "C" int jsmpeg_hip_mp2_encoder_chain_info(jsmpeg_hip_mp2_encoder_t *e, uint32_t stream, uint64_t out[2]) {
 	g_err[0] = 0;
 	if (!e) return fail("MP2 encoder: NULL handle");
 	if (!out) return fail("MP2 encoder: NULL out");
-	if (stream >= e->cfg.max_streams) return fail("MP2 encoder: stream %u >= max_streams %u", stream, e->cfg.max_streams);
+	if (jm_pass_stream_bound("MP2 encoder", stream, e->cfg.max_streams) < 0) return -1;
 	out[0] = e->chain[stream].have; out[1] = e->chain[stream].have ? e->chain[stream].n : 0;
 	return 0;
 }
@@ -304,19 +272,17 @@ extern "C" int jsmpeg_hip_mp2_encoder_chain_info(jsmpeg_hip_mp2_encoder_t *e, ui
 extern "C" int jsmpeg_hip_mp2_encoder_timings(jsmpeg_hip_mp2_encoder_t *e, float out_ms[2]) {
 	if (mp2e_ready(e) < 0) return -1;
 	if (!out_ms) return fail("MP2 encoder: NULL out_ms");
-	HIP_TRY(hipSetDevice(e->device));
-	HIP_TRY(hipEventElapsedTime(&out_ms[0], e->ev[0], e->ev[1]));
-	HIP_TRY(hipEventElapsedTime(&out_ms[1], e->ev[0], e->ev[2]));
-	return 0;
+	if (jm_pass_elapsed(e->pass, 0, 1, &out_ms[0]) < 0) return -1;
+	return jm_pass_elapsed(e->pass, 0, 2, &out_ms[1]);
 }
 
 /* ------------------------------------------------------------------ the last call as the program mux's audio source
  * (ts_prog_sources.h): closed form, so everything is the host's at enqueue time */
 int jm_mp2e_tsp_source(jsmpeg_hip_mp2_encoder_t *e, JmTspAudioSource *out, uint64_t *offset, uint32_t *bytes, uint32_t *stream, uint64_t *ordinal, uint32_t cap) {
 	if (!e) return fail("ts_program: NULL MP2 encoder");
-	if (!e->have_pass) return fail("ts_program: the MP2 encoder has not encoded anything yet");
+	if (!e->pass.have_pass) return fail("ts_program: the MP2 encoder has not encoded anything yet");
 	if (e->count > cap) return fail("ts_program: the MP2 encoder's last call has %u frames, max_audio_units is %u", e->count, cap);
-	out->count = e->count; out->max_streams = e->cfg.max_streams; out->sample_rate = (uint32_t)e->R.fs; out->device = e->device;
+	out->count = e->count; out->max_streams = e->cfg.max_streams; out->sample_rate = (uint32_t)e->R.fs; out->device = e->pass.device;
 	out->d_es = e->d_es;
 	for (uint32_t k = 0; k < e->count; k++) {
 		offset[k] = e->h_frames[k].out; bytes[k] = e->h_frames[k].bytes; stream[k] = e->h_frames[k].stream; ordinal[k] = e->ordinal[k];

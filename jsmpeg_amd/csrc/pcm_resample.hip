@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "host_common.h"
+#include "pass_state.h"
 #include "jsmpeg_hip.h"
 #include "pcm_resample.h"
 
@@ -42,7 +43,7 @@ __global__ void __launch_bounds__(RS_WG) k_resample(RsRule R, const RsStream *st
 
 struct jsmpeg_hip_resampler_t {
 	jsmpeg_hip_resampler_config_t cfg;
-	int device = 0;
+	JmPass pass{ "resampler: a pass is in flight: jsmpeg_hip_resampler_sync (or a reader) settles it first", "resampler: nothing was resampled yet" };
 	RsRule R;
 	uint64_t cap = 0;                                          /* of d_out: elements (WAVEFORM) or frames (FRAMES) */
 	float *d_taps = nullptr, *d_carry = nullptr, *d_part = nullptr;
@@ -51,19 +52,15 @@ struct jsmpeg_hip_resampler_t {
 	std::vector<RsChain> chain;                                /* per stream number */
 	std::vector<uint64_t> offset, count, o_list, c_list;       /* per stream number; per listed stream */
 	uint64_t total = 0;
-	bool pending = false, have_pass = false;
-	hipEvent_t ev[3] = { nullptr, nullptr, nullptr };          /* begin, behind the upload, done */
-};
+};                                                             /* pass.ev[1]: behind the upload */
 
 static size_t rs_elem_bytes(const RsRule &R) { return R.form == RS_FORM_FRAMES ? sizeof(float) * 2 * RS_FRAME : (R.dtype == RS_F32 ? 4 : 2); }
 
 static void rs_free(jsmpeg_hip_resampler_t *r) {
 	if (!r) return;
-	hipSetDevice(r->device);
-	if (r->pending) hipEventSynchronize(r->ev[2]);
+	jm_pass_close(r->pass);
 	hipFree(r->d_taps); hipFree(r->d_carry); hipFree(r->d_part); hipFree(r->d_streams); hipFree(r->d_out);
 	if (r->h_streams) hipHostFree(r->h_streams);
-	for (hipEvent_t v : r->ev) if (v) hipEventDestroy(v);
 	delete r;
 }
 
@@ -80,7 +77,7 @@ static int rs_alloc(jsmpeg_hip_resampler_t *r) {
 	HIP_TRY(jm_malloc(&r->d_streams, sizeof(RsStream) * ns));
 	HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&r->h_streams), sizeof(RsStream) * ns, hipHostMallocDefault));
 	HIP_TRY(jm_malloc(reinterpret_cast<uint8_t **>(&r->d_out), (size_t)r->cap * rs_elem_bytes(r->R)));
-	for (hipEvent_t &v : r->ev) HIP_TRY(hipEventCreate(&v));
+	if (jm_pass_events(r->pass) < 0) return -1;
 	HIP_TRY(hipDeviceSynchronize());
 	return 0;
 }
@@ -133,8 +130,7 @@ extern "C" jsmpeg_hip_resampler_t *jsmpeg_hip_resampler_create(const jsmpeg_hip_
 	r->cfg = *config;
 	r->R = R;
 	r->cap = cap;
-	if (config->device >= 0 && hipSetDevice(config->device) != hipSuccess) { fail("hipSetDevice(%d) failed", config->device); delete r; return nullptr; }
-	if (hipGetDevice(&r->device) != hipSuccess) { fail("hipGetDevice failed"); delete r; return nullptr; }
+	if (jm_pass_open(r->pass, config->device) < 0) { delete r; return nullptr; }
 	r->chain.assign(config->max_streams, RsChain{ 0, 0, 0, 0 });
 	r->offset.assign(config->max_streams, 0); r->count.assign(config->max_streams, 0);
 	r->o_list.resize(config->max_streams); r->c_list.resize(config->max_streams);
@@ -144,32 +140,17 @@ extern "C" jsmpeg_hip_resampler_t *jsmpeg_hip_resampler_create(const jsmpeg_hip_
 
 extern "C" void jsmpeg_hip_resampler_destroy(jsmpeg_hip_resampler_t *r) { rs_free(r); }
 
-/* waits for the pass in flight */
-static int rs_settle(jsmpeg_hip_resampler_t *r) {
-	if (!r->pending) return 0;
-	HIP_TRY(hipSetDevice(r->device));
-	r->pending = false;
-	HIP_TRY(hipEventSynchronize(r->ev[2]));
-	return 0;
-}
-
 extern "C" int jsmpeg_hip_resampler_resample(jsmpeg_hip_resampler_t *r, const void *const *pcm, const uint32_t *frames, const uint32_t *stream_numbers,
                                              uint32_t n_streams, uint32_t flags, void *hip_stream) {
 	g_err[0] = 0;
 	if (!r) return fail("resampler: NULL handle");
-	if (r->pending) return fail("resampler: a pass is in flight: jsmpeg_hip_resampler_sync (or a reader) settles it first");
+	if (jm_pass_idle(r->pass) < 0) return -1;
 	if (flags & ~(JSMPEG_HIP_RESAMPLE_END | JSMPEG_HIP_RESAMPLE_CHAIN)) return fail("resampler: unknown flags 0x%x", flags);
 	if (n_streams > r->cfg.max_streams) return fail("resampler: %u streams > max_streams %u", n_streams, r->cfg.max_streams);
 	if (n_streams && (!pcm || !frames)) return fail("resampler: NULL pcm or frames");
+	if (jm_pass_check_streams("resampler", pcm, frames, stream_numbers, n_streams, r->cfg.max_streams) < 0) return -1;
 	uint64_t in_frames = 0;
-	for (uint32_t i = 0; i < n_streams; i++) {
-		const uint32_t s = stream_numbers ? stream_numbers[i] : i;
-		if (s >= r->cfg.max_streams) return fail("resampler: stream_numbers[%u] = %u >= max_streams %u", i, s, r->cfg.max_streams);
-		if (stream_numbers && i && s <= stream_numbers[i - 1]) return fail("resampler: stream_numbers[] must ascend (stream_numbers[%u] = %u after %u)", i, s, stream_numbers[i - 1]);
-		if (frames[i] && !pcm[i]) return fail("resampler: pcm[%u] is NULL", i);
-		if (frames[i] && ((uintptr_t)pcm[i] & 3u)) return fail("resampler: pcm[%u] is not 4-byte aligned", i);
-		in_frames += frames[i];
-	}
+	for (uint32_t i = 0; i < n_streams; i++) in_frames += frames[i];
 	if (in_frames > r->cfg.max_frames) return fail("resampler: %llu frames > max_frames %u", (unsigned long long)in_frames, r->cfg.max_frames);
 	uint64_t total = 0;
 	const int rc = rs_plan_call(r->R, reinterpret_cast<const float *const *>(pcm), frames, stream_numbers, n_streams, flags, r->chain.data(), r->h_streams,
@@ -179,17 +160,16 @@ extern "C" int jsmpeg_hip_resampler_resample(jsmpeg_hip_resampler_t *r, const vo
 	if (total > r->cap) return fail("resampler: the call yields %llu frames, the buffer holds %llu: nothing was enqueued", (unsigned long long)total, (unsigned long long)r->cap);
 	uint32_t slots = 0;
 	for (uint32_t i = 0; i < n_streams; i++) slots = std::max(slots, r->h_streams[i].slots);
-	HIP_TRY(hipSetDevice(r->device));
 	hipStream_t st = (hipStream_t)hip_stream;
-	HIP_TRY(hipEventRecord(r->ev[0], st));
+	if (jm_pass_begin(r->pass, st) < 0) return -1;
 	if (slots) HIP_TRY(hipMemcpyAsync(r->d_streams, r->h_streams, sizeof(RsStream) * n_streams, hipMemcpyHostToDevice, st));
-	HIP_TRY(hipEventRecord(r->ev[1], st));
+	if (jm_pass_mark(r->pass, st) < 0) return -1;
 	if (slots) {
 		hipLaunchKernelGGL(k_resample, dim3((slots + RS_WG - 1) / RS_WG, (uint32_t)r->R.channels, n_streams), dim3(RS_WG), 0, st, r->R, r->d_streams, r->d_taps,
 		                   r->d_carry, r->d_part, r->d_out);
 		HIP_TRY(hipGetLastError());
 	}
-	HIP_TRY(hipEventRecord(r->ev[2], st));
+	if (jm_pass_end(r->pass, st) < 0) return -1;
 	std::fill(r->offset.begin(), r->offset.end(), 0); std::fill(r->count.begin(), r->count.end(), 0);
 	for (uint32_t i = 0; i < n_streams; i++) {
 		const uint32_t s = stream_numbers ? stream_numbers[i] : i;
@@ -197,34 +177,20 @@ extern "C" int jsmpeg_hip_resampler_resample(jsmpeg_hip_resampler_t *r, const vo
 	}
 	rs_plan_commit(r->R, frames, stream_numbers, n_streams, flags, r->chain.data());
 	r->total = total;
-	r->pending = true; r->have_pass = true;
+	r->pass.pending = true; r->pass.have_pass = true;
 	return 0;
 }
 
 extern "C" int jsmpeg_hip_resampler_sync(jsmpeg_hip_resampler_t *r) {
 	g_err[0] = 0;
 	if (!r) return fail("resampler: NULL handle");
-	return rs_settle(r);
+	return jm_pass_settle(r->pass);
 }
 
 extern "C" int jsmpeg_hip_resampler_query(jsmpeg_hip_resampler_t *r) {
 	g_err[0] = 0;
 	if (!r) return fail("resampler: NULL handle");
-	if (!r->pending) return 1;
-	HIP_TRY(hipSetDevice(r->device));
-	const hipError_t e = hipEventQuery(r->ev[2]);
-	if (e == hipSuccess) return 1;
-	if (e == hipErrorNotReady) return 0;
-	return fail("hipEventQuery: %s", hipGetErrorString(e));
-}
-
-/* the readers of the device's results: settle, then refuse a handle without a pass */
-static int rs_ready(jsmpeg_hip_resampler_t *r) {
-	g_err[0] = 0;
-	if (!r) return fail("resampler: NULL handle");
-	if (rs_settle(r) < 0) return -1;
-	if (!r->have_pass) return fail("resampler: nothing was resampled yet");
-	return 0;
+	return jm_pass_query(r->pass);
 }
 
 /* the address and the bytes are the plan's: answered without waiting, so that a consumer on the same HIP stream is enqueued
@@ -232,7 +198,7 @@ static int rs_ready(jsmpeg_hip_resampler_t *r) {
 extern "C" void *jsmpeg_hip_resampler_out(jsmpeg_hip_resampler_t *r, uint64_t *bytes) {
 	g_err[0] = 0;
 	if (!r) { fail("resampler: NULL handle"); return nullptr; }
-	if (!r->have_pass) { fail("resampler: nothing was resampled yet"); return nullptr; }
+	if (jm_pass_have(r->pass) < 0) return nullptr;
 	if (bytes) *bytes = r->total * rs_elem_bytes(r->R);
 	return r->d_out;
 }
@@ -241,8 +207,7 @@ extern "C" void *jsmpeg_hip_resampler_out(jsmpeg_hip_resampler_t *r, uint64_t *b
 extern "C" int jsmpeg_hip_resampler_stream_out(jsmpeg_hip_resampler_t *r, uint32_t stream, uint64_t *offset, uint64_t *count) {
 	g_err[0] = 0;
 	if (!r) return fail("resampler: NULL handle");
-	if (!r->have_pass) return fail("resampler: nothing was resampled yet");
-	if (stream >= r->cfg.max_streams) return fail("resampler: stream %u >= max_streams %u", stream, r->cfg.max_streams);
+	if (jm_pass_have(r->pass) < 0 || jm_pass_stream_bound("resampler", stream, r->cfg.max_streams) < 0) return -1;
 	if (offset) *offset = r->offset[stream];
 	if (count) *count = r->count[stream];
 	return 0;
@@ -251,28 +216,24 @@ extern "C" int jsmpeg_hip_resampler_stream_out(jsmpeg_hip_resampler_t *r, uint32
 extern "C" int jsmpeg_hip_resampler_chain_reset(jsmpeg_hip_resampler_t *r, uint32_t stream) {
 	g_err[0] = 0;
 	if (!r) return fail("resampler: NULL handle");
-	if (r->pending) return fail("resampler: a pass is in flight: jsmpeg_hip_resampler_sync (or a reader) settles it first");
-	if (stream != 0xffffffffu && stream >= r->cfg.max_streams) return fail("resampler: stream %u >= max_streams %u", stream, r->cfg.max_streams);
-	for (uint32_t s = 0; s < r->cfg.max_streams; s++)
-		if (stream == 0xffffffffu || stream == s) r->chain[s] = RsChain{ 0, 0, 0, 0 };
-	return 0;
+	return jm_pass_chain_reset(r->pass, "resampler", r->chain, stream);
 }
 
 extern "C" int jsmpeg_hip_resampler_chain_info(jsmpeg_hip_resampler_t *r, uint32_t stream, uint64_t out[3]) {
 	g_err[0] = 0;
 	if (!r) return fail("resampler: NULL handle");
 	if (!out) return fail("resampler: NULL out");
-	if (stream >= r->cfg.max_streams) return fail("resampler: stream %u >= max_streams %u", stream, r->cfg.max_streams);
+	if (jm_pass_stream_bound("resampler", stream, r->cfg.max_streams) < 0) return -1;
 	const RsChain &c = r->chain[stream];
 	out[0] = c.have; out[1] = c.have ? c.n_in : 0; out[2] = c.have ? c.n_out : 0;
 	return 0;
 }
 
 extern "C" int jsmpeg_hip_resampler_timings(jsmpeg_hip_resampler_t *r, float out_ms[2]) {
-	if (rs_ready(r) < 0) return -1;
+	g_err[0] = 0;
+	if (!r) return fail("resampler: NULL handle");
+	if (jm_pass_ready(r->pass) < 0) return -1;
 	if (!out_ms) return fail("resampler: NULL out_ms");
-	HIP_TRY(hipSetDevice(r->device));
-	HIP_TRY(hipEventElapsedTime(&out_ms[0], r->ev[1], r->ev[2]));
-	HIP_TRY(hipEventElapsedTime(&out_ms[1], r->ev[0], r->ev[2]));
-	return 0;
+	if (jm_pass_elapsed(r->pass, 1, 2, &out_ms[0]) < 0) return -1;
+	return jm_pass_elapsed(r->pass, 0, 2, &out_ms[1]);
 }

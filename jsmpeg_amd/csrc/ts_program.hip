@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "host_common.h"
+#include "pass_state.h"
 #include "jsmpeg_hip.h"
 #include "ts_prog.h"
 #include "ts_prog_sources.h"
@@ -202,7 +203,7 @@ static int tsp_check_table(const char *what, uint32_t pid, const uint32_t *strea
 struct jsmpeg_hip_ts_program_t {
 	jsmpeg_hip_ts_program_config_t cfg;
 	JmTspRule rule;
-	int device = 0;
+	JmPass pass{ "ts_program: a pass is in flight: jsmpeg_hip_ts_program_sync (or a reader) settles it first", "ts_program: nothing was muxed yet" };
 	uint32_t max_units = 0;
 	uint8_t *d_ts = nullptr;                                   /* the handle's own output */
 	uint8_t *out = nullptr;                                    /* where the calls write: d_ts or the caller's */
@@ -213,9 +214,7 @@ struct jsmpeg_hip_ts_program_t {
 	uint32_t *d_work = nullptr;
 	JmTspEdges *d_edges = nullptr;
 	uint32_t *d_state = nullptr, *d_tpl = nullptr;
-	uint32_t n_v = 0, n_a = 0;                                 /* of the last call */
-	bool pending = false, have_pass = false;
-	hipEvent_t ev[3] = { nullptr, nullptr, nullptr };          /* begin, behind the kernels, done */
+	uint32_t n_v = 0, n_a = 0;                                 /* of the last call; pass.ev[1]: behind the kernels */
 	std::vector<uint32_t> scratch_stream;
 	std::vector<uint64_t> scratch_ord, scratch_off;
 	std::vector<uint32_t> scratch_bytes, scratch_ord32;
@@ -230,13 +229,11 @@ static const JmTspPlaced *tsp_h_placed(const jsmpeg_hip_ts_program_t *p) {
 
 static void tsp_free(jsmpeg_hip_ts_program_t *p) {
 	if (!p) return;
-	hipSetDevice(p->device);
-	if (p->pending) hipEventSynchronize(p->ev[2]);
+	jm_pass_close(p->pass);
 	hipFree(p->d_ts); hipFree(p->d_units); hipFree(p->d_pts); hipFree(p->d_back); hipFree(p->d_work); hipFree(p->d_edges); hipFree(p->d_state); hipFree(p->d_tpl);
 	if (p->h_units) hipHostFree(p->h_units);
 	if (p->h_pts) hipHostFree(p->h_pts);
 	if (p->h_back) hipHostFree(p->h_back);
-	for (hipEvent_t v : p->ev) if (v) hipEventDestroy(v);
 	delete p;
 }
 
@@ -259,7 +256,7 @@ static int tsp_alloc(jsmpeg_hip_ts_program_t *p) {
 	HIP_TRY(hipMemset(p->d_state, 0, sizeof(uint32_t) * JM_TSP_STATE * ns));
 	HIP_TRY(jm_malloc(&p->d_tpl, sizeof(psi)));
 	HIP_TRY(hipMemcpy(p->d_tpl, psi, sizeof(psi), hipMemcpyHostToDevice));
-	for (hipEvent_t &v : p->ev) HIP_TRY(hipEventCreate(&v));
+	if (jm_pass_events(p->pass) < 0) return -1;
 	HIP_TRY(hipDeviceSynchronize());
 	p->out = p->d_ts; p->out_cap = p->cfg.max_ts_bytes;
 	return 0;
@@ -277,20 +274,17 @@ extern "C" jsmpeg_hip_ts_program_t *jsmpeg_hip_ts_program_create(const jsmpeg_hi
 	p->cfg = *config;
 	p->rule = tsp_rule(*config);
 	p->max_units = config->max_video_units + config->max_audio_units;
-	if (config->device >= 0 && hipSetDevice(config->device) != hipSuccess) { fail("hipSetDevice(%d) failed", config->device); delete p; return nullptr; }
-	if (hipGetDevice(&p->device) != hipSuccess) { fail("hipGetDevice failed"); delete p; return nullptr; }
+	if (jm_pass_open(p->pass, config->device) < 0) { delete p; return nullptr; }
 	if (tsp_alloc(p) != 0) { tsp_free(p); return nullptr; }
 	return p;
 }
 
 extern "C" void jsmpeg_hip_ts_program_destroy(jsmpeg_hip_ts_program_t *p) { tsp_free(p); }
 
-#define TSP_IN_FLIGHT "ts_program: a pass is in flight: jsmpeg_hip_ts_program_sync (or a reader) settles it first"
-
 extern "C" int jsmpeg_hip_ts_program_set_output(jsmpeg_hip_ts_program_t *p, void *dev_ts, uint64_t cap) {
 	g_err[0] = 0;
 	if (!p) return fail("ts_program: NULL handle");
-	if (p->pending) return fail(TSP_IN_FLIGHT);
+	if (jm_pass_idle(p->pass) < 0) return -1;
 	if ((uintptr_t)dev_ts & 3u) return fail("ts_program: dev_ts is not 4-byte aligned");
 	if (dev_ts && cap > 0xffffffffull * 4) return fail("ts_program: cap above 16 GiB");
 	p->out = dev_ts ? (uint8_t *)dev_ts : p->d_ts;
@@ -312,11 +306,11 @@ static int tsp_enqueue(jsmpeg_hip_ts_program_t *p, const uint8_t *src_v, const u
 	k_tsp_plan<<<dim3(1), dim3(256), 0, st>>>(t);
 	k_tsp_write<<<dim3(JM_TSP_WRITE_GRID), dim3(256), 0, st>>>(t);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(p->ev[1], st));
+	if (jm_pass_mark(p->pass, st) < 0) return -1;
 	HIP_TRY(hipMemcpyAsync(p->h_back, p->d_back, tsp_result_bytes(p->cfg.max_streams) + tsp_rank_bytes(p) + sizeof(JmTspPlaced) * n, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipEventRecord(p->ev[2], st));
+	if (jm_pass_end(p->pass, st) < 0) return -1;
 	p->n_v = n_v; p->n_a = n_a;
-	p->pending = true; p->have_pass = true;
+	p->pass.pending = true; p->pass.have_pass = true;
 	return 0;
 }
 
@@ -326,7 +320,7 @@ extern "C" int jsmpeg_hip_ts_program_mux(jsmpeg_hip_ts_program_t *p,
                                          void *hip_stream) {
 	g_err[0] = 0;
 	if (!p) return fail("ts_program: NULL handle");
-	if (p->pending) return fail(TSP_IN_FLIGHT);
+	if (jm_pass_idle(p->pass) < 0) return -1;
 	if (n_v > p->cfg.max_video_units) return fail("ts_program: %u video units > max_video_units %u", n_v, p->cfg.max_video_units);
 	if (n_a > p->cfg.max_audio_units) return fail("ts_program: %u audio units > max_audio_units %u", n_a, p->cfg.max_audio_units);
 	if (n_v && (!dev_video || !v_offset || !v_bytes || !v_pts)) return fail("ts_program: NULL video argument");
@@ -337,12 +331,11 @@ extern "C" int jsmpeg_hip_ts_program_mux(jsmpeg_hip_ts_program_t *p,
 	for (uint32_t i = 0; i < n_v; i++) payload += v_bytes[i];
 	for (uint32_t i = 0; i < n_a; i++) payload += a_bytes[i];
 	if (payload > 0xffffffffull * 4) return fail("ts_program: the call's units hold more than 16 GiB");
-	HIP_TRY(hipSetDevice(p->device));
 	hipStream_t st = (hipStream_t)hip_stream;
 	JmTsUnit *hv = p->h_units, *ha = p->h_units + p->cfg.max_video_units;
 	for (uint32_t i = 0; i < n_v; i++) { hv[i].off = v_offset[i]; hv[i].bytes = v_bytes[i]; hv[i].stream = v_stream ? v_stream[i] : 0u; hv[i].pts = v_pts[i]; }
 	for (uint32_t i = 0; i < n_a; i++) { ha[i].off = a_offset[i]; ha[i].bytes = a_bytes[i]; ha[i].stream = a_stream ? a_stream[i] : 0u; ha[i].pts = a_pts[i]; }
-	HIP_TRY(hipEventRecord(p->ev[0], st));
+	if (jm_pass_begin(p->pass, st) < 0) return -1;
 	if (n_v) HIP_TRY(hipMemcpyAsync(p->d_units, hv, sizeof(JmTsUnit) * n_v, hipMemcpyHostToDevice, st));
 	if (n_a) HIP_TRY(hipMemcpyAsync(p->d_units + p->cfg.max_video_units, ha, sizeof(JmTsUnit) * n_a, hipMemcpyHostToDevice, st));
 	return tsp_enqueue(p, (const uint8_t *)dev_video, (const uint8_t *)dev_audio, n_v, n_a, nullptr, st);
@@ -352,7 +345,7 @@ extern "C" int jsmpeg_hip_ts_program_mux_encoders(jsmpeg_hip_ts_program_t *p, js
                                                   jsmpeg_hip_mp2_encoder_t *mp2enc, const uint64_t *a_pts, void *hip_stream) {
 	g_err[0] = 0;
 	if (!p) return fail("ts_program: NULL handle");
-	if (p->pending) return fail(TSP_IN_FLIGHT);
+	if (jm_pass_idle(p->pass) < 0) return -1;
 	JmTspVideoSource vs;
 	JmTspAudioSource as;
 	memset(&vs, 0, sizeof(vs)); memset(&as, 0, sizeof(as));
@@ -362,7 +355,7 @@ extern "C" int jsmpeg_hip_ts_program_mux_encoders(jsmpeg_hip_ts_program_t *p, js
 	JmTsUnit *ha = p->h_units + mv;
 	if (enc) {
 		if (jm_enc_tsp_source(enc, &vs, p->scratch_stream.data(), p->scratch_ord32.data(), mv) < 0) return -1;
-		if (vs.device != p->device) return fail("ts_program: the encoder lives on device %d, the program handle on %d", vs.device, p->device);
+		if (vs.device != p->pass.device) return fail("ts_program: the encoder lives on device %d, the program handle on %d", vs.device, p->pass.device);
 		uint32_t num, den;
 		jm_ts_frame_rate(vs.frame_rate_code, &num, &den);
 		for (uint32_t k = 0; k < vs.count; k++) p->h_pts[k] = v_pts ? v_pts[k] : (uint64_t)p->scratch_ord32[k] * 90000u * den / num;
@@ -370,7 +363,7 @@ extern "C" int jsmpeg_hip_ts_program_mux_encoders(jsmpeg_hip_ts_program_t *p, js
 	}
 	if (mp2enc) {
 		if (jm_mp2e_tsp_source(mp2enc, &as, p->scratch_off.data(), p->scratch_bytes.data(), p->scratch_stream.data(), p->scratch_ord.data(), ma) < 0) return -1;
-		if (as.device != p->device) return fail("ts_program: the MP2 encoder lives on device %d, the program handle on %d", as.device, p->device);
+		if (as.device != p->pass.device) return fail("ts_program: the MP2 encoder lives on device %d, the program handle on %d", as.device, p->pass.device);
 		for (uint32_t k = 0; k < as.count; k++) {
 			ha[k].off = p->scratch_off[k]; ha[k].bytes = p->scratch_bytes[k]; ha[k].stream = p->scratch_stream[k];
 			ha[k].pts = a_pts ? a_pts[k] : p->scratch_ord[k] * 1152u * 90000u / as.sample_rate;
@@ -378,9 +371,8 @@ extern "C" int jsmpeg_hip_ts_program_mux_encoders(jsmpeg_hip_ts_program_t *p, js
 		for (uint32_t k = 0; k < as.count; k++) { p->scratch_stream[k] = ha[k].stream; p->scratch_ord[k] = ha[k].pts; }
 		if (tsp_check_table("audio", p->rule.pid[1], p->scratch_stream.data(), p->scratch_ord.data(), as.count, p->cfg.max_streams) < 0) return -1;
 	}
-	HIP_TRY(hipSetDevice(p->device));
 	hipStream_t st = (hipStream_t)hip_stream;
-	HIP_TRY(hipEventRecord(p->ev[0], st));
+	if (jm_pass_begin(p->pass, st) < 0) return -1;
 	if (vs.count) {
 		HIP_TRY(hipMemcpyAsync(p->d_pts, p->h_pts, sizeof(uint64_t) * vs.count, hipMemcpyHostToDevice, st));
 		if (jm_enc_tsp_units(enc, p->d_units, p->d_pts, hip_stream) < 0) return -1;
@@ -389,21 +381,11 @@ extern "C" int jsmpeg_hip_ts_program_mux_encoders(jsmpeg_hip_ts_program_t *p, js
 	return tsp_enqueue(p, vs.d_es, as.d_es, vs.count, as.count, vs.count ? vs.d_result : nullptr, st);
 }
 
-/* waits for the pass in flight */
-static int tsp_settle(jsmpeg_hip_ts_program_t *p) {
-	if (!p->pending) return 0;
-	HIP_TRY(hipSetDevice(p->device));
-	p->pending = false;
-	HIP_TRY(hipEventSynchronize(p->ev[2]));
-	return 0;
-}
-
 /* settles, then the verdict of the last call */
 static int tsp_ready(jsmpeg_hip_ts_program_t *p) {
 	g_err[0] = 0;
 	if (!p) return fail("ts_program: NULL handle");
-	if (tsp_settle(p) < 0) return -1;
-	if (!p->have_pass) return fail("ts_program: nothing was muxed yet");
+	if (jm_pass_ready(p->pass) < 0) return -1;
 	const uint64_t *r = tsp_h_result(p);
 	if (r[1] == 1) return fail("ts_program: the call needs %llu bytes, the output holds %llu: nothing was written, the state stays", (unsigned long long)r[0], (unsigned long long)p->out_cap);
 	if (r[1] == 2) return fail("ts_program: the video encoder's call overflowed its max_es_bytes: there is no program, the state stays");
@@ -412,19 +394,14 @@ static int tsp_ready(jsmpeg_hip_ts_program_t *p) {
 
 extern "C" int jsmpeg_hip_ts_program_sync(jsmpeg_hip_ts_program_t *p) {
 	if (!p) { g_err[0] = 0; return fail("ts_program: NULL handle"); }
-	if (!p->have_pass) { g_err[0] = 0; return 0; }
+	if (!p->pass.have_pass) { g_err[0] = 0; return 0; }
 	return tsp_ready(p);
 }
 
 extern "C" int jsmpeg_hip_ts_program_query(jsmpeg_hip_ts_program_t *p) {
 	g_err[0] = 0;
 	if (!p) return fail("ts_program: NULL handle");
-	if (!p->pending) return 1;
-	HIP_TRY(hipSetDevice(p->device));
-	const hipError_t r = hipEventQuery(p->ev[2]);
-	if (r == hipSuccess) return 1;
-	if (r == hipErrorNotReady) return 0;
-	return fail("hipEventQuery: %s", hipGetErrorString(r));
+	return jm_pass_query(p->pass);
 }
 
 extern "C" void *jsmpeg_hip_ts_program_ts(jsmpeg_hip_ts_program_t *p, uint64_t *total_bytes) {
@@ -435,7 +412,7 @@ extern "C" void *jsmpeg_hip_ts_program_ts(jsmpeg_hip_ts_program_t *p, uint64_t *
 
 extern "C" int jsmpeg_hip_ts_program_stream_range(jsmpeg_hip_ts_program_t *p, uint32_t stream, uint64_t *begin, uint64_t *end) {
 	if (tsp_ready(p) < 0) return -1;
-	if (stream >= p->cfg.max_streams) return fail("ts_program: stream %u >= max_streams %u", stream, p->cfg.max_streams);
+	if (jm_pass_stream_bound("ts_program", stream, p->cfg.max_streams) < 0) return -1;
 	if (begin) *begin = tsp_h_result(p)[4 + stream];
 	if (end) *end = tsp_h_result(p)[4 + p->cfg.max_streams + stream];
 	return 0;
@@ -464,7 +441,7 @@ extern "C" int64_t jsmpeg_hip_ts_program_read(jsmpeg_hip_ts_program_t *p, uint32
 	}
 	const uint64_t k = std::min(n, cap);
 	if (k && host) {
-		HIP_TRY(hipSetDevice(p->device));
+		HIP_TRY(hipSetDevice(p->pass.device));
 		HIP_TRY(hipMemcpy(host, p->out + b, k, hipMemcpyDeviceToHost));
 	}
 	return (int64_t)n;
@@ -475,8 +452,8 @@ extern "C" int jsmpeg_hip_ts_program_state(jsmpeg_hip_ts_program_t *p, uint32_t 
 	g_err[0] = 0;
 	if (!p) return fail("ts_program: NULL handle");
 	if (!out) return fail("ts_program: NULL out");
-	if (stream >= p->cfg.max_streams) return fail("ts_program: stream %u >= max_streams %u", stream, p->cfg.max_streams);
-	if (tsp_settle(p) < 0) return -1;
+	if (jm_pass_stream_bound("ts_program", stream, p->cfg.max_streams) < 0) return -1;
+	if (jm_pass_settle(p->pass) < 0) return -1;
 	const uint32_t *after = reinterpret_cast<const uint32_t *>(tsp_h_result(p) + 4 + 2 * (size_t)p->cfg.max_streams) + JM_TSP_STATE * (size_t)p->cfg.max_streams;
 	for (uint32_t i = 0; i < JM_TSP_STATE; i++) out[i] = after[JM_TSP_STATE * stream + i];   /* (zeros before the first call; reset and set_state keep the copy current) */
 	return 0;
@@ -485,9 +462,9 @@ extern "C" int jsmpeg_hip_ts_program_state(jsmpeg_hip_ts_program_t *p, uint32_t 
 extern "C" int jsmpeg_hip_ts_program_reset(jsmpeg_hip_ts_program_t *p, uint32_t stream) {
 	g_err[0] = 0;
 	if (!p) return fail("ts_program: NULL handle");
-	if (p->pending) return fail(TSP_IN_FLIGHT);
-	if (stream != UINT32_MAX && stream >= p->cfg.max_streams) return fail("ts_program: stream %u >= max_streams %u", stream, p->cfg.max_streams);
-	HIP_TRY(hipSetDevice(p->device));
+	if (jm_pass_idle(p->pass) < 0) return -1;
+	if (stream != UINT32_MAX && jm_pass_stream_bound("ts_program", stream, p->cfg.max_streams) < 0) return -1;
+	HIP_TRY(hipSetDevice(p->pass.device));
 	const size_t ns = p->cfg.max_streams, first = stream == UINT32_MAX ? 0 : stream, count = stream == UINT32_MAX ? ns : 1;
 	HIP_TRY(hipMemset(p->d_state + JM_TSP_STATE * first, 0, sizeof(uint32_t) * JM_TSP_STATE * count));
 	HIP_TRY(hipDeviceSynchronize());
@@ -500,11 +477,11 @@ extern "C" int jsmpeg_hip_ts_program_set_state(jsmpeg_hip_ts_program_t *p, uint3
 	g_err[0] = 0;
 	if (!p) return fail("ts_program: NULL handle");
 	if (!in) return fail("ts_program: NULL in");
-	if (p->pending) return fail(TSP_IN_FLIGHT);
-	if (stream >= p->cfg.max_streams) return fail("ts_program: stream %u >= max_streams %u", stream, p->cfg.max_streams);
+	if (jm_pass_idle(p->pass) < 0) return -1;
+	if (jm_pass_stream_bound("ts_program", stream, p->cfg.max_streams) < 0) return -1;
 	for (uint32_t i = 0; i < JM_TSP_STATE; i++)
 		if (in[i] > (i == 4u ? 1u : 15u)) return fail("ts_program: state word %u = %u (counters are 0 .. 15, started 0 or 1)", i, in[i]);
-	HIP_TRY(hipSetDevice(p->device));
+	HIP_TRY(hipSetDevice(p->pass.device));
 	HIP_TRY(hipMemcpy(p->d_state + JM_TSP_STATE * (size_t)stream, in, sizeof(uint32_t) * JM_TSP_STATE, hipMemcpyHostToDevice));
 	const size_t ns = p->cfg.max_streams;
 	uint32_t *after = reinterpret_cast<uint32_t *>(reinterpret_cast<uint64_t *>(p->h_back) + 4 + 2 * ns) + JM_TSP_STATE * ns;
@@ -515,13 +492,10 @@ extern "C" int jsmpeg_hip_ts_program_set_state(jsmpeg_hip_ts_program_t *p, uint3
 extern "C" int jsmpeg_hip_ts_program_timings(jsmpeg_hip_ts_program_t *p, float out_ms[2]) {
 	g_err[0] = 0;
 	if (!p) return fail("ts_program: NULL handle");
-	if (tsp_settle(p) < 0) return -1;
-	if (!p->have_pass) return fail("ts_program: nothing was muxed yet");
+	if (jm_pass_ready(p->pass) < 0) return -1;
 	if (!out_ms) return fail("ts_program: NULL out_ms");
-	HIP_TRY(hipSetDevice(p->device));
-	HIP_TRY(hipEventElapsedTime(&out_ms[0], p->ev[0], p->ev[1]));
-	HIP_TRY(hipEventElapsedTime(&out_ms[1], p->ev[0], p->ev[2]));
-	return 0;
+	if (jm_pass_elapsed(p->pass, 0, 1, &out_ms[0]) < 0) return -1;
+	return jm_pass_elapsed(p->pass, 0, 2, &out_ms[1]);
 }
 
 extern "C" uint64_t jsmpeg_hip_ts_program_bound(uint64_t v_bytes, uint32_t n_v, uint64_t a_bytes, uint32_t n_a, uint32_t streams) {

@@ -7,20 +7,18 @@ import ctypes
 
 import numpy as np
 
+from . import _pass
 from . import batch as _batch
+from ._pass import c_int, p_f32, p_u64, u32, u64, vp
 
 END = 1
 CHAIN = 2        # continue the call's streams where their last chained call left them (JSMPEG_HIP_LOGMEL_CHAIN)
-
-SYMBOLS = ("jsmpeg_hip_logmel_create", "jsmpeg_hip_logmel_destroy", "jsmpeg_hip_logmel_features", "jsmpeg_hip_logmel_sync", "jsmpeg_hip_logmel_query",
-           "jsmpeg_hip_logmel_out", "jsmpeg_hip_logmel_stream_out", "jsmpeg_hip_logmel_chain_reset", "jsmpeg_hip_logmel_chain_info",
-           "jsmpeg_hip_logmel_timings", "jsmpeg_hip_logmel_plan", "jsmpeg_hip_logmel_basis", "jsmpeg_hip_logmel_filters")
 
 SCALES = {"power": 0, "log": 1, "log10": 2, "db": 3, "whisper": 4}
 LAYOUTS = {"mel_major": 0, "time_major": 1}
 MEL_SCALES = {"htk": 0, "slaney": 1}
 MEL_NORMS = {"none": 0, None: 0, "slaney": 1}
-DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}
+DTYPES = _pass.DTYPES
 
 
 class LogMelConfig(ctypes.Structure):
@@ -31,6 +29,24 @@ class LogMelConfig(ctypes.Structure):
                 ("device", ctypes.c_int32)]
 
 
+_cfg = ctypes.POINTER(LogMelConfig)
+SIGNATURES = {
+    "jsmpeg_hip_logmel_create": (vp, [_cfg]),
+    "jsmpeg_hip_logmel_destroy": (None, [vp]),
+    "jsmpeg_hip_logmel_features": (c_int, [vp, vp, vp, vp, u32, u32, vp]),
+    "jsmpeg_hip_logmel_sync": (c_int, [vp]),
+    "jsmpeg_hip_logmel_query": (c_int, [vp]),
+    "jsmpeg_hip_logmel_out": (vp, [vp, p_u64]),
+    "jsmpeg_hip_logmel_stream_out": (c_int, [vp, u32, p_u64, p_u64]),
+    "jsmpeg_hip_logmel_chain_reset": (c_int, [vp, u32]),
+    "jsmpeg_hip_logmel_chain_info": (c_int, [vp, u32, p_u64]),
+    "jsmpeg_hip_logmel_timings": (c_int, [vp, p_f32]),
+    "jsmpeg_hip_logmel_plan": (c_int, [_cfg, u64, p_u64]),
+    "jsmpeg_hip_logmel_basis": (c_int, [_cfg, vp]),
+    "jsmpeg_hip_logmel_filters": (c_int, [_cfg, vp, vp]),
+}
+SYMBOLS = tuple(SIGNATURES)
+
 _bound = None
 
 
@@ -38,37 +54,7 @@ def lib():
     """libjsmpeg_hip with the part-12 argtypes set"""
     global _bound
     if _bound is None:
-        L = _batch.lib()
-        vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
-        cfg = ctypes.POINTER(LogMelConfig)
-        L.jsmpeg_hip_logmel_create.restype = vp
-        L.jsmpeg_hip_logmel_create.argtypes = [cfg]
-        L.jsmpeg_hip_logmel_destroy.restype = None
-        L.jsmpeg_hip_logmel_destroy.argtypes = [vp]
-        L.jsmpeg_hip_logmel_features.restype = ctypes.c_int
-        L.jsmpeg_hip_logmel_features.argtypes = [vp, vp, vp, vp, u32, u32, vp]
-        for name in ("jsmpeg_hip_logmel_sync", "jsmpeg_hip_logmel_query"):
-            getattr(L, name).restype = ctypes.c_int
-            getattr(L, name).argtypes = [vp]
-        L.jsmpeg_hip_logmel_out.restype = vp
-        L.jsmpeg_hip_logmel_out.argtypes = [vp, ctypes.POINTER(u64)]
-        L.jsmpeg_hip_logmel_stream_out.restype = ctypes.c_int
-        L.jsmpeg_hip_logmel_stream_out.argtypes = [vp, u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
-        L.jsmpeg_hip_logmel_chain_reset.restype = ctypes.c_int
-        L.jsmpeg_hip_logmel_chain_reset.argtypes = [vp, u32]
-        L.jsmpeg_hip_logmel_chain_info.restype = ctypes.c_int
-        L.jsmpeg_hip_logmel_chain_info.argtypes = [vp, u32, ctypes.POINTER(u64)]
-        L.jsmpeg_hip_logmel_timings.restype = ctypes.c_int
-        L.jsmpeg_hip_logmel_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-        L.jsmpeg_hip_logmel_plan.restype = ctypes.c_int
-        L.jsmpeg_hip_logmel_plan.argtypes = [cfg, u64, ctypes.POINTER(u64)]
-        L.jsmpeg_hip_logmel_basis.restype = ctypes.c_int
-        L.jsmpeg_hip_logmel_basis.argtypes = [cfg, vp]
-        L.jsmpeg_hip_logmel_filters.restype = ctypes.c_int
-        L.jsmpeg_hip_logmel_filters.argtypes = [cfg, vp, vp]
-        L.jsmpeg_hip_device_read.restype = ctypes.c_int
-        L.jsmpeg_hip_device_read.argtypes = [vp, vp, u64]
-        _bound = L
+        _bound = _pass.bind(_pass.lib(), SIGNATURES)
     return _bound
 
 
@@ -123,55 +109,28 @@ def filters(**config):
     return fb, rg
 
 
-class LogMel:
+class LogMel(_pass.RowPass):
     """Float32 mono PCM on the device -> log-mel features on the device.  chain=True on a call continues its streams -- the
     stream NUMBER is a stream's identity from call to call -- and the pieces concatenated are bit for bit the frames of one
-    call.  end=True ends the streams: the reflection at the end and the last frames come out."""
+    call.  end=True ends the streams: the reflection at the end and the last frames come out.  stream_out and counts: the
+    element index of a stream's first row and its frames."""
+    PREFIX = "jsmpeg_hip_logmel_"
 
     def __init__(self, sample_rate=16000, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=0.0, mel_scale="slaney", mel_norm="slaney", window=None,
                  floor=1e-10, scale="log10", layout="mel_major", dtype="float32", max_streams=1, max_samples=1, row=None, device=-1):
-        self.L = lib()
         self.config = dict(sample_rate=sample_rate, n_fft=n_fft, hop=hop, n_mels=n_mels, f_min=f_min, f_max=f_max, mel_scale=mel_scale, mel_norm=mel_norm,
                            window=window, floor=floor, scale=scale, layout=layout, dtype=dtype, max_streams=max_streams, max_samples=max_samples, row=row,
                            device=device)
         cfg, _w = _config(**self.config)
-        self.h = self.L.jsmpeg_hip_logmel_create(ctypes.byref(cfg))
-        if not self.h:
-            raise RuntimeError("jsmpeg_hip_logmel_create: " + _batch.last_error())
+        self._open(lib(), SIGNATURES, cfg)
         self.n_fft, self.hop, self.n_mels, self.scale, self.layout, self.dtype = n_fft, hop, n_mels, scale, layout, dtype
         self.max_streams, self.max_samples = max_streams, max_samples
         self.row = plan(**self.config)["row"]
         self._numbers = []
         self._keep = None
 
-    def _ok(self, rc):
-        if rc < 0:
-            raise RuntimeError(_batch.last_error())
-        return rc
-
-    def close(self):
-        if self.h:
-            self.L.jsmpeg_hip_logmel_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
     def _enqueue(self, ptrs, samples, streams, chain, end, stream):
-        n = len(ptrs)
-        cnt = np.ascontiguousarray(samples, dtype=np.uint32)
-        if cnt.shape != (n,):
-            raise ValueError("counts: one sample count per stream")
-        st = None if streams is None else np.ascontiguousarray(streams, dtype=np.uint32)
-        if st is not None and st.shape != (n,):
-            raise ValueError("streams: one stream number per stream")
-        arr = (ctypes.c_void_p * max(1, n))(*[int(p) if p else None for p in ptrs])
-        self._ok(self.L.jsmpeg_hip_logmel_features(self.h, arr, cnt.ctypes.data, None if st is None else st.ctypes.data, n,
-                                                   (END if end else 0) | (CHAIN if chain else 0), stream))
-        self._numbers = list(range(n)) if st is None else [int(v) for v in st]
+        self._submit("features", "counts: one sample count per stream", ptrs, samples, streams, chain, end, stream)
 
     def features(self, source, counts=None, streams=None, chain=False, end=None, stream=None, channel=0):
         """source: a Resampler whose last call was form="waveform", dtype="float32" -- read in place on the device, nothing is
@@ -190,7 +149,7 @@ class LogMel:
             if counts is not None and counts != "row":
                 raise ValueError("features: counts is None or 'row' for a Resampler")
             base = source.device_out()[0]
-            outs = [source.stream_out(s) for s in source._numbers]
+            outs = [source.stream_out(s) for s in source.numbers()]
             ptrs = [base + (o + channel * source.row) * 4 for o, _ in outs]
             self._enqueue(ptrs, [source.row if counts == "row" else c for _, c in outs], streams, chain, end, stream)
             self._keep = source
@@ -211,32 +170,6 @@ class LogMel:
         self._enqueue([x.data_ptr() + i * n * 4 if n else 0 for i in range(s)], cnt, streams, chain, end, torch.cuda.current_stream(x.device).cuda_stream)
         self._keep = x          # the tensor stays alive until the next call
 
-    def sync(self):
-        self._ok(self.L.jsmpeg_hip_logmel_sync(self.h))
-
-    def query(self):
-        """True once the pass in flight has finished on the device; never waits"""
-        return bool(self._ok(self.L.jsmpeg_hip_logmel_query(self.h)))
-
-    def stream_out(self, stream):
-        """(offset, count) of stream NUMBER `stream` in the last call's buffer: the element index of its first row and its
-        frames.  Answered without waiting."""
-        o, c = ctypes.c_uint64(), ctypes.c_uint64()
-        self._ok(self.L.jsmpeg_hip_logmel_stream_out(self.h, stream, ctypes.byref(o), ctypes.byref(c)))
-        return int(o.value), int(c.value)
-
-    def counts(self):
-        """frames of every stream of the last call, in call order"""
-        return [self.stream_out(s)[1] for s in self._numbers]
-
-    def device_out(self):
-        """(device address, bytes) of the last call's buffer: closed form, nothing is waited for"""
-        total = ctypes.c_uint64()
-        p = self.L.jsmpeg_hip_logmel_out(self.h, ctypes.byref(total))
-        if not p:
-            raise RuntimeError(_batch.last_error())
-        return p, int(total.value)
-
     def shape(self):
         n = len(self._numbers)
         return (n, self.n_mels, self.row) if self.layout == "mel_major" else (n, self.row, self.n_mels)
@@ -244,41 +177,8 @@ class LogMel:
     def tensor(self):
         """the last call's features as a torch tensor OVER the device buffer: no copy, valid until the handle's next call.
         Settles the pass, so the tensor is safe on any torch stream."""
-        import torch
-        self.sync()
-        p, total = self.device_out()
-        shape = self.shape()
-        dt = {"float32": torch.float32, "float16": torch.float16, "bfloat16": torch.bfloat16}[self.dtype]
-        if not shape[0]:
-            return torch.empty(shape, dtype=dt, device="cuda")
-        typestr = "<f4" if self.dtype == "float32" else ("<f2" if self.dtype == "float16" else "<i2")
-
-        class _Span:
-            __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (p, False), "version": 2}
-        assert total == shape[0] * shape[1] * shape[2] * (4 if self.dtype == "float32" else 2)
-        t = torch.as_tensor(_Span(), device="cuda")
-        return t.view(torch.bfloat16) if self.dtype == "bfloat16" else t
+        return self._tensor(self.shape())
 
     def read(self):
         """the last call's features on the host (bfloat16 as its uint16 bits)"""
-        self.sync()
-        p, total = self.device_out()
-        out = np.zeros(self.shape(), {"float32": np.float32, "float16": np.float16, "bfloat16": np.uint16}[self.dtype])
-        if total:
-            self._ok(self.L.jsmpeg_hip_device_read(out.ctypes.data, p, total))
-        return out
-
-    def chain_reset(self, stream=None):
-        """ends the chain of `stream` (None: of every stream): its next chained call starts from nothing"""
-        self._ok(self.L.jsmpeg_hip_logmel_chain_reset(self.h, 0xffffffff if stream is None else stream))
-
-    def chain_info(self, stream):
-        """(whether `stream` has chain state, samples it has taken, frames it has made)"""
-        out = (ctypes.c_uint64 * 3)()
-        self._ok(self.L.jsmpeg_hip_logmel_chain_info(self.h, stream, out))
-        return bool(out[0]), int(out[1]), int(out[2])
-
-    def timings(self):
-        ms = (ctypes.c_float * 2)()
-        self._ok(self.L.jsmpeg_hip_logmel_timings(self.h, ms))
-        return dict(kernel_ms=float(ms[0]), total_ms=float(ms[1]))
+        return self._host(self.shape())

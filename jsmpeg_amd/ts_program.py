@@ -7,20 +7,15 @@ import ctypes
 
 import numpy as np
 
+from . import _pass
 from . import batch as _batch
+from ._pass import c_int, i64, p_f32, p_u32, p_u64, u32, u64, vp
 
 PSI = 1
 PCR = 2
 NO_PID = 0x1fff
 VIDEO, AUDIO = 0, 1
 ALL = 0xffffffff
-
-SYMBOLS = ("jsmpeg_hip_ts_program_create", "jsmpeg_hip_ts_program_destroy", "jsmpeg_hip_ts_program_set_output", "jsmpeg_hip_ts_program_mux",
-           "jsmpeg_hip_ts_program_mux_encoders", "jsmpeg_hip_ts_program_sync", "jsmpeg_hip_ts_program_query", "jsmpeg_hip_ts_program_ts",
-           "jsmpeg_hip_ts_program_stream_range", "jsmpeg_hip_ts_program_unit_range", "jsmpeg_hip_ts_program_read", "jsmpeg_hip_ts_program_state",
-           "jsmpeg_hip_ts_program_reset", "jsmpeg_hip_ts_program_timings", "jsmpeg_hip_ts_program_mux_host", "jsmpeg_hip_ts_program_bound",
-           "jsmpeg_hip_ts_program_psi", "jsmpeg_hip_ts_program_set_state")
-
 
 class TsProgramConfig(ctypes.Structure):
     _fields_ = [("max_streams", ctypes.c_uint32), ("max_video_units", ctypes.c_uint32), ("max_audio_units", ctypes.c_uint32),
@@ -36,6 +31,29 @@ def config(max_streams=1, max_video_units=1, max_audio_units=1, max_ts_bytes=188
                            audio_stream_id, program_number, transport_stream_id, (PSI if psi else 0) | (PCR if pcr else 0), pcr_lead_90k, device)
 
 
+_cfg = ctypes.POINTER(TsProgramConfig)
+SIGNATURES = {
+    "jsmpeg_hip_ts_program_create": (vp, [_cfg]),
+    "jsmpeg_hip_ts_program_destroy": (None, [vp]),
+    "jsmpeg_hip_ts_program_set_output": (c_int, [vp, vp, u64]),
+    "jsmpeg_hip_ts_program_mux": (c_int, [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp]),
+    "jsmpeg_hip_ts_program_mux_encoders": (c_int, [vp, vp, vp, vp, vp, vp]),
+    "jsmpeg_hip_ts_program_sync": (c_int, [vp]),
+    "jsmpeg_hip_ts_program_query": (c_int, [vp]),
+    "jsmpeg_hip_ts_program_ts": (vp, [vp, p_u64]),
+    "jsmpeg_hip_ts_program_stream_range": (c_int, [vp, u32, p_u64, p_u64]),
+    "jsmpeg_hip_ts_program_unit_range": (c_int, [vp, u32, u32, p_u64, p_u32, p_u32]),
+    "jsmpeg_hip_ts_program_read": (i64, [vp, u32, vp, u64]),
+    "jsmpeg_hip_ts_program_state": (c_int, [vp, u32, p_u32]),
+    "jsmpeg_hip_ts_program_reset": (c_int, [vp, u32]),
+    "jsmpeg_hip_ts_program_timings": (c_int, [vp, p_f32]),
+    "jsmpeg_hip_ts_program_mux_host": (i64, [_cfg, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, u64, vp, vp]),
+    "jsmpeg_hip_ts_program_bound": (u64, [u64, u32, u64, u32, u32]),
+    "jsmpeg_hip_ts_program_psi": (c_int, [_cfg, vp]),
+    "jsmpeg_hip_ts_program_set_state": (c_int, [vp, u32, p_u32]),
+}
+SYMBOLS = tuple(SIGNATURES)
+
 _bound = None
 
 
@@ -43,45 +61,7 @@ def lib():
     """libjsmpeg_hip with the part-10 argtypes set"""
     global _bound
     if _bound is None:
-        L = _batch.lib()
-        vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
-        cfg = ctypes.POINTER(TsProgramConfig)
-        L.jsmpeg_hip_ts_program_create.restype = vp
-        L.jsmpeg_hip_ts_program_create.argtypes = [cfg]
-        L.jsmpeg_hip_ts_program_destroy.restype = None
-        L.jsmpeg_hip_ts_program_destroy.argtypes = [vp]
-        L.jsmpeg_hip_ts_program_set_output.restype = ctypes.c_int
-        L.jsmpeg_hip_ts_program_set_output.argtypes = [vp, vp, u64]
-        L.jsmpeg_hip_ts_program_mux.restype = ctypes.c_int
-        L.jsmpeg_hip_ts_program_mux.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp]
-        L.jsmpeg_hip_ts_program_mux_encoders.restype = ctypes.c_int
-        L.jsmpeg_hip_ts_program_mux_encoders.argtypes = [vp, vp, vp, vp, vp, vp]
-        for name in ("jsmpeg_hip_ts_program_sync", "jsmpeg_hip_ts_program_query"):
-            getattr(L, name).restype = ctypes.c_int
-            getattr(L, name).argtypes = [vp]
-        L.jsmpeg_hip_ts_program_ts.restype = vp
-        L.jsmpeg_hip_ts_program_ts.argtypes = [vp, ctypes.POINTER(u64)]
-        L.jsmpeg_hip_ts_program_stream_range.restype = ctypes.c_int
-        L.jsmpeg_hip_ts_program_stream_range.argtypes = [vp, u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
-        L.jsmpeg_hip_ts_program_unit_range.restype = ctypes.c_int
-        L.jsmpeg_hip_ts_program_unit_range.argtypes = [vp, u32, u32, ctypes.POINTER(u64), ctypes.POINTER(u32), ctypes.POINTER(u32)]
-        L.jsmpeg_hip_ts_program_read.restype = ctypes.c_int64
-        L.jsmpeg_hip_ts_program_read.argtypes = [vp, u32, vp, u64]
-        L.jsmpeg_hip_ts_program_state.restype = ctypes.c_int
-        L.jsmpeg_hip_ts_program_state.argtypes = [vp, u32, ctypes.POINTER(u32)]
-        L.jsmpeg_hip_ts_program_set_state.restype = ctypes.c_int
-        L.jsmpeg_hip_ts_program_set_state.argtypes = [vp, u32, ctypes.POINTER(u32)]
-        L.jsmpeg_hip_ts_program_reset.restype = ctypes.c_int
-        L.jsmpeg_hip_ts_program_reset.argtypes = [vp, u32]
-        L.jsmpeg_hip_ts_program_timings.restype = ctypes.c_int
-        L.jsmpeg_hip_ts_program_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-        L.jsmpeg_hip_ts_program_mux_host.restype = ctypes.c_int64
-        L.jsmpeg_hip_ts_program_mux_host.argtypes = [cfg, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u32, vp, vp, u64, vp, vp]
-        L.jsmpeg_hip_ts_program_bound.restype = u64
-        L.jsmpeg_hip_ts_program_bound.argtypes = [u64, u32, u64, u32, u32]
-        L.jsmpeg_hip_ts_program_psi.restype = ctypes.c_int
-        L.jsmpeg_hip_ts_program_psi.argtypes = [cfg, vp]
-        _bound = L
+        _bound = _pass.bind(_pass.lib(), SIGNATURES)
     return _bound
 
 
@@ -148,45 +128,28 @@ def program_mux_host(cfg, video=None, v_ranges=(), v_pts=(), v_streams=None, aud
     return out[:got], {s: (int(sb[s]), int(se[s])) for s in present}, [[int(w) for w in row] for row in st]
 
 
-class TsProgram:
+class TsProgram(_pass.Pass):
     """One program per stream number out of two unit tables, on the device.  A call is a pure enqueue; sync() or any reader
     settles it.  The continuity counters of PAT, PMT, video and audio and the `started` word of every stream number live on
     the device and go on from call to call: the pieces of a stream, concatenated in call order, are one valid stream."""
+    PREFIX = "jsmpeg_hip_ts_program_"
+    TIMINGS = ("mux_ms", "total_ms")
 
     def __init__(self, cfg):
-        self.L = lib()
         self.cfg = cfg
-        self.h = self.L.jsmpeg_hip_ts_program_create(ctypes.byref(cfg))
-        if not self.h:
-            raise RuntimeError("jsmpeg_hip_ts_program_create: " + _batch.last_error())
+        self._open(lib(), SIGNATURES, cfg)
         self.n_v = self.n_a = 0
-
-    def _ok(self, rc):
-        if rc < 0:
-            raise RuntimeError(_batch.last_error())
-        return rc
-
-    def close(self):
-        if self.h:
-            self.L.jsmpeg_hip_ts_program_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def set_output(self, dev_ts, cap):
         """the calls write into the caller's device buffer (4-byte aligned, cap bytes); None: the handle's own again"""
-        self._ok(self.L.jsmpeg_hip_ts_program_set_output(self.h, dev_ts, int(cap)))
+        self._call("set_output", dev_ts, int(cap))
 
     def mux(self, dev_video=None, v_ranges=(), v_pts=(), v_streams=None, dev_audio=None, a_ranges=(), a_pts=(), a_streams=None, stream=None):
         """dev_video / dev_audio: device addresses; v_ranges / a_ranges = [(offset, bytes)], one PES per range; v_pts / a_pts:
         90 kHz integers, unwrapped, non-decreasing within a stream; v_streams / a_streams: ascending stream numbers (None: all
         0); stream: the HIP stream to enqueue on -- the one the bytes were produced on"""
         v, a = _Table(v_ranges, v_pts, v_streams, "video"), _Table(a_ranges, a_pts, a_streams, "audio")
-        self._ok(self.L.jsmpeg_hip_ts_program_mux(*([self.h] + v.args(dev_video) + a.args(dev_audio) + [stream])))
+        self._call("mux", *(v.args(dev_video) + a.args(dev_audio) + [stream]))
         self.n_v, self.n_a = v.n, a.n
 
     def mux_encoders(self, encoder=None, mp2_encoder=None, v_pts=None, a_pts=None, stream=None):
@@ -198,34 +161,21 @@ class TsProgram:
         n_v, n_a = (encoder.count if encoder is not None else 0), (mp2_encoder.count if mp2_encoder is not None else 0)
         if (vp is not None and vp.shape != (n_v,)) or (ap is not None and ap.shape != (n_a,)):
             raise ValueError("mux_encoders: one pts per picture / frame of the encoders' last calls")
-        self._ok(self.L.jsmpeg_hip_ts_program_mux_encoders(self.h, encoder.h if encoder is not None else None, None if vp is None else vp.ctypes.data,
-                                                           mp2_encoder.h if mp2_encoder is not None else None, None if ap is None else ap.ctypes.data, stream))
+        self._call("mux_encoders", encoder.h if encoder is not None else None, None if vp is None else vp.ctypes.data,
+                   mp2_encoder.h if mp2_encoder is not None else None, None if ap is None else ap.ctypes.data, stream)
         self.n_v, self.n_a = n_v, n_a
-
-    def sync(self):
-        self._ok(self.L.jsmpeg_hip_ts_program_sync(self.h))
-
-    def query(self):
-        """True once the pass in flight has finished on the device; never waits"""
-        return bool(self._ok(self.L.jsmpeg_hip_ts_program_query(self.h)))
 
     def device_ts(self):
         """(device address, total bytes) of the last call's buffer"""
-        total = ctypes.c_uint64()
-        p = self.L.jsmpeg_hip_ts_program_ts(self.h, ctypes.byref(total))
-        if not p:
-            raise RuntimeError(_batch.last_error())
-        return p, int(total.value)
+        return self._buffer("ts")
 
     def stream_range(self, stream):
-        b, e = ctypes.c_uint64(), ctypes.c_uint64()
-        self._ok(self.L.jsmpeg_hip_ts_program_stream_range(self.h, stream, ctypes.byref(b), ctypes.byref(e)))
-        return int(b.value), int(e.value)
+        return self._pair("stream_range", stream)
 
     def _read(self, stream):
-        n = self._ok(self.L.jsmpeg_hip_ts_program_read(self.h, stream, None, 0))
+        n = self._call("read", stream, None, 0)
         out = np.empty(max(1, n), dtype=np.uint8)
-        self._ok(self.L.jsmpeg_hip_ts_program_read(self.h, stream, out.ctypes.data, n))
+        self._call("read", stream, out.ctypes.data, n)
         return out[:n]
 
     def ts(self, stream=0):
@@ -247,25 +197,20 @@ class TsProgram:
         out = []
         for k in range(self.n_a if kind else self.n_v):
             o, b, p = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
-            self._ok(self.L.jsmpeg_hip_ts_program_unit_range(self.h, kind, k, ctypes.byref(o), ctypes.byref(b), ctypes.byref(p)))
+            self._call("unit_range", kind, k, ctypes.byref(o), ctypes.byref(b), ctypes.byref(p))
             out.append((int(o.value), int(b.value), int(p.value)))
         return out
 
     def state(self, stream):
         """[PAT, PMT, video, audio counters, started] of a stream number behind the last call"""
         out = (ctypes.c_uint32 * 5)()
-        self._ok(self.L.jsmpeg_hip_ts_program_state(self.h, stream, out))
+        self._call("state", stream, out)
         return [int(v) for v in out]
 
     def set_state(self, stream, words):
         """sets the five words of a stream number: a relay that restarts goes on where its streams were"""
-        self._ok(self.L.jsmpeg_hip_ts_program_set_state(self.h, stream, (ctypes.c_uint32 * 5)(*[int(w) for w in words])))
+        self._call("set_state", stream, (ctypes.c_uint32 * 5)(*[int(w) for w in words]))
 
     def reset(self, stream=None):
         """zeroes the five words of `stream` (None: of every stream): its next unit gets PSI in front again"""
-        self._ok(self.L.jsmpeg_hip_ts_program_reset(self.h, ALL if stream is None else stream))
-
-    def timings(self):
-        ms = (ctypes.c_float * 2)()
-        self._ok(self.L.jsmpeg_hip_ts_program_timings(self.h, ms))
-        return dict(mux_ms=float(ms[0]), total_ms=float(ms[1]))
+        self._call("reset", ALL if stream is None else stream)
